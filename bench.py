@@ -2,8 +2,14 @@
 """Benchmark of the two hot paths (BASELINE.json metric:
 "RQ-VAE items encoded/s + SASRec seqs scored/s @1/8 GPU; HR@10/NDCG@10 parity").
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
+
+A plain run sets up the headline workload (C2, below), warms it up for W steps, times K steps and
+prints the result line (``value``, ``ms_per_step``); ``--dump-outputs DIR`` also writes what the
+K-th timed step returned (the [items, 3] semantic IDs, as float64) to ``DIR/rq_c2_indices.npy`` --
+the inputs are seeded, so two builds can be compared output for output.  Everything else below --
+the other legs, the rooflines and per-kernel timings, the CPU baselines -- runs with ``--full``.
 
 ``python bench.py --gpus N`` (N > 1) outside torch.distributed.run launches its N ranks itself: the
 parent imports neither torch nor gr_amd, runs ``torch.distributed.run`` as a child process (one rank
@@ -163,6 +169,11 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="every leg (" + ",".join(LEGS) + "), the CPU baselines and the per-kernel / roofline "
+                         "figures; without it only the C2 headline is set up, warmed up and timed")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed C2 step returned as DIR/<name>.npy")
     ap.add_argument("--rq-items", type=int, default=100_000)
     ap.add_argument("--sas-batch", type=int, default=2048)
     ap.add_argument("--c4-items", type=int, default=10_000_000)
@@ -180,8 +191,8 @@ def parse():
                     help="user sub-batches per step of the split exchange")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--train-batch", type=int, default=128, help="sas_train leg: users per rank per step")
-    ap.add_argument("--legs", default="", help="comma list of legs to run (default: " + ",".join(LEGS) + "; also " + ",".join(OPT_LEGS) + ")")
-    ap.add_argument("--skip", default="", help="comma list of legs to skip")
+    ap.add_argument("--legs", default="", help="with --full: comma list of legs to run (default: " + ",".join(LEGS) + "; also " + ",".join(OPT_LEGS) + ")")
+    ap.add_argument("--skip", default="", help="with --full: comma list of legs to skip")
     ap.add_argument("--spinup-s", type=float, default=1.0,
                     help="untimed seconds of each leg's workload before its warmup (clock ramp)")
     return ap.parse_args()
@@ -222,13 +233,14 @@ def spinup(fn, seconds=None, world=1):
             torch.cuda.synchronize()
 
 
-def timed(fn, steps, warmup, world, tail=None):
+def timed(fn, steps, warmup, world, tail=None, last=None):
     """Spin-up, W untimed warmup steps, then exactly K steps between barrier+synchronize; returns
     (max-over-ranks wall seconds, mean device ms per step from two HIP events on the launch stream
     around the K steps -- no markers between steps, which would themselves open dispatch gaps).
     ``tail``: a step that leaves work for the next one (the cross-step C5 exchange) is completed by
     it -- once before the timed region (the warmup's leftover) and once inside it, after the K
-    steps, so the region holds exactly K steps' work."""
+    steps, so the region holds exactly K steps' work.  ``last``: a list that receives what the
+    K-th timed step returned (the other steps' results are dropped at once, as before)."""
     spinup(fn, world=world)
     for _ in range(warmup):
         fn()
@@ -238,13 +250,17 @@ def timed(fn, steps, warmup, world, tail=None):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     t0 = time.perf_counter()
     e0.record()
-    for _ in range(steps):
+    for _ in range(steps - 1):
         fn()
+    out = fn()
     if tail is not None:
         tail()
     e1.record()
     sync_all(world)
     wall = time.perf_counter() - t0
+    if last is not None:
+        last.append(out)
+    del out
     dev_ms = e0.elapsed_time(e1) / steps
     if world > 1:
         t = torch.tensor([wall], dtype=torch.float64, device="cuda")
@@ -486,17 +502,32 @@ def cpu_sas_baseline(model, B, n, items, tag, table=None, params=None):
                       agree=lambda out: sas_agreement(out, gpu_logits))
 
 
+def dump_outputs(path, arrays, rank, budget=64 << 20):
+    """--dump-outputs: ``arrays`` (name -> tensor) as ``path/<name>.npy`` (``<name>.rank<r>.npy`` on
+    ranks above 0), float64.  An array over its share of ``budget`` bytes is cut to a fixed seeded
+    sample of its rows, the same rows on every run."""
+    os.makedirs(path, exist_ok=True)
+    share = budget // max(1, len(arrays))
+    for name, t in arrays.items():
+        v = t.detach().cpu().to(torch.float64).numpy()
+        v = v.reshape(v.shape[0], -1) if v.ndim > 1 else v.reshape(-1, 1)
+        keep = share // (8 * v.shape[1])
+        if v.shape[0] > keep:
+            v = v[np.sort(np.random.default_rng(0).choice(v.shape[0], keep, replace=False))]
+        np.save(os.path.join(path, name + (f".rank{rank}" if rank else "") + ".npy"), v)
+
+
 def bench_rq_c2(a, world, rank, dev):
+    """The headline: ``--warmup`` + ``--steps`` calls of RQVAE.get_indices on seeded inputs.  A plain
+    run stops after the timed steps; ``--full`` adds the quantize kernel timed alone and the roofline."""
     L, K = 3, 256
     model = synth.rqvae_model(L, K, dev)
     x = synth.items(a.rq_items, 1000 + rank, dev)
-    wall, dev_ms = timed(lambda: model.get_indices(x), a.steps, a.warmup, world)
-    # the encoder's share of the call = the call minus the quantize kernel timed alone on the same
-    # z (ops.rq_mlp would also time the per-call weight pack that get_indices caches)
-    z = model.encoder(x)
-    cbs = model.rq.codebooks()
-    quant_ms = kernel_ms(lambda: ops.rq_quantize(z, cbs))
-    enc_ms = dev_ms - quant_ms
+    last = []
+    wall, dev_ms = timed(lambda: model.get_indices(x), a.steps, a.warmup, world, last=last)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"rq_c2_indices": last[0]}, rank)
+    del last
     line = {
         "metric": METRIC, "value": a.rq_items * world * a.steps / wall, "unit": "items/s",
         "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": wall / a.steps * 1e3,
@@ -506,6 +537,17 @@ def bench_rq_c2(a, world, rank, dev):
                                "e 32, data-derived codebooks, BERT-statistics item embeddings",
                    "items_per_rank_per_step": a.rq_items, "global_batch": a.rq_items * world,
                    "parallelism": f"item-sharded x{world}, no collective"},
+    }
+    if not a.full:
+        line["call"] = {"device_ms": dev_ms}
+        return line, model
+    # the encoder's share of the call = the call minus the quantize kernel timed alone on the same
+    # z (ops.rq_mlp would also time the per-call weight pack that get_indices caches)
+    z = model.encoder(x)
+    cbs = model.rq.codebooks()
+    quant_ms = kernel_ms(lambda: ops.rq_quantize(z, cbs))
+    enc_ms = dev_ms - quant_ms
+    line.update({
         "roofline": roofline("rq_encoder_kernel<256,128>", ENC_FLOP_PER_ITEM * a.rq_items, enc_ms, "c2",
                              call_kernels=["rq_encoder_kernel", "rq_leftover_kernel"],
                              note="the encoder launches of one call (rq_encoder_kernel, plus rq_leftover_kernel for "
@@ -517,7 +559,7 @@ def bench_rq_c2(a, world, rank, dev):
                  "frac_of_fp32_peak": rq_flop_per_item(L, K) * a.rq_items / (dev_ms * 1e-3) / 1e12 / FP32_PEAK_TFLOPS,
                  "hbm_algorithmic_GBs": rq_bytes_per_item(L) * a.rq_items / (dev_ms * 1e-3) / 1e9,
                  "quantize_ms": quant_ms},
-    }
+    })
     return line, model
 
 
@@ -1474,7 +1516,13 @@ def main():
     a = parse()
     global SPINUP_S
     SPINUP_S = a.spinup_s
-    legs = [l for l in (a.legs.split(",") if a.legs else LEGS) if l]
+    if a.steps < 1:
+        sys.exit("bench.py: --steps must be at least 1")
+    if not a.full and (a.legs or a.skip):
+        sys.exit("bench.py: --legs / --skip choose among the legs of a --full run")
+    # a plain run times the C2 headline and nothing else; every other leg, the CPU baselines and the
+    # per-kernel figures belong to --full
+    legs = [l for l in (a.legs.split(",") if a.legs else LEGS if a.full else ["c2"]) if l]
     skip = set(s for s in a.skip.split(",") if s)
     legs = [l for l in legs if l not in skip]
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -1498,7 +1546,7 @@ def main():
             dist.init_process_group("nccl", device_id=dev)
         else:
             dist.init_process_group(backend)
-    cpu = rank == 0 and world == 1 and not a.no_cpu_baseline
+    cpu = a.full and rank == 0 and world == 1 and not a.no_cpu_baseline
 
     if "c2" in legs:
         line, rq_model = bench_rq_c2(a, world, rank, dev)

@@ -26,7 +26,7 @@ for s in $STEPS; do
   case $s in
     tests) step pytest_gpu 1200 python -m pytest tests -m gpu -q -rs ;;
     smoke) step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) step bench 900 python bench.py ;;
+    bench) step bench 900 python bench.py --full ;;
     trace_rq)
       export TMPDIR=/tmp
       cd /tmp
@@ -38,7 +38,7 @@ for s in $STEPS; do
       export TMPDIR=/tmp
       cd /tmp
       step rocprof 900 rocprofv3 --kernel-trace --stats --output-format csv \
-          -d /tmp/gr_rocprof -o run -- python3 "$ROOT/bench.py" --steps 10 --warmup 3 --no-cpu-baseline
+          -d /tmp/gr_rocprof -o run -- python3 "$ROOT/bench.py" --full --steps 10 --warmup 3 --no-cpu-baseline
       # the full trace is tens of MB (gpurun copies back <= 64 MiB): keep the stats and a per-launch-shape summary
       mkdir -p "$OUT/rocprof"
       cp /tmp/gr_rocprof/run_kernel_stats.csv "$OUT/rocprof/" 2>/dev/null
@@ -51,7 +51,7 @@ for s in $STEPS; do
       for c in FETCH_SIZE WRITE_SIZE; do
         cd /tmp
         step pmc_$c 900 rocprofv3 --pmc $c --output-format csv \
-            -d "$OUT/pmc_$c" -o run -- python3 "$ROOT/bench.py" --steps 5 --warmup 2 --no-cpu-baseline
+            -d "$OUT/pmc_$c" -o run -- python3 "$ROOT/bench.py" --full --steps 5 --warmup 2 --no-cpu-baseline
         cd "$ROOT"
       done ;;
     pmc3)  # HBM bytes per kernel and bench leg (FETCH_SIZE / WRITE_SIZE, separate passes): scripts/pmc_legs.sh

@@ -1,6 +1,6 @@
 #!/bin/bash
 # HBM traffic per bench leg (MI355X_MICROARCH.md §HBM): rocprofv3 --pmc FETCH_SIZE and --pmc
-# WRITE_SIZE in separate passes over `bench.py --legs LEG`, raw output in /tmp on the box, summarised
+# WRITE_SIZE in separate passes over `bench.py --full --legs LEG`, raw output in /tmp, summarised
 # by scripts/pmc_traffic.py into gpurun_out/TAG/traffic.json (copy to profiles/traffic.json).
 # Usage: scripts/pmc_legs.sh TAG [legs...]   (default: c2 sasrec c5 shard train)
 set -u
@@ -16,7 +16,7 @@ for leg in $LEGS; do
   for c in FETCH_SIZE WRITE_SIZE; do
     rm -rf /tmp/gr_pmc_${leg}_$c
     timeout -k 10 240 rocprofv3 --pmc $c --output-format csv -d /tmp/gr_pmc_${leg}_$c -o run -- \
-      python3 "$ROOT/bench.py" --legs $leg --steps 3 --warmup 1 --no-cpu-baseline --spinup-s 0 \
+      python3 "$ROOT/bench.py" --full --legs $leg --steps 3 --warmup 1 --no-cpu-baseline --spinup-s 0 \
       > "$OUT/pmc_${leg}_$c.log" 2>&1
     rc=$?
     echo "pmc $leg $c rc=$rc"
