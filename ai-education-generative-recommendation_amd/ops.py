@@ -537,10 +537,10 @@ def rq_mlp(x, weights, biases, bn=None, act="relu", group_sizes=None):
             big = [i for i, g in enumerate(sizes) if all(k == "chain" for k, _ in plan(g))]
             while big:   # the kept groups' one call must have every kept group's own order
                 pb = plan(sum(sizes[i] for i in big))
-                keep = [i for i in big if plan(sizes[i]) == pb]
-                if keep == big:
+                kept = [i for i in big if plan(sizes[i]) == pb]   # (``keep`` holds the BN tensors alive)
+                if kept == big:
                     break
-                big = keep
+                big = kept
             small = [i for i in range(len(sizes)) if i not in set(big)]
             offs = [0]
             for g in sizes:

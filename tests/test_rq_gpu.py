@@ -312,6 +312,47 @@ def test_mlp_exact_activations_and_batchnorm(act, bn, dev):
     assert np.array_equal(got, ref)
 
 
+def test_rq_mlp_keeps_converted_batchnorm_stats_alive(dev):
+    """ops.rq_mlp with ``group_sizes`` and BatchNorm statistics passed as non-contiguous views: the
+    contiguous copies it makes must outlive the launches that read their raw pointers (the index
+    tensors of the group split are allocated in between and would otherwise reuse their memory).
+    Chain-sized and 1-15-row groups, so both the per-row and the MFMA branch run; the output is
+    bit-equal to the same call on contiguous statistics."""
+    from gr_amd import ops
+    from gr_amd.rqvae import MLPLayers
+    torch.manual_seed(11)
+    m = MLPLayers([96, 64, 48, 16], dropout=0.1, activation="relu", bn=True)
+    with torch.no_grad():
+        for mod in m.mlp_layers:
+            if isinstance(mod, torch.nn.BatchNorm1d):
+                mod.running_mean.normal_(0, 0.3)
+                mod.running_var.uniform_(0.5, 2.0)
+                mod.weight.normal_(1, 0.1)
+                mod.bias.normal_(0, 0.1)
+    m = m.to(dev).eval()
+    sizes = [40, 3, 64, 7, 16]
+    x = torch.randn(sum(sizes), 96, generator=torch.Generator().manual_seed(12)).to(dev)
+    lin = m.linears()
+    ws, bs = [l.weight.detach() for l in lin], [l.bias.detach() for l in lin]
+    means, vars_, bws, bbs, eps = m.bn_params()
+
+    def strided(ts):   # the same values as [::2] views of tensors twice as long
+        out = []
+        for t in ts:
+            buf = torch.full((2 * t.numel(),), float("nan"), device=dev)
+            buf[::2] = t
+            out.append(buf[::2])
+            assert not out[-1].is_contiguous() and torch.equal(out[-1], t)
+        return out
+
+    want = ops.rq_mlp(x, ws, bs, bn=(means, vars_, bws, bbs, eps), act="relu", group_sizes=sizes)
+    torch.cuda.synchronize()
+    got = ops.rq_mlp(x, ws, bs, bn=(strided(means), strided(vars_), strided(bws), strided(bbs), eps), act="relu",
+                     group_sizes=sizes)
+    assert bool(torch.isfinite(want).all())
+    assert torch.equal(got, want)
+
+
 @pytest.mark.parametrize("act", ["sigmoid", "tanh"])
 def test_mlp_smooth_activations_vs_torch(act, dev):
     """Sigmoid / Tanh MLPs (gr_linear_f32 epilogues): fp32-close to torch (1e-5 relative) -- torch's

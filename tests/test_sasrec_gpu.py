@@ -290,16 +290,23 @@ def test_tail_h_form_vs_full_block_and_oracle(d, heads, n, blocks, B, dev):
 @pytest.mark.parametrize("heads", [1, 2])
 def test_tail_reduction_forms_bitwise(heads, dev):
     """sas_tail_h2_kernel's two reduction forms (gr_common.h xsum on the VALU when B <= CUs, ds_bpermute
-    above) are the same sums: rows of a 600-sequence call (ds_bpermute form) equal the same rows
-    computed in a 100-sequence call (VALU form) bit for bit."""
+    above) are the same sums: rows of a call of more sequences than the device has CUs (ds_bpermute
+    form) equal the same rows computed in a call of at most that many (VALU form) bit for bit.  The
+    two batches are sized from the device's CU count, so the two forms are compared on any device."""
     from gr_amd import synth
     d, n, items = 128, 200, 3000
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    if cus < 1:
+        pytest.skip("the device reports no compute units: no batch can take the VALU form")
+    b_small, b_big = min(100, cus), cus + 88
+    assert b_small <= cus < b_big
     p = synth.sasrec_params(d, n, 2, heads, 64, dev)
     m = synth.sasrec_model(items, p, dev, seed=91 + heads)
-    seqs = synth.sequences(600, n, items, 97, dev)
+    seqs = synth.sequences(b_big, n, items, 97, dev)
+    lo = (b_big - b_small) // 2                      # rows from inside both calls
     big = m.last_hidden(seqs)
-    small = m.last_hidden(seqs[200:300].contiguous())
-    assert torch.equal(big[200:300], small)
+    small = m.last_hidden(seqs[lo:lo + b_small].contiguous())
+    assert torch.equal(big[lo:lo + b_small], small)
 
 
 @pytest.mark.parametrize("d,heads,n,blocks,B", [(128, 1, 200, 2, 37), (128, 2, 130, 2, 9), (64, 1, 100, 2, 17),
