@@ -19,12 +19,28 @@
 //       the x chunk ([32FP x 64]) is shared through a double-buffered LDS image staged one chunk
 //       ahead (across pass boundaries too).  At the MKL block boundary the first block's sum plus
 //       the bias moves to registers and the chain restarts from zero.
-//   L2  h2^T[128 x 32FP] = W2 . relu(h1)^T   waves 0-3, wave w owns features [32w, 32w+32)
-//   L3  z^T[32 x 32FP] = W3 . relu(h2)^T     16x16x4 MFMA tiles (also an fma chain in k order),
-//       one per wave, each the whole k = 128 chain, W3 from an LDS copy staged at kernel start
+//   L2  h2^T[128 x 32FP] = W2 . relu(h1)^T   v_mfma_f32_16x16x4_f32 (also one fma chain in k order,
+//       rq_small.hip): all 8 waves, wave w owns features [16w, 16w+16) for the pass's four 16-item
+//       tiles -- four independent K = 256 chains per wave, two waves per SIMD (the 0.934 point of
+//       profiles/r02_mfma_rate.txt; the 32x32x2 form on waves 0-3 ran two chains on one wave per
+//       SIMD, 0.835).  W2 comes in the 16x16x4 order (image 4 of the pack), its first four blocks'
+//       fragments stay in registers for the whole kernel; h1 sits in LDS in that order, k-group
+//       pairs flipped in rows 4..11 of 16 so that the ds_read_b128 lane groups are conflict-free.
+//   L3  z^T[32 x 32FP] = W3 . relu(h2)^T     16x16x4 MFMA tiles, one per wave, each the whole
+//       k = 128 chain, W3 from an LDS copy staged at kernel start
+// Every bias fragment is loaded a phase ahead of its use (b1 before the chunk loops, b2 and b3 at
+// the start of L2): a load first issued after a loop is an L2 round trip that both waves of a SIMD
+// wait out together, four times per pass (profiles/r07/ab_rq_parts.txt).
+// The tiles past (tiles / CUs) whole tiles per workgroup run layer 1 as feature pieces spread over
+// the workgroups -- quarters while every piece gets a workgroup of its own, halves past that -- and
+// rq_leftover_kernel (8 waves, the same L2 / L3) finishes them.
 #include <type_traits>
 
 #include "gr_common.h"
+
+#ifndef GR_EDIAG
+#define GR_EDIAG 0   // diagnostic builds only (scripts/build_variant.sh; wrong results, timing only): 1 no
+#endif               // layer 2, 2 no layer 3 / z store, 3 no leftover pieces and no rq_leftover_kernel
 
 namespace gr {
 
@@ -44,6 +60,14 @@ struct FusedCfg {
   static constexpr int LDS = 2 * PI * FXP + PI * P1 + PI * P2 + E * P3;
   static_assert(H1 == 32 * FWV && H2 == 128, "8-wave form: H1 = 256, H2 = 128");
 };
+
+// A 16-byte load from a pointer known to be global memory.  The weight and bias pointers of the later
+// phases pass through an empty asm (rq_fused_pass) and come out without their address space; a plain
+// dereference is then a flat load, which counts on lgkmcnt as well as vmcnt -- every LDS wait behind
+// it (the next ds_read's, a barrier's) waits out its L2 round trip too.
+__device__ __forceinline__ f32x4 ldg4(const float* p) {
+  return *reinterpret_cast<const __attribute__((address_space(1))) f32x4*>(reinterpret_cast<uintptr_t>(p));
+}
 
 // Packed-order position of the 4 consecutive features k0..k0+3 (k0 % 4 == 0) of a 32-deep group:
 // feature 8j + 2s + h sits at 16h + 4j + s, so a float4 splits into two 8-byte halves.
@@ -73,6 +97,7 @@ struct FusedCtx {
   const float* w1row;
   f32x4 awc[4];           // W1 fragments of the current 32-deep group
   f32x4 awc2[4];          // k-split pass: the same for the second MKL block's chain
+  f32x4 w2f[4];           // L2: W2 fragments of the first four 16-deep blocks (the same every pass)
   f32x4 xr[C::XV];
   bool xok[C::XV];
   int buf;
@@ -100,86 +125,96 @@ struct FusedCtx {
   }
 };
 
-// h^T accumulator (feature rows 8g4 + 4h + i of a 32-feature tile, item column r) -> packed LDS row.
-// Features 8g4 + 4h + i = 8j + 2s + hh with j = g4, s = 2h + (i >> 1), hh = i & 1.
-__device__ __forceinline__ void store_h_packed(float* row, int g4, int h, const f32x4& o) {
-  *reinterpret_cast<f32x2*>(row + 4 * g4 + 2 * h) = f32x2{o[0], o[2]};
-  *reinterpret_cast<f32x2*>(row + 16 + 4 * g4 + 2 * h) = f32x2{o[1], o[3]};
+// The h1 image is in the 16x16x4 ("transposed") order L2 reads: within every 16-feature block,
+// feature 4t + g sits at 4 (g ^ x) + t, where x = h1_swz(row) flips the block's k-group pairs in
+// rows 4..11 of every 16.  A 16x16x4 lane (j, g) reads row 16 tile + j at 16b + 4 (g ^ x) as one
+// float4 (four k steps); with a pitch == 4 mod 64 the sixteen lanes of every ds_read_b128 lane
+// group ({0-3, 12-15} of one g with {4-11} of g ^ 1, MI355X LDS) then start at sixteen different
+// multiples of four banks -- without the flip lanes 12 and 27 (and 19 and 8) share banks.
+__device__ __forceinline__ int h1_swz(int row) { return ((row >> 2) ^ (row >> 3)) & 1; }
+
+// L1 h^T accumulator (feature rows 8g4 + 4h + i of a 32-feature tile, item column r) -> the h1
+// image row: feature 8g4 + 4h + i = 16 (g4 >> 1) + 4t + g with t = 2 (g4 & 1) + h, g = i.
+__device__ __forceinline__ void store_h1(float* row, int x, int g4, int h, const f32x4& o) {
+  float* p = row + 16 * (g4 >> 1) + 2 * (g4 & 1) + h;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) p[4 * (i ^ x)] = o[i];
 }
 
-// Layers 2 and 3 of NR item tiles whose relu(h1) sits packed in cx.h1s: z = W3 . relu(W2 . h1 + b2)
-// + b3 for tiles tb .. tb + NR - 1, written to cx.z_out.
+// Layers 2 and 3 of NR item tiles whose relu(h1) sits in cx.h1s (8 waves): z = W3 . relu(W2 . h1 +
+// b2) + b3 for tiles tb .. tb + NR - 1, written to cx.z_out.  cx.W2 is the 16x16x4-order image.
 template <int NR, int H1, int H2>
 __device__ __forceinline__ void rq_l23(FusedCtx<H1, H2>& cx, int tb) {
 #pragma clang fp contract(off)
   using C = FusedCfg<H1, H2>;
   constexpr int E = C::E, P1 = C::P1, P2 = C::P2;
-  const int w = cx.w, r = cx.r, h = cx.h;
+  const int w = cx.w, lane = cx.tid & 63, j = lane & 15, g = lane >> 4;
+  f32x4 bb3;   // L3's bias fragment (output half w & 1)
   // ------------------------------------------------------------------ L2: W2 . h1^T
-  // waves 0-3: wave w, features [32w, 32w + 32) for all NR item tiles (NR accumulator chains per
-  // wave); waves 4-7 skip L2 (splitting it into one chain per wave over all 8 measured 483 vs 462
-  // us per C2 call, profiles/r02_ab_quant_ablation.txt)
-  if (w < 4) {
-    f32x16 acc2[NR];
+  // v_mfma_f32_16x16x4_f32 (one fma chain over k in order, as L3): wave w owns features [16w, 16w +
+  // 16) for the pass's NT 16-item tiles -- NT independent chains of K = 256 per wave on all 8 waves
+  // (2 waves per SIMD), W2 fragments from L2 pipelined four 16-deep blocks ahead.
+  {
+    constexpr int NT = 2 * NR, UB = 4, NI = H1 / (16 * UB);
+    f32x4 acc2[NT];
 #pragma unroll
-    for (int it = 0; it < NR; ++it)
+    for (int it = 0; it < NT; ++it) acc2[it] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const float* hb = cx.h1s + j * P1 + 4 * (g ^ h1_swz(j));
+    const float* w2row = cx.W2 + (int64_t)(w * 16 + j) * H1 + 4 * g;
+    // the first UB blocks' fragments are the same for every pass: loaded once per workgroup
+    // (cx.w2f), so the phase does not start on an L2 round trip; the biases of this phase and of
+    // L3 are fetched here, a whole phase before their use (a load placed after the loops would be
+    // issued there, and both waves of a SIMD would wait for it together)
+    f32x4 aw2[UB];
 #pragma unroll
-      for (int v = 0; v < 16; ++v) acc2[it][v] = 0.f;
-    const float* hb = cx.h1s + r * P1 + 16 * h;
-    const float* w2row = cx.W2 + (int64_t)(w * 32 + r) * H1 + 16 * h;
-    f32x4 aw2[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) aw2[j] = *reinterpret_cast<const f32x4*>(w2row + 4 * j);
+    for (int u = 0; u < UB; ++u) aw2[u] = cx.w2f[u];
+    const f32x4 bb = ldg4(cx.b2 + w * 16 + 4 * g);
+    bb3 = ldg4(cx.b3 + 16 * (w & 1) + 4 * g);
+    asm volatile("" ::: "memory");
 #pragma unroll 1
-    for (int g = 0; g < H1 / 32; ++g) {
-      const int gn = (g + 1 < H1 / 32) ? g + 1 : g;
-      f32x4 awn[4];
+    for (int bi = 0; bi < (GR_EDIAG == 1 ? 0 : NI); ++bi) {
+      const int bn = (bi + 1 < NI) ? bi + 1 : bi;
+      f32x4 awn[UB];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) awn[j] = *reinterpret_cast<const f32x4*>(w2row + gn * 32 + 4 * j);
-      f32x4 bx[NR][4];
+      for (int u = 0; u < UB; ++u) awn[u] = ldg4(w2row + 16 * (bn * UB + u));
+      f32x4 bx[UB][NT];
 #pragma unroll
-      for (int it = 0; it < NR; ++it)
+      for (int u = 0; u < UB; ++u)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) bx[it][j] = *reinterpret_cast<const f32x4*>(hb + it * FT * P1 + g * 32 + 4 * j);
+        for (int it = 0; it < NT; ++it)
+          bx[u][it] = *reinterpret_cast<const f32x4*>(hb + it * 16 * P1 + 16 * (bi * UB + u));
 #pragma unroll
-      for (int it = 0; it < NR; ++it)
+      for (int u = 0; u < UB; ++u)
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
+        for (int t = 0; t < 4; ++t)
 #pragma unroll
-          for (int s = 0; s < 4; ++s) acc2[it] = mfma32(aw2[j][s], bx[it][j][s], acc2[it]);
-      // same interleave as L1: item tile 0's h1 fragments first, then one load per MFMA
-      __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
+          for (int it = 0; it < NT; ++it) acc2[it] = mfma16(aw2[u][t], bx[u][it][t], acc2[it]);
+      // same interleave as L1: the first block's h1 fragments, then one load per MFMA
+      __builtin_amdgcn_sched_group_barrier(0x100, NT, 0);
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
+      for (int i = 0; i < UB; ++i) {
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
         __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
       }
 #pragma unroll
-      for (int i = 0; i < 4 * (NR - 1); ++i) {
+      for (int i = 0; i < (UB - 1) * NT; ++i) {
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
         __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
       }
-      __builtin_amdgcn_sched_group_barrier(0x008, 16 * NR - 4 - 4 * (NR - 1), 0);
+      __builtin_amdgcn_sched_group_barrier(0x008, 4 * UB * NT - UB - (UB - 1) * NT, 0);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) aw2[j] = awn[j];
+      for (int u = 0; u < UB; ++u) aw2[u] = awn[u];
     }
+    // acc2[it][i]: feature 16w + 4g + i of item 16 it + j.  L3 layout: within each 16-feature
+    // block, feature 4t + g at 4g + t (a lane of k group g reads four consecutive 16x16x4 steps
+    // as one float4)
 #pragma unroll
-    for (int g4 = 0; g4 < 4; ++g4) {
-      const f32x4 bb = *reinterpret_cast<const f32x4*>(cx.b2 + w * 32 + 8 * g4 + 4 * h);
+    for (int it = 0; it < NT; ++it) {
+      float* row = cx.h2s + (it * 16 + j) * P2 + w * 16 + g;
 #pragma unroll
-      for (int it = 0; it < NR; ++it) {
-        f32x4 o;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float u = bb[i] + acc2[it][4 * g4 + i];
-          o[i] = u < 0.f ? 0.f : u;
-        }
-        // L3 layout: within each 16-feature block, feature 4t + g at 4g + t (a lane of k group g
-        // reads four consecutive 16x16x4 steps as one float4)
-        float* row = cx.h2s + (it * FT + r) * P2 + w * 32 + 16 * (g4 >> 1);
-        const int t = (2 * g4 + h) & 3;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) row[4 * i + t] = o[i];
+      for (int i = 0; i < 4; ++i) {
+        const float u = bb[i] + acc2[it][i];
+        row[4 * i] = u < 0.f ? 0.f : u;
       }
     }
   }
@@ -189,9 +224,8 @@ __device__ __forceinline__ void rq_l23(FusedCtx<H1, H2>& cx, int tb) {
   // 16x16x4 tiles (16 outputs x 16 items), one per wave: item tile w >> 2, item half (w >> 1) & 1,
   // output half w & 1; one k-ordered chain over k = 0..127 (32 MFMAs), z = b3 + chain, to HBM.
   // W3 arrives packed for this form: feature 16b + 4t + g of a row at 16b + 4g + t.
-  if (w < 4 * NR) {
+  if (GR_EDIAG != 2 && w < 4 * NR) {
     const int it = w >> 2, ih = (w >> 1) & 1, oh = w & 1;
-    const int lane = cx.tid & 63, j = lane & 15, g = lane >> 4;
     f32x4 acc3 = {0.f, 0.f, 0.f, 0.f};
     const float* hb = cx.h2s + (it * FT + 16 * ih + j) * P2 + 4 * g;
     const float* w3row = cx.w3s + (16 * oh + j) * C::P3 + 4 * g;   // LDS: rows 4 banks apart
@@ -204,10 +238,9 @@ __device__ __forceinline__ void rq_l23(FusedCtx<H1, H2>& cx, int tb) {
     }
     const int64_t item = (int64_t)(tb + it) * FT + 16 * ih + j;
     if (item < cx.n) {
-      const f32x4 bb = *reinterpret_cast<const f32x4*>(cx.b3 + 16 * oh + 4 * g);
       f32x4 o;
 #pragma unroll
-      for (int i = 0; i < 4; ++i) o[i] = bb[i] + acc3[i];
+      for (int i = 0; i < 4; ++i) o[i] = bb3[i] + acc3[i];
       *reinterpret_cast<f32x4*>(cx.z_out + item * E + 16 * oh + 4 * g) = o;
     }
   }
@@ -351,6 +384,12 @@ __device__ __forceinline__ void rq_fused_pass(FusedCtx<H1, H2>& cx, int tb, int 
   };
   int c = 0;
   f32x16 part[NP];
+  // b1 is fetched before the chunk loops (after them both waves of a SIMD would wait out the L2
+  // round trip together); it is live only while `part` is not
+  f32x4 b1f[4];
+#pragma unroll
+  for (int g4 = 0; g4 < 4; ++g4) b1f[g4] = ldg4(cx.b1 + f0 + 8 * g4 + 4 * h);
+  asm volatile("" ::: "memory");
   if constexpr (KS) {
     // the second block's first W1 group (the previous pass's prefetch wrapped the first stream only)
 #pragma unroll
@@ -360,7 +399,7 @@ __device__ __forceinline__ void rq_fused_pass(FusedCtx<H1, H2>& cx, int tb, int 
     // block 0 = chain 0, block 1 = chain 1: y = (b1 + block 0) + block 1
 #pragma unroll
     for (int g4 = 0; g4 < 4; ++g4) {
-      const f32x4 bb = *reinterpret_cast<const f32x4*>(cx.b1 + f0 + 8 * g4 + 4 * h);
+      const f32x4 bb = b1f[g4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) part[0][4 * g4 + i] = bb[i] + acc1[0][4 * g4 + i];
     }
@@ -374,7 +413,7 @@ __device__ __forceinline__ void rq_fused_pass(FusedCtx<H1, H2>& cx, int tb, int 
     // part + 0 below is exact (part is never -0: the chain starts from +0).
 #pragma unroll
     for (int g4 = 0; g4 < 4; ++g4) {
-      const f32x4 bb = *reinterpret_cast<const f32x4*>(cx.b1 + f0 + 8 * g4 + 4 * h);
+      const f32x4 bb = b1f[g4];
 #pragma unroll
       for (int it = 0; it < NP; ++it)
 #pragma unroll
@@ -398,7 +437,7 @@ __device__ __forceinline__ void rq_fused_pass(FusedCtx<H1, H2>& cx, int tb, int 
         const float u = part[it][4 * g4 + i] + acc1[it][4 * g4 + i];
         o[i] = u < 0.f ? 0.f : u;
       }
-      store_h_packed(cx.h1s + (it * FT + r) * P1 + f0, g4, h, o);
+      store_h1(cx.h1s + (it * FT + r) * P1 + f0, h1_swz(r), g4, h, o);
     }
   __syncthreads();
 
@@ -415,7 +454,8 @@ __device__ __forceinline__ void rq_fused_pass(FusedCtx<H1, H2>& cx, int tb, int 
 // rows [FT, 2 FT): block 1's); the block-1 waves hand their sums to the block-0 waves through LDS,
 // which form y = (b1 + block 0) + block 1 exactly as every other pass.  The x image's chunk 0 is
 // already staged (k-split layout) by the pass before; chunk NC/2 - 1 prefetches nothing.
-// PF = 64 (quarter pieces, the short-call plan): waves 0-3 only (feature group w & 1, block w >> 1,
+// PF = 64 (quarter pieces: the short-call plan, and any call whose 4 r pieces fit the grid -- C2's
+// 53 leftover tiles are 212 pieces on 256 workgroups, half the piece time): waves 0-3 only (feature group w & 1, block w >> 1,
 // one chain per SIMD); waves 4-7 stage x and keep the barriers.
 template <int H1, int H2, int PF = 128>
 __device__ __forceinline__ void rq_piece_pass(FusedCtx<H1, H2>& cx, int tb, int fh, float* __restrict__ h1g,
@@ -495,7 +535,7 @@ __device__ __forceinline__ void rq_piece_pass(FusedCtx<H1, H2>& cx, int tb, int 
     const int64_t item = (int64_t)tb * FT + r;
 #pragma unroll
     for (int g4 = 0; g4 < 4; ++g4) {
-      const f32x4 bb = *reinterpret_cast<const f32x4*>(cx.b1 + f0 + 8 * g4 + 4 * h);
+      const f32x4 bb = ldg4(cx.b1 + f0 + 8 * g4 + 4 * h);
       const f32x4 a1 = *reinterpret_cast<const f32x4*>(hand + 4 * g4);
       f32x4 o;
 #pragma unroll
@@ -511,7 +551,8 @@ __device__ __forceinline__ void rq_piece_pass(FusedCtx<H1, H2>& cx, int tb, int 
 }
 
 // Partition: q = tiles / grid whole tiles per workgroup (contiguous); the r = tiles % grid tiles
-// past q x grid run as 2 r feature-half pieces (rq_piece_pass), workgroup b taking pieces b, b + G.
+// past q x grid run as pq r feature pieces (rq_piece_pass: pq = 4 quarters when 4 r <= G, else 2
+// halves), workgroup b taking pieces b, b + G.
 template <int H1, int H2>
 __global__ __launch_bounds__(64 * FWV, 1) void rq_encoder_kernel(
     const float* __restrict__ x, int64_t n, int D0, int csplit, const float* __restrict__ W1,
@@ -520,9 +561,9 @@ __global__ __launch_bounds__(64 * FWV, 1) void rq_encoder_kernel(
     int tiles, float* __restrict__ h1g, int pq) {
   using C = FusedCfg<H1, H2>;
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  // pq: pieces per leftover tile (2: feature halves; 4: quarters, the short-call plan)
+  // pq: pieces per leftover tile (2: feature halves; 4: quarters, one workgroup per piece)
   const int G = gridDim.x, q = tiles / G, b = blockIdx.x;
-  const int npieces = h1g ? pq * (tiles - q * G) : 0;
+  const int npieces = (h1g && GR_EDIAG != 3) ? pq * (tiles - q * G) : 0;
   const int t_begin = h1g ? b * q : (int)((int64_t)b * tiles / G);
   const int t_end = h1g ? t_begin + q : (int)((int64_t)(b + 1) * tiles / G);
   const int piece0 = b < npieces ? b : -1;          // this workgroup's first piece
@@ -546,6 +587,9 @@ __global__ __launch_bounds__(64 * FWV, 1) void rq_encoder_kernel(
   cx.w1row = W1 + (int64_t)(cx.w * 32 + cx.r) * D0 + 16 * cx.h;
 #pragma unroll
   for (int j = 0; j < 4; ++j) cx.awc[j] = *reinterpret_cast<const f32x4*>(cx.w1row + 4 * j);
+#pragma unroll
+  for (int u = 0; u < 4; ++u)
+    cx.w2f[u] = *reinterpret_cast<const f32x4*>(W2 + (int64_t)(cx.w * 16 + (lane & 15)) * H1 + 4 * (lane >> 4) + 16 * u);
   cx.buf = 0;
   // an odd last tile runs as a k-split pass when MKL's block edge halves the chunks (in = 768)
   const bool kso = 2 * csplit == cx.NC;
@@ -577,9 +621,10 @@ __global__ __launch_bounds__(64 * FWV, 1) void rq_encoder_kernel(
   }
 }
 
-// Layers 2-3 of the leftover tiles (one 4-wave workgroup each) from the pieces' relu(h1).
+// Layers 2-3 of the leftover tiles (one 8-wave workgroup each: layer 2 as two 16x16x4 chains per
+// wave, two waves per SIMD) from the pieces' relu(h1).
 template <int H1, int H2>
-__global__ __launch_bounds__(256) void rq_leftover_kernel(const float* __restrict__ h1g, int64_t n, int t0,
+__global__ __launch_bounds__(64 * FWV) void rq_leftover_kernel(const float* __restrict__ h1g, int64_t n, int t0,
                                                           const float* __restrict__ W2, const float* __restrict__ b2,
                                                           const float* __restrict__ W3, const float* __restrict__ b3,
                                                           float* __restrict__ z_out) {
@@ -588,17 +633,23 @@ __global__ __launch_bounds__(256) void rq_leftover_kernel(const float* __restric
   __shared__ __attribute__((aligned(16))) float h2s[FT * C::P2];
   __shared__ __attribute__((aligned(16))) float w3s[C::E * C::P3];
   const int tid = threadIdx.x, lane = tid & 63;
+  FusedCtx<H1, H2> cx;
+#pragma unroll
+  for (int u = 0; u < 4; ++u)   // in flight while the images are staged
+    cx.w2f[u] = *reinterpret_cast<const f32x4*>(W2 + (int64_t)((tid >> 6) * 16 + (lane & 15)) * H1 + 4 * (lane >> 4) + 16 * u);
   const float* src = h1g + (int64_t)blockIdx.x * FT * H1;
-  for (int f = tid; f < FT * H1 / 4; f += 256) {   // relu(h1) -> the packed h1 image
+  for (int f = tid; f < FT * H1 / 4; f += C::NTH) {   // relu(h1) -> the h1 image (16x16x4 order)
     const int row = f / (H1 / 4), k0 = (f % (H1 / 4)) * 4;
-    put_packed(h1s + row * C::P1, k0, *reinterpret_cast<const f32x4*>(src + row * H1 + k0));
+    const f32x4 v = *reinterpret_cast<const f32x4*>(src + row * H1 + k0);
+    float* p = h1s + row * C::P1 + (k0 & ~15) + ((k0 >> 2) & 3);   // features 16b + 4t + g, g = 0..3
+#pragma unroll
+    for (int g = 0; g < 4; ++g) p[4 * (g ^ h1_swz(row))] = v[g];
   }
-  for (int f = tid; f < C::E * H2 / 4; f += 256) {
+  for (int f = tid; f < C::E * H2 / 4; f += C::NTH) {
     const int row = f / (H2 / 4), qq = f % (H2 / 4);
     *reinterpret_cast<f32x4*>(w3s + row * C::P3 + 4 * qq) = *reinterpret_cast<const f32x4*>(W3 + row * H2 + 4 * qq);
   }
   __syncthreads();
-  FusedCtx<H1, H2> cx;
   cx.n = n; cx.W2 = W2; cx.b2 = b2; cx.W3 = W3; cx.b3 = b3; cx.z_out = z_out;
   cx.h1s = h1s; cx.h2s = h2s; cx.w3s = w3s;
   cx.tid = tid; cx.w = tid >> 6; cx.r = lane & 31; cx.h = lane >> 5;
@@ -608,7 +659,8 @@ __global__ __launch_bounds__(256) void rq_leftover_kernel(const float* __restric
 // Packed weight images (one launch), back to back in `out`: W1 and W2 for the 32x32x2 chains
 // (within every 32-deep k group, feature 8j + 2s + h at 16h + 4j + s), W3 for the 16x16x4 chain
 // (within every 16-deep block, feature 4t + g at 4g + t), then W1 and W2 again in the 16x16x4 order
-// for the short-call kernels (rq_small.hip).
+// for the short-call kernels (rq_small.hip); layer 2 here reads that last W2 image too (the 32x32x2
+// W2 image keeps its place in the layout and is no longer read).
 constexpr int PACK_IMAGES = 5;
 struct PackArgs {
   const float* w[PACK_IMAGES];
@@ -699,7 +751,7 @@ int gr_rq_encoder_fused_launch(const float* x, int64_t n, int32_t n_linear, cons
   // as four feature-quarter pieces, each on its own workgroup with one MKL-block chain per SIMD
   // (layer 1 in a quarter of the time of a whole-tile pass on one CU), and rq_leftover_kernel for
   // layers 2-3; otherwise one workgroup per CU over whole tiles with the tiles past q x grid as
-  // feature-half pieces
+  // feature pieces (pq below)
   const bool small = can_split && 4 * tiles <= cus;
   const int64_t grid = small ? 4 * tiles : tiles < cus ? tiles : cus;
   using Cfg = FusedCfg<256, 128>;
@@ -710,12 +762,16 @@ int gr_rq_encoder_fused_launch(const float* x, int64_t n, int32_t n_linear, cons
   // leftover-tile pieces when the MKL split halves the chunks (in = 768) and tiles % grid != 0
   const int64_t left = small ? tiles : tiles % grid;
   float* h1g = (can_split && left) ? scratch : nullptr;
+  // feature quarters while every piece still gets a workgroup of its own (half the piece time on
+  // twice the CUs), feature halves (at most two per workgroup) past that
+  const int pq = 4 * left <= grid ? 4 : 2;
+  // layer 2 reads W2 in the 16x16x4 order: image 4 of the pack
+  const float* w2t = wp[2] + 128 * 32 + (size_t)dims[0] * 256;
   hipLaunchKernelGGL((rq_encoder_kernel<256, 128>), dim3((unsigned)grid), dim3(64 * FWV), Cfg::LDS * sizeof(float), st, x, n,
-                     dims[0], csplit, wp[0], biases[0], wp[1], biases[1], wp[2], biases[2], z_out, (int)tiles, h1g,
-                     small ? 4 : 2);
+                     dims[0], csplit, wp[0], biases[0], w2t, biases[1], wp[2], biases[2], z_out, (int)tiles, h1g, pq);
   int rc = check_launch("rq fused encoder");
-  if (rc || !h1g) return rc;
-  hipLaunchKernelGGL((rq_leftover_kernel<256, 128>), dim3((unsigned)left), dim3(256), 0, st, h1g, n,
-                     (int)(tiles - left), wp[1], biases[1], wp[2], biases[2], z_out);
+  if (rc || !h1g || GR_EDIAG == 3) return rc;
+  hipLaunchKernelGGL((rq_leftover_kernel<256, 128>), dim3((unsigned)left), dim3(64 * FWV), 0, st, h1g, n,
+                     (int)(tiles - left), w2t, biases[1], wp[2], biases[2], z_out);
   return check_launch("rq fused encoder (leftover tiles)");
 }
