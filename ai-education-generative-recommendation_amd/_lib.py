@@ -209,9 +209,16 @@ def as_f32(t):
     return t.contiguous()
 
 
+# Counts set_option calls: a switch can change what a shape needs (sas_fused: a [B, d] workspace or the
+# layer-wise buffers), so sizes cached per shape (ops.SasrecBinding) are dropped when it moves.
+OPTION_EPOCH = 0
+
+
 def set_option(name, value):
     """gr_set_option (include/gr_amd.h): process-wide path / tuning switches."""
+    global OPTION_EPOCH
     check(lib().gr_set_option(name.encode(), int(value)), "gr_set_option")
+    OPTION_EPOCH += 1
 
 
 def get_option(name):

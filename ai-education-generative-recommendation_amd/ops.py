@@ -677,6 +677,7 @@ class SasrecBinding:
         self.p_ref = ctypes.byref(p)
         self.device = model.item_emb.weight.device
         self._ws = {}
+        self._ws_epoch = L.OPTION_EPOCH
 
     def _f(self, t):
         L.require_gpu(t)
@@ -690,9 +691,17 @@ class SasrecBinding:
         self.keep.append(a)
         return ctypes.cast(a, ctypes.c_void_p)
 
+    def _sizes(self):
+        """The per-shape size cache, emptied when a path switch has moved since it was filled (the
+        fused and the layer-wise forward of one shape need different workspaces)."""
+        if self._ws_epoch != L.OPTION_EPOCH:
+            self._ws.clear()
+            self._ws_epoch = L.OPTION_EPOCH
+        return self._ws
+
     def workspace_bytes(self, B, n):
         key = (0, B, n)
-        nb = self._ws.get(key)
+        nb = self._sizes().get(key)
         if nb is None:
             nb = L.lib().gr_sasrec_workspace_bytes(self.p_ref, B, n)
             if len(self._ws) < 256:
@@ -701,7 +710,7 @@ class SasrecBinding:
 
     def rank_workspace_bytes(self, B, n):
         key = (1, B, n)
-        nb = self._ws.get(key)
+        nb = self._sizes().get(key)
         if nb is None:
             nb = (L.lib().gr_sasrec_rank_workspace_bytes(self.p_ref, B, n),
                   L.lib().gr_score_count_workspace_bytes(B))

@@ -8,8 +8,11 @@ stays bounded at the 1M-row catalog.  Per user:
 
 * logits: ``|gpu - oracle| <= 1e-5 * max|row|`` (north_star's tolerance, row-scaled), every user;
 * ranks (SASRec/evaluate.py:27-32): exact for every user whose oracle target logit has no
-  competitor within 2 delta (delta = 1e-5 row scale, the logits bar); every user's GPU rank lies
-  in the band the logits bar allows, ``#{l > t + 2 delta} + 1 <= rank <= #{l > t - 2 delta} + 1``;
+  competitor within 2 delta; every user's GPU rank lies in the band
+  ``#{l > t + 2 delta} + 1 <= rank <= #{l > t - 2 delta} + 1``.  delta = BAND x row scale, the
+  triangle bound of a GPU logit against the fp32 oracle: the kernels' fp64 logits tolerance plus the
+  oracle's own worst distance from fp64 (tests/test_sasrec_infer_fp64_gpu.py: 3e-6 + 6.5e-7), about
+  a third of the 1e-5 bar; the whole-batch logits error is held to it as well;
 * HR@10 and NDCG@10 of the whole batch (evaluate.py:35-47, float64 ``np.mean``) equal the oracle's;
 * top-10 (C5, ``dist.sharded_rank_topk`` and an 8-shard merge on one GPU): values within delta of
   the oracle's value for the same id, ids equal to the oracle's top-10 wherever consecutive oracle
@@ -22,9 +25,11 @@ import pytest
 import torch
 
 from oracle import sasrec_oracle
+from test_sasrec_infer_fp64_gpu import T32_LOGITS, TOL_LOGITS
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
+BAND = TOL_LOGITS + T32_LOGITS   # |gpu - fp64| + |fp64 - fp32 oracle|, row-scaled
 CHUNK = 64          # users per host-side oracle logits chunk ([64, 1M] fp32 = 256 MB at C5)
 
 
@@ -61,7 +66,7 @@ class _Batch:
         chunk's targets and per-user delta."""
         scale = ref.abs().amax(1)
         self.err = max(self.err, float(((got - ref).abs().amax(1) / scale).max()))
-        delta = (scale * TOL).double()
+        delta = (scale * BAND).double()
         lg = ref.double()
         lg[:, 0] = -1e9
         c, rows = lg.shape
@@ -99,13 +104,14 @@ class _Batch:
         hr_o, nd_o = _hr_ndcg(exact)
         hr_g, nd_g = _hr_ndcg(ranks)
         rec = dict(users=len(ranks), max_row_scaled_logit_err=self.err,
-                   ranks_exact=int((ranks == exact).sum()), ranks_isolated=int(iso.sum()),
+                   ranks_exact=int((ranks == exact).sum()), ranks_isolated=int(iso.sum()), band=BAND,
                    ranks_in_band=int(((ranks >= lo) & (ranks <= hi)).sum()),
                    hr10_oracle=hr_o, hr10_gpu=hr_g, ndcg10_oracle=nd_o, ndcg10_gpu=nd_g, **info)
         if self.topk_checked:
             rec.update(top10_users_checked=self.topk_checked, top10_exact_users=self.topk_exact)
         parity_log(**rec)
         assert self.err <= TOL
+        assert self.err <= BAND      # what the rank / top-k bands above rest on
         assert hr_g == hr_o and nd_g == nd_o, (hr_g, hr_o, nd_g, nd_o)
 
 
