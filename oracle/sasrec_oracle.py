@@ -115,3 +115,76 @@ def train_loss_grads(seq_features, item_emb_weight, target_o_t, negs, eps):
     gf = f.grad if f.grad is not None else torch.zeros_like(f)
     gw = w.grad if w.grad is not None else torch.zeros_like(w)
     return bl.detach(), valid, gf, gw
+
+
+def train_loss_grads_scores(seq_features, item_emb_weight, target_o_t, negs, eps):
+    """``train_loss_grads`` plus the dense score matrix ``S [B, n, N+1]`` and its gradient ``dS`` from
+    the same graph (``retain_grad``; small shapes only).  ``dS`` is non-zero only at the gathered
+    entries, so ``|dS| . |M|`` and ``|dS|^T . |F|`` bound the magnitude of every gradient entry's
+    terms.  Works in the dtype of the inputs (float64 copies give the fp64 reference)."""
+    f = seq_features.detach().clone().requires_grad_(True)
+    w = item_emb_weight.detach().clone().requires_grad_(True)
+    score_matrix = torch.matmul(f, w.t())
+    score_matrix.retain_grad()
+    mask = (target_o_t != 0).float()
+    neg_expanded = negs.unsqueeze(1).expand(-1, score_matrix.shape[1], -1)
+    pos_scores = torch.gather(score_matrix, dim=2, index=target_o_t.unsqueeze(-1)).squeeze(-1)
+    neg_scores = torch.gather(score_matrix, dim=2, index=neg_expanded)
+    pos_loss = -torch.log(torch.sigmoid(pos_scores) + eps) * mask
+    neg_loss = (-torch.log(1 - torch.sigmoid(neg_scores) + eps) * mask.unsqueeze(-1)).sum(dim=-1)
+    bl, valid = (pos_loss + neg_loss).sum(), mask.sum()
+    if valid.item() > 0:
+        (bl / valid.item()).backward()
+    zeros = torch.zeros_like
+    gf = f.grad if f.grad is not None else zeros(f)
+    gw = w.grad if w.grad is not None else zeros(w)
+    ds = score_matrix.grad if score_matrix.grad is not None else zeros(score_matrix)
+    return bl.detach(), valid, gf, gw, score_matrix.detach(), ds
+
+
+# ---------------------------------------------------------------- csrc/neg_sample.hip, restated
+
+_M64 = (1 << 64) - 1
+NS_MAX_ROUNDS = 4096
+
+
+def mix64(z):
+    """The splitmix64 finaliser of csrc/neg_sample.hip on Python integers (64-bit wrap-around)."""
+    z = (z + 0x9E3779B97F4A7C15) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def neg_samples_replica(seq, item_num, num_neg, seed, seed_word=None):
+    """``neg_sample_kernel`` in integer arithmetic: the very ids ``ops.neg_samples(seq, item_num,
+    num_neg, seed=seed)`` returns (``seed_word``: the value of ``seed_tensor`` before the call).
+
+    Row ``r`` is keyed by ``rkey = mix64(seed ^ mix64(r))``.  Round ``k`` draws 64 candidates, lane
+    ``l`` taking ``1 + ((mix64(rkey + 64 k + l) * item_num) >> 64)``; a candidate is rejected when it
+    is in the row's history, was kept in an earlier round or was drawn by an earlier lane of this
+    round; the survivors are kept in lane order until ``num_neg`` are held.  A row still short after
+    4096 rounds is all -1 (the kernel raises the population error for it)."""
+    seq = np.asarray(seq, dtype=np.int64)
+    seed = int(seed) & _M64
+    if seed_word is not None:
+        seed ^= int(seed_word) & _M64
+    out = np.full((seq.shape[0], num_neg), -1, dtype=np.int64)
+    for row, hist in enumerate(seq.tolist()):
+        rkey = mix64(seed ^ mix64(row))
+        hist, kept, earlier = set(hist), [], set()
+        for rnd in range(NS_MAX_ROUNDS):
+            if len(kept) >= num_neg:
+                break
+            drawn = set()                                      # by the earlier lanes of this round
+            for lane in range(64):
+                c = 1 + ((mix64((rkey + 64 * rnd + lane) & _M64) * item_num) >> 64)
+                if c not in hist and c not in earlier and c not in drawn:
+                    kept.append(c)                             # lane order
+                    if len(kept) == num_neg:                   # later survivors of the round are cut
+                        break
+                drawn.add(c)
+            earlier.update(kept)
+        if len(kept) >= num_neg:
+            out[row] = kept[:num_neg]
+    return torch.from_numpy(out)

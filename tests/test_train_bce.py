@@ -6,6 +6,9 @@ Parity: against the reference-generated fixtures (features from the reference mo
 from the oracle's verbatim restatement, make_golden_train.py) and against the oracle on seeded
 inputs.  Bar: ``valid`` exact; ``batch_loss`` within 1e-5 relative; gradients within 1e-5 of the
 tensor's largest magnitude (fp32, different summation order; dM accumulates with atomics).
+The kernels' elementwise fp64 bar, the group / shape edges, saturation and the sampler's exact stream
+are in test_train_bce_fp64_gpu.py; the CPU tests of the oracle's additions it relies on
+(``train_loss_grads_scores``, ``mix64``, ``neg_samples_replica``) are here.
 """
 import numpy as np
 import pytest
@@ -47,6 +50,80 @@ def test_oracle_neg_samples_exclude_history():
     negs = sasrec_oracle.neg_samples(seqs, 12, 4, rng).numpy()
     for s, ng in zip(seqs, negs):
         assert len(set(ng)) == 4 and not set(ng) & set(s[s != 0]) and ng.min() >= 1 and ng.max() <= 12
+
+
+def test_mix64_pinned():
+    """mix64 is the splitmix64 output function: with the generator's state starting at 0 its first
+    two outputs are mix64(0) and mix64(golden gamma), the published test vectors of splitmix64."""
+    assert sasrec_oracle.mix64(0) == 0xE220A8397B1DCDAF
+    assert sasrec_oracle.mix64(0x9E3779B97F4A7C15) == 0x6E789E6AA1B965F4
+    assert sasrec_oracle.mix64(2 ** 64 - 1) == sasrec_oracle.mix64(-1 & (2 ** 64 - 1)) < 2 ** 64
+
+
+def test_neg_replica_contract_and_repeatable():
+    """The restated sampler stream on its own: distinct, in range, off the history (zeros and
+    repeats in it included), repeatable per seed, another stream for another seed or seed word, the
+    seed taken modulo 2^64, an unfillable row all -1, n = 0 and num_neg = item_num a permutation."""
+    rep = sasrec_oracle.neg_samples_replica
+    g = torch.Generator().manual_seed(5)
+    for B, n, items, J in [(9, 7, 50, 4), (5, 20, 30, 10), (3, 200, 300, 64), (3, 6, 2 ** 40, 8)]:
+        seq = torch.randint(1, min(items, 2 ** 31) + 1, (B, n), generator=g)
+        seq[:, : n // 3] = 0
+        seq[0, -1] = seq[0, -2]
+        out = rep(seq, items, J, 7)
+        assert out.shape == (B, J) and out.dtype == torch.int64
+        for s, ng in zip(seq.tolist(), out.tolist()):
+            assert len(set(ng)) == J and min(ng) >= 1 and max(ng) <= items and not set(ng) & set(s)
+        assert torch.equal(out, rep(seq, items, J, 7))
+        assert torch.equal(out, rep(seq, items, J, 7 + 2 ** 64)) and torch.equal(out, rep(seq, items, J, 7 - 2 ** 64))
+        assert not torch.equal(out, rep(seq, items, J, 8))
+        assert torch.equal(rep(seq, items, J, 7, seed_word=123), rep(seq, items, J, 7 ^ 123))
+        assert torch.equal(rep(seq, items, J, 0, seed_word=-1), rep(seq, items, J, 2 ** 64 - 1))
+    assert rep([[1, 2, 3, 4], [0, 0, 0, 1]], 6, 3, 0)[0].tolist() == [-1, -1, -1]
+    assert set(rep([[1, 2, 3, 4], [0, 0, 0, 1]], 6, 3, 0)[1].tolist()) <= {2, 3, 4, 5, 6}
+    full = rep(np.zeros((4, 0), np.int64), 64, 64, 3)
+    assert all(sorted(r) == list(range(1, 65)) for r in full.tolist())
+    assert rep([[1, 2]], 10, 0, 3).shape == (1, 0)
+
+
+def test_neg_replica_uniform():
+    """The population and threshold of test_neg_samples_uniform_and_seeded: 18 valid items, 20000
+    rows of 3, chi-square over 17 degrees of freedom below 45 (p ~ 3e-4), each slot uniform too."""
+    items, J, B = 20, 3, 20000
+    seq = np.zeros((B, 4), np.int64)
+    seq[:, 0], seq[:, 1] = 5, 17
+    a = sasrec_oracle.neg_samples_replica(seq, items, J, 123).numpy()
+    cnt = np.bincount(a.ravel(), minlength=items + 1)
+    assert cnt[0] == 0 and cnt[5] == 0 and cnt[17] == 0
+    valid = [i for i in range(1, items + 1) if i not in (5, 17)]
+    exp = B * J / len(valid)
+    chi2 = sum((cnt[i] - exp) ** 2 / exp for i in valid)
+    assert chi2 < 45.0
+    first = np.bincount(a[:, 0], minlength=items + 1)[valid]
+    assert (first.max() - first.min()) < 0.25 * first.mean()
+
+
+def test_train_loss_grads_scores_is_train_loss_grads():
+    """The variant that also returns S and dS computes the verbatim restatement's results (fp32 and
+    fp64), dS is zero off the gathered entries, and dF = dS . M, dM = dS^T . F."""
+    g = torch.Generator().manual_seed(2)
+    f, w = torch.randn(3, 4, 5, generator=g) * 0.3, torch.randn(9, 5, generator=g) * 0.3
+    tg = torch.randint(0, 9, (3, 4), generator=g)
+    tg[0] = 0
+    ng = torch.randint(1, 9, (3, 2), generator=g)
+    for dt in (torch.float32, torch.float64):
+        a = sasrec_oracle.train_loss_grads(f.to(dt), w.to(dt), tg, ng, 1e-24)
+        b = sasrec_oracle.train_loss_grads_scores(f.to(dt), w.to(dt), tg, ng, 1e-24)
+        for x, y in zip(a, b[:4]):
+            assert x.dtype == y.dtype and torch.equal(x, y)
+        S, dS = b[4], b[5]
+        assert S.dtype == dt and dS.shape == (3, 4, 9)
+        hit = torch.zeros(3, 4, 9, dtype=torch.bool)
+        hit.scatter_(2, tg.unsqueeze(-1), True)
+        hit.scatter_(2, ng.unsqueeze(1).expand(-1, 4, -1), True)
+        assert torch.count_nonzero(dS[~hit]) == 0 and torch.count_nonzero(dS[0]) == 0
+        assert torch.allclose(b[2], dS @ w.to(dt), rtol=1e-5, atol=1e-8)
+        assert torch.allclose(b[3], torch.einsum("btr,btd->rd", dS, f.to(dt)), rtol=1e-5, atol=1e-8)
 
 
 def _run(t, eps, dev):
