@@ -61,6 +61,94 @@ __device__ __forceinline__ double seq_sum(const double* p, int n, int stride) {
   return s;
 }
 
+// torch's CPU sum of n values as ATen's multi_row_sum runs it (SumKernel.cpp), M accumulators side
+// by side (value i of accumulator m at p[i * stride + m * mstride]): blocks of 2^lp values
+// (lp = max(4, ceil_log2(n) / 4): 16 below 2^20 values), each summed from zero in index order and
+// pushed up four levels of partial sums; the tail from zero too; then level 0 + 1 + 2 + 3.  Equal
+// to the index-order sum only below 18 values.  16 loads in flight ahead of the dependent adds.
+template <int M>
+__device__ __forceinline__ void cascade_sum_lp(const double* p, int n, int64_t stride, int64_t mstride,
+                                               double (&out)[M], const int lp) {
+  constexpr int U = 16 / M;
+  const int step = 1 << lp;   // a multiple of 16
+  const int64_t mask = step - 1;
+  double a0[M], a1[M], a2[M], a3[M];
+#pragma unroll
+  for (int m = 0; m < M; ++m) a0[m] = a1[m] = a2[m] = a3[m] = 0.0;
+  int i = 0;
+  while (i + step <= n) {
+    for (int j = 0; j < step; j += U) {
+      double v[U][M];
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+#pragma unroll
+        for (int m = 0; m < M; ++m) v[u][m] = p[(int64_t)(i + j + u) * stride + m * mstride];
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+#pragma unroll
+        for (int m = 0; m < M; ++m) a0[m] += v[u][m];
+    }
+    i += step;
+    const bool up2 = ((int64_t)i & (mask << lp)) == 0;
+    const bool up3 = up2 && ((int64_t)i & (mask << (2 * lp))) == 0;
+#pragma unroll
+    for (int m = 0; m < M; ++m) {
+      a1[m] += a0[m];
+      a0[m] = 0.0;
+      if (up2) {
+        a2[m] += a1[m];
+        a1[m] = 0.0;
+      }
+      if (up3) {
+        a3[m] += a2[m];
+        a2[m] = 0.0;
+      }
+    }
+  }
+  for (; i < n; ++i)
+#pragma unroll
+    for (int m = 0; m < M; ++m) a0[m] += p[(int64_t)i * stride + m * mstride];
+#pragma unroll
+  for (int m = 0; m < M; ++m) {
+    a0[m] += a1[m];
+    a0[m] += a2[m];
+    a0[m] += a3[m];
+    out[m] = a0[m];
+  }
+}
+
+template <int M>
+__device__ __forceinline__ void cascade_sum(const double* p, int n, int64_t stride, int64_t mstride,
+                                            double (&out)[M]) {
+  if (n <= (1 << 19)) {   // ceil_log2(n) / 4 <= 4: blocks of 16, as a compile-time constant
+    cascade_sum_lp<M>(p, n, stride, mstride, out, 4);
+  } else {
+    const int lg = 32 - __clz(n - 1);
+    cascade_sum_lp<M>(p, n, stride, mstride, out, lg / 4);
+  }
+}
+
+// torch.sum(Q, dim=0)[k] of a contiguous float64 [B, K] matrix in torch's CPU order (ATen's
+// vectorized_outer_sum on its AVX2 build, 4 doubles per vector, which the sum kernels use on
+// AVX-512 hosts too): the columns below the last multiple of 16 take the cascade sum over the
+// rows; the others four interleaved partial sums (rows 4i + m, each a cascade sum), the B % 4 tail
+// rows added to the first, then p0 + p1 + p2 + p3.  (K = 1 is an inner reduction there and has no
+// choice to make here.)
+__device__ __forceinline__ double torch_col_sum(const double* q, int k, int B, int K, int P) {
+  if (k < (K & ~15)) {
+    double s[1];
+    cascade_sum<1>(q + k, B, P, 0, s);
+    return s[0];
+  }
+  double p[4];
+  cascade_sum<4>(q + k, B >> 2, 4 * (int64_t)P, P, p);
+  for (int b = B & ~3; b < B; ++b) p[0] += q[(int64_t)b * P + k];
+  p[0] += p[1];
+  p[0] += p[2];
+  p[0] += p[3];
+  return p[0];
+}
+
 // largest power of two <= min(64, x), at least 1
 __device__ __forceinline__ int pow2_group(int x) {
   int g = 1;
@@ -71,8 +159,9 @@ __device__ __forceinline__ int pow2_group(int x) {
 // One workgroup per group of rows.  The [B, K] Sinkhorn matrix of a group lives in LDS when it fits
 // (every training batch of main.py: 64 x 8; a 64 x 256 batch: 128 KiB) and in the caller's
 // workspace otherwise; both go through the same generic pointer.  Every row / column sum runs in
-// index order in one lane (the reference's argmax can sit on ties that only its rounding order
-// decides: identical rows of a collision group), and the divisions -- the reference's two per
+// one lane, rows in index order and columns in torch's CPU order (the reference's argmax can sit
+// on ties that only its rounding order decides: identical rows of a collision group), and the
+// divisions -- the reference's two per
 // element and half-step, Q /= sum; Q /= B, in float64 -- spread over the whole workgroup.  The
 // final argmax / argmin gives each row a group of lanes (a power of two within one wave) that
 // combine their first extremes with shuffles.
@@ -159,7 +248,9 @@ __global__ __launch_bounds__(SK_T) void rq_sk_kernel(const float* __restrict__ z
         const bool powB = (B & (B - 1)) == 0;
         const double invB = 1.0 / dB, invK = 1.0 / dK;
         if (B <= SK_SUMS && K <= SK_SUMS) {
-          // Each sum runs in index order in one lane (torch's CPU order for the column sums); the
+          // Each sum runs in one lane: a row in index order (torch's vectorised row sum differs, but
+          // it scales a whole row and shows only through rounding ties), a column in torch's CPU
+          // order (torch_col_sum: it decides exact ties between columns, 17 x 40 at eps 0.003); the
           // divisions then spread over the whole workgroup.
           for (int it = 0; it < sk_iters; ++it) {
             for (int b = tid; b < B; b += SK_T)     // rows (dim=1): Q /= sum_k Q[b, k]; Q /= B
@@ -171,7 +262,7 @@ __global__ __launch_bounds__(SK_T) void rq_sk_kernel(const float* __restrict__ z
               for (int i = tid; i < B * K; i += SK_T) Q[qi(i)] = (Q[qi(i)] / sums[i / K]) / dB;
             __syncthreads();
             for (int k = tid; k < K; k += SK_T)     // columns (dim=0): Q /= sum_b Q[b, k]; Q /= K
-              sums[k] = seq_sum<16>(Q + k, B, P);
+              sums[k] = torch_col_sum(Q, k, B, K, P);
             __syncthreads();
             if (powK)
               for (int i = tid; i < B * K; i += SK_T) Q[qi(i)] = (Q[qi(i)] / sums[i & (K - 1)]) * invK;
@@ -187,7 +278,7 @@ __global__ __launch_bounds__(SK_T) void rq_sk_kernel(const float* __restrict__ z
             }
             __syncthreads();
             for (int k = tid; k < K; k += SK_T) {
-              const double s = seq_sum<16>(Q + k, B, P);
+              const double s = torch_col_sum(Q, k, B, K, P);
               for (int b = 0; b < B; ++b) Q[(int64_t)b * P + k] = (Q[(int64_t)b * P + k] / s) / dK;
             }
             __syncthreads();

@@ -116,15 +116,16 @@ def sinkhorn(distances, epsilon, iters):
     return Q
 
 
-def vq_level_sk(latent, codebook, sk_epsilon, sk_iters):
+def vq_level_sk(latent, codebook, sk_epsilon, sk_iters, dot=None):
     """VectorQuantizer.forward(x, use_sk=True) (vq.py:63-99): Sinkhorn assignment when
-    sk_epsilon > 0 (vq.py:76-84), else the argmin path."""
+    sk_epsilon > 0 (vq.py:76-84), else the argmin path.  ``dot(latent, codebook) -> [B, K]``
+    replaces this host's ``latent @ codebook.t()`` on a Sinkhorn level (see quantize_sk)."""
     if sk_epsilon <= 0:
         x_q, ind, _ = vq_level(latent, codebook)
         return x_q, ind
     d = torch.sum(latent ** 2, dim=1, keepdim=True) + \
         torch.sum(codebook ** 2, dim=1, keepdim=True).t() - \
-        2 * torch.matmul(latent, codebook.t())
+        2 * (torch.matmul(latent, codebook.t()) if dot is None else dot(latent, codebook))
     d = center_distance(d).double()
     Q = sinkhorn(d, sk_epsilon, sk_iters)
     ind = torch.argmax(Q, dim=-1)
@@ -142,6 +143,79 @@ def get_indices_sk(x, weights, biases, codebooks, sk_epsilons, sk_iters):
         residual = residual - x_res
         idx.append(ind)
     return torch.stack(idx, dim=-1)
+
+
+@torch.no_grad()
+def quantize_sk(z, codebooks, sk_epsilons, sk_iters, dot=None):
+    """ResidualVectorQuantizer.forward(z, use_sk=True) indices (rq.py:39-56) for ONE group of rows:
+    the level chain of ``vq_level_sk`` with the residual update of rq.py:47 -> idx [B, L].
+
+    The exact reference: torch's own CPU fp32 distances and the float64 Sinkhorn of
+    layers.py:85-108, in this host's summation order.  The host's sgemm order is part of it: MKL
+    on another CPU may round r . C^T differently, even differently for two equal rows of one call
+    (a 6-row call on an AVX-512 AMD host: rows 0-3 and rows 4-5 come out of different kernels).  ``dot``
+    puts a stated order in its place on the Sinkhorn levels, e.g. oracle.rq_exact.linear, the
+    restatement of the fixture host's MKL order that the kernels follow."""
+    residual, idx = z, []
+    for cb, eps in zip(codebooks, sk_epsilons):
+        x_res, ind = vq_level_sk(residual, cb, eps, sk_iters, dot)
+        residual = residual - x_res
+        idx.append(ind)
+    return torch.stack(idx, dim=-1)
+
+
+SK_LOG_MARGIN = 1e-2      # certified Sinkhorn level: log Q_top1 - log Q_top2 above this
+SK_ARGMIN_MARGIN = 1e-4   # certified argmin level: relative distance gap above this
+
+
+@torch.no_grad()
+def quantize_sk_fp64(z, codebooks, sk_epsilons, sk_iters):
+    """The same chain in float64 from the inputs on: distances, the centring with its ``+ 1e-5``,
+    the Sinkhorn and the residual ``r - C[idx]`` -> (idx [B, L], margin [B, L]).
+
+    It depends on no BLAS or vectorised-sum order, so it is the same on every host.  ``margin`` says
+    how far a row's choice is from its runner-up, in the units in which an fp32 distance error acts:
+      Sinkhorn level   log Q_top1 - log Q_top2 (Q is monotone in -d'/eps, so a distance error moves
+                       log Q by about |delta d'| / eps);
+      argmin level     (d_2nd - d_1st) / (|r|^2 + max |c|^2), the gap relative to the magnitude
+                       whose rounding an fp32 distance carries;
+      K = 1            infinity (nothing to choose).
+    A row whose Q is NaN or all zero has margin 0."""
+    r = z.double()
+    idx, margins = [], []
+    for cb, eps in zip(codebooks, sk_epsilons):
+        c = cb.double()
+        d = (r * r).sum(1, keepdim=True) + (c * c).sum(1)[None] - 2.0 * (r @ c.t())
+        if eps > 0:
+            mx, mn = d.max(), d.min()
+            middle = (mx + mn) / 2
+            Q = sinkhorn((d - middle) / (mx - middle + 1e-5), eps, sk_iters)
+            ind = torch.argmax(Q, dim=-1)
+            if c.shape[0] > 1:
+                two = torch.topk(Q, 2, dim=1).values
+                m = torch.log(two[:, 0]) - torch.log(two[:, 1])
+                m = torch.where(torch.isnan(m), torch.zeros_like(m), m)
+            else:
+                m = torch.full((r.shape[0],), float("inf"), dtype=torch.float64)
+        else:
+            ind = torch.argmin(d, dim=-1)
+            if c.shape[0] > 1:
+                two = torch.topk(d, 2, dim=1, largest=False).values
+                m = (two[:, 1] - two[:, 0]) / ((r * r).sum(1) + (c * c).sum(1).max())
+            else:
+                m = torch.full((r.shape[0],), float("inf"), dtype=torch.float64)
+        r = r - c[ind]
+        idx.append(ind)
+        margins.append(m)
+    return torch.stack(idx, dim=-1), torch.stack(margins, dim=-1)
+
+
+def sk_certified(margin, sk_epsilons):
+    """Rows of ``quantize_sk_fp64`` whose margin exceeds its level's threshold on EVERY level:
+    SK_LOG_MARGIN where the level runs the Sinkhorn, SK_ARGMIN_MARGIN where it is the argmin."""
+    thr = torch.tensor([SK_LOG_MARGIN if eps > 0 else SK_ARGMIN_MARGIN for eps in sk_epsilons],
+                       dtype=torch.float64)
+    return (margin > thr).all(1)
 
 
 def collision_groups(codes):

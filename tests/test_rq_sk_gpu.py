@@ -86,12 +86,7 @@ def test_sinkhorn_batch_shapes_vs_oracle(B, K, dev, parity_log):
     z = torch.randn(B, 32, generator=g)
     cbs = [torch.randn(K, 32, generator=g) * 0.8 for _ in range(3)]
     got = ops.rq_quantize_sk(z.to(dev), [c.to(dev) for c in cbs], [0.01, 0.0, 0.01], 50).cpu()
-    r, ref = z.clone(), []
-    for c, eps in zip(cbs, [0.01, 0.0, 0.01]):
-        xq, ind = rq_oracle.vq_level_sk(r, c, eps, 50)
-        ref.append(ind)
-        r = r - xq
-    ref = torch.stack(ref, -1)
+    ref = rq_oracle.quantize_sk(z, cbs, [0.01, 0.0, 0.01], 50)
     bad = int((got != ref).any(1).sum())
     parity_log(kind="rq_sinkhorn_batch", shape=f"B{B} K{K}", rows=B, rows_differ=bad, cap=0)
     assert bad == 0
