@@ -17,15 +17,25 @@
 //   L1  h1^T[256 x 32FP] = W1 . x^T   wave w owns features [32w, 32w+32) for all FP item tiles;
 //       W1 fragments go straight from L2 to registers, software-pipelined one 32-deep group ahead;
 //       the x chunk ([32FP x 64]) is shared through a double-buffered LDS image staged one chunk
-//       ahead (across pass boundaries too).  At the MKL block boundary the first block's sum plus
-//       the bias moves to registers and the chain restarts from zero.
+//       ahead (across pass boundaries too).  Item tile 0's fragments are read from that image one
+//       32-deep group before their MFMAs (FusedCtx::read_bxa) -- group 0's right behind the chunk
+//       barrier, with the last four MFMAs of the chunk before still to issue -- and item tile 1's
+//       under tile 0's first MFMAs, so no ds_read is waited for with the MFMA pipe empty.  At the
+//       MKL block boundary the first block's sum plus the bias moves to registers and the chain
+//       restarts from zero.  An LDS-fed 32x32x2 chain tops out at 0.93-0.95 of MFMA issue however
+//       early its reads go out (profiles/r08/mfma_rate_prefetch.txt; 0.99 from registers): reading
+//       ahead is worth 1.2 cycles per MFMA at this phase's 8 waves x 2 chains in the microbenchmark
+//       and 1.8 in the kernel (profiles/r08/encoder_phase_split.txt).
 //   L2  h2^T[128 x 32FP] = W2 . relu(h1)^T   v_mfma_f32_16x16x4_f32 (also one fma chain in k order,
 //       rq_small.hip): all 8 waves, wave w owns features [16w, 16w+16) for the pass's four 16-item
-//       tiles -- four independent K = 256 chains per wave, two waves per SIMD (the 0.934 point of
-//       profiles/r02_mfma_rate.txt; the 32x32x2 form on waves 0-3 ran two chains on one wave per
-//       SIMD, 0.835).  W2 comes in the 16x16x4 order (image 4 of the pack), its first four blocks'
-//       fragments stay in registers for the whole kernel; h1 sits in LDS in that order, k-group
-//       pairs flipped in rows 4..11 of 16 so that the ds_read_b128 lane groups are conflict-free.
+//       tiles -- four independent K = 256 chains per wave, two waves per SIMD (0.94 of MFMA issue
+//       for LDS-fed chains in profiles/r08/mfma_rate_prefetch.txt, where that is also what they
+//       level off at; the 32x32x2 form on waves 0-3 ran two chains on one wave per SIMD, 0.84.
+//       Reading each 64-deep block's first h1 fragments a block ahead measured nothing here,
+//       profiles/r08/ab_rq_parts.txt).  W2 comes in the 16x16x4 order (image 4 of the pack), its
+//       first four blocks' fragments stay in registers for the whole kernel; h1 sits in LDS in
+//       that order, k-group pairs flipped in rows 4..11 of 16 so that the ds_read_b128 lane groups
+//       are conflict-free.
 //   L3  z^T[32 x 32FP] = W3 . relu(h2)^T     16x16x4 MFMA tiles, one per wave, each the whole
 //       k = 128 chain, W3 from an LDS copy staged at kernel start
 // Every bias fragment is loaded a phase ahead of its use (b1 before the chunk loops, b2 and b3 at
@@ -100,6 +110,7 @@ struct FusedCtx {
   f32x4 w2f[4];           // L2: W2 fragments of the first four 16-deep blocks (the same every pass)
   f32x4 xr[C::XV];
   bool xok[C::XV];
+  f32x4 bxa[4];           // L1: item tile 0's x fragments of the NEXT 32-deep group (read_bxa)
   int buf;
   // x chunk staging: [PI items x 64 k] = PI*16 float4, 16 threads per item row.  Rows past n
   // (or past this workgroup's range) load a clamped valid row and are zeroed only when written
@@ -114,6 +125,17 @@ struct FusedCtx {
       xr[i] = *reinterpret_cast<const f32x4*>(x + (item < n ? item : n - 1) * D0 +
                                               (int64_t)c * FXC + k4 + (ks && it >= FT ? csplit * FXC : 0));
     }
+  }
+  // Item tile 0's fragments are read one 32-deep group ahead of their MFMAs: group 1's during group
+  // 0 (the same image), group 0's right behind the barrier that publishes their image -- the next
+  // chunk's, the next pass's chunk 0 (which stays in place through L2 / L3), or after a workgroup's
+  // last chunk an image that nobody uses (always inside the x buffers).  A read issued at the head
+  // of its own group is waited for with nothing queued on the MFMA pipe, by both waves of a SIMD at
+  // once, since they leave the barrier together.
+  __device__ __forceinline__ void read_bxa(int g) {
+    const float* xb = xs + buf * C::PI * FXP + r * FXP + 16 * h + g * 32;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) bxa[j] = *reinterpret_cast<const f32x4*>(xb + 4 * j);
   }
   __device__ __forceinline__ void swrite_x(int b) {
 #pragma unroll
@@ -311,10 +333,13 @@ __device__ __forceinline__ void rq_fused_pass(FusedCtx<H1, H2>& cx, int tb, int 
     const float* xb = cx.xs + cx.buf * PI * FXP + r * FXP + 16 * h + g * 32;
     f32x4 bx[NP][4];
 #pragma unroll
-    for (int it = 0; it < NP; ++it)
+    for (int j = 0; j < 4; ++j) bx[0][j] = cx.bxa[j];   // read a group ahead (FusedCtx::read_bxa)
+#pragma unroll
+    for (int it = 1; it < NP; ++it)
 #pragma unroll
       for (int j = 0; j < 4; ++j) bx[it][j] = *reinterpret_cast<const f32x4*>(xb + it * FT * FXP + 4 * j);
     if constexpr (g == 0) {
+      cx.read_bxa(1);                  // group 1's item tile 0: the same image, behind tile 1's reads
       asm volatile("" ::: "memory");   // x loads stay behind the W1 loads and LDS reads
       const bool same = c + 1 < NC;
 #pragma unroll
@@ -338,20 +363,20 @@ __device__ __forceinline__ void rq_fused_pass(FusedCtx<H1, H2>& cx, int tb, int 
                    ok ? cx.xr[i] : f32x4{0.f, 0.f, 0.f, 0.f});
       }
     }
-    // schedule: item tile 0's LDS fragments, the W1 loads and item tile 1's LDS fragments one per
-    // MFMA, then (group 0) the x loads, (group 1) the x image writes (two per float4) near the end
+    // schedule: the W1 loads, item tile 1's LDS fragments and (group 0) item tile 0's of group 1
+    // one per MFMA, then (group 0) the x loads, (group 1) the x image writes (two per float4) at the
+    // end; group 1's last NDW MFMAs are placed by chunk(), behind the barrier and the reads after it
     constexpr int NX = (g == 0) ? C::XV : 0, NDW = (g == 1) ? 2 * C::XV : 0;
-    constexpr int NW = KS ? 8 : 4;
-    static_assert(NW + 4 * (NP - 1) + NX + 2 * NDW <= M1, "schedule");
+    constexpr int NW = KS ? 8 : 4, NA = (g == 0) ? 4 : 0;
+    static_assert(NW + 4 * (NP - 1) + NA + NX + 2 * NDW <= M1, "schedule");
     {
-      __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
 #pragma unroll
       for (int i = 0; i < NW; ++i) {
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
         __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
       }
 #pragma unroll
-      for (int i = 0; i < 4 * (NP - 1); ++i) {
+      for (int i = 0; i < 4 * (NP - 1) + NA; ++i) {
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
         __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
       }
@@ -360,13 +385,12 @@ __device__ __forceinline__ void rq_fused_pass(FusedCtx<H1, H2>& cx, int tb, int 
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
         __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
       }
-      __builtin_amdgcn_sched_group_barrier(0x008, M1 - NW - 4 * (NP - 1) - NX - 2 * NDW, 0);
+      __builtin_amdgcn_sched_group_barrier(0x008, M1 - NW - 4 * (NP - 1) - NA - NX - 2 * NDW, 0);
 #pragma unroll
       for (int i = 0; i < NDW; ++i) {
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
         __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
       }
-      __builtin_amdgcn_sched_group_barrier(0x008, NDW, 0);
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) cx.awc[j] = awn[j];
@@ -381,6 +405,11 @@ __device__ __forceinline__ void rq_fused_pass(FusedCtx<H1, H2>& cx, int tb, int 
     group(std::integral_constant<int, 1>{}, c);
     __syncthreads();
     cx.buf ^= 1;
+    // the next group 0's item tile 0 fragments, from the image the barrier has just published, with
+    // this chunk's last MFMAs (operands in registers) behind them
+    cx.read_bxa(0);
+    __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
+    __builtin_amdgcn_sched_group_barrier(0x008, 2 * C::XV, 0);
   };
   int c = 0;
   f32x16 part[NP];
@@ -599,6 +628,7 @@ __global__ __launch_bounds__(64 * FWV, 1) void rq_encoder_kernel(
   cx.gload_x(pieces_only ? ptile : t_begin, 0, pieces_only || (ks && t_end - t_begin == 1));
   cx.swrite_x(0);
   __syncthreads();
+  cx.read_bxa(0);   // the first pass's first group (unused when the workgroup runs pieces only)
   int tb = t_begin;
   for (; tb + FP <= t_end; tb += FP) {
     const bool last = tb + FP >= t_end;
