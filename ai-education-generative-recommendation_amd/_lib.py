@@ -94,6 +94,14 @@ SIGNATURES = {
     "gr_sasrec_train_bwd_f32": (ctypes.c_int, [ctypes.POINTER(SasrecParams), _vp, _i64, _i32, _f32,
                                                ctypes.c_uint64, _vp, ctypes.POINTER(SasrecTrainBufs), _vp,
                                                _vp, _vp]),
+    "gr_sasrec_train_tiled_workspace_bytes": (_sz, [ctypes.POINTER(SasrecParams), _i64, _i32]),
+    "gr_sasrec_train_tiled_parts": (_i32, [ctypes.POINTER(SasrecParams), _i64, _i32]),
+    "gr_sasrec_train_tiled_fwd_f32": (ctypes.c_int, [ctypes.POINTER(SasrecParams), _vp, _i64, _i32, _f32,
+                                                     ctypes.c_uint64, _vp, ctypes.POINTER(SasrecTrainBufs), _vp,
+                                                     _vp, _vp, _sz, _vp]),
+    "gr_sasrec_train_tiled_bwd_f32": (ctypes.c_int, [ctypes.POINTER(SasrecParams), _vp, _i64, _i32, _f32,
+                                                     ctypes.c_uint64, _vp, ctypes.POINTER(SasrecTrainBufs), _vp,
+                                                     _vp, _vp, _sz, _vp]),
     "gr_score_f32": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp]),
     "gr_sampled_bce_fwd_f32": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _i32, _f32,
                                               _vp, _vp, _vp, _vp, _vp]),

@@ -965,9 +965,28 @@ def dropout_seed(device):
     return t
 
 
+def _sas_train_fits(model, n, n_max, d_max, mlp_max):
+    return (1 <= n <= n_max and n <= model.pos_emb.weight.shape[0] and 1 <= model.d <= d_max
+            and model.d % model.num_heads == 0 and 1 <= model.mlp_layer <= mlp_max
+            and 1 <= model.num_blocks <= 8)
+
+
+def sasrec_train_fits_sequence(model, n):
+    """One workgroup per sequence (sasrec_train.hip): n, d <= 64, mlp_layer <= 128."""
+    return _sas_train_fits(model, n, 64, 64, 128)
+
+
+def sasrec_train_fits_tiled(model, n):
+    """The tiled kernels (sasrec_train_tiled.hip): n <= 256, d <= 128, mlp_layer <= 256."""
+    return _sas_train_fits(model, n, 256, 128, 256)
+
+
 def sasrec_train_supported(model, n):
-    return (n <= 64 and n <= model.pos_emb.weight.shape[0] and model.d <= 64
-            and model.d % model.num_heads == 0 and model.mlp_layer <= 128 and 1 <= model.num_blocks <= 8)
+    """Whether the train-mode forward / backward of this shape runs on the training kernels (either
+    set); honours ``model.train_kernels`` ("sequence" / "tiled" restrict it to that set)."""
+    mode = getattr(model, "train_kernels", "auto")
+    seq = mode in ("auto", "sequence") and sasrec_train_fits_sequence(model, n)
+    return seq or (mode in ("auto", "tiled") and sasrec_train_fits_tiled(model, n))
 
 
 def _train_params(model):
@@ -980,6 +999,81 @@ def _train_params(model):
     return ps + [model.last_layernorm.weight, model.last_layernorm.bias]
 
 
+def _sas_train_fwd(ctx, tiled, seqs, binding, p_drop, seed_snap, params):
+    """Forward of ``_SasTrain`` (tiled False) / ``_SasTrainTiled``: allocate the saved-activation
+    buffers (and the tiled kernels' workspace), launch, keep what the backward needs."""
+    B, n = seqs.shape
+    p = binding.p
+    d, m, nb, H = p.d, p.mlp, p.n_blocks, p.n_heads
+    dev = seqs.device
+    R = B * n
+    e = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)   # noqa: E731
+    bufs = {"xin": e(nb, R, d), "hs": e(nb, R, d), "qkv": e(nb, R, 3 * d), "prob": e(nb, B, H, n, n),
+            "os": e(nb, R, d), "x1": e(nb, R, d), "fs": e(nb, R, d), "zs": e(nb, R, m), "us": e(nb, R, m),
+            "xl": e(R, d)}
+    out = e(B, n, d)
+    err = err_flag(dev)
+    cb = L.SasrecTrainBufs(**{k: v.data_ptr() for k, v in bufs.items()})
+    with L.on(dev):
+        if tiled:
+            nbytes = L.lib().gr_sasrec_train_tiled_workspace_bytes(ctypes.byref(p), B, n)
+            ws = L.workspace(nbytes, dev)
+            L.check(L.lib().gr_sasrec_train_tiled_fwd_f32(ctypes.byref(p), L.ptr(seqs), B, n, float(p_drop), 0,
+                                                          L.ptr(seed_snap), ctypes.byref(cb), L.ptr(out),
+                                                          L.ptr(err), L.ptr(ws), nbytes, L.stream_of(dev)),
+                    "gr_sasrec_train_tiled_fwd_f32")
+        else:
+            L.check(L.lib().gr_sasrec_train_fwd_f32(ctypes.byref(p), L.ptr(seqs), B, n, float(p_drop), 0,
+                                                    L.ptr(seed_snap), ctypes.byref(cb), L.ptr(out), L.ptr(err),
+                                                    L.stream_of(dev)), "gr_sasrec_train_fwd_f32")
+    _check_err(err)
+    ctx.binding, ctx.p_drop, ctx.bufs, ctx.seqs, ctx.seed = binding, p_drop, bufs, seqs, seed_snap
+    ctx.shapes = (B, n, d, m, nb, params[1].shape[0])
+    return out
+
+
+def _sas_train_bwd(ctx, tiled, dout):
+    """Backward of ``_SasTrain`` / ``_SasTrainTiled``: the kernels leave every parameter gradient but
+    the item table's as partial rows of g_vec (one per sequence; the tiled kernels: one per split-k
+    chunk of the rows), summed and sliced here; item-table rows are scattered in the kernel."""
+    B, n, d, m, nb, max_len = ctx.shapes
+    bufs, seqs = ctx.bufs, ctx.seqs
+    dev = seqs.device
+    p = ctx.binding.p
+    vw = L.lib().gr_sasrec_train_vec_width(ctypes.byref(p), n)
+    parts = L.lib().gr_sasrec_train_tiled_parts(ctypes.byref(p), B, n) if tiled else B
+    g_vec = torch.empty((parts, vw), dtype=torch.float32, device=dev)
+    g_item = torch.zeros((p.item_rows, d), dtype=torch.float32, device=dev)
+    cb = L.SasrecTrainBufs(g_vec=g_vec.data_ptr(), **{k: v.data_ptr() for k, v in bufs.items()})
+    dout = dout.contiguous().float()
+    with L.on(dev):
+        if tiled:
+            nbytes = L.lib().gr_sasrec_train_tiled_workspace_bytes(ctypes.byref(p), B, n)
+            ws = L.workspace(nbytes, dev)
+            L.check(L.lib().gr_sasrec_train_tiled_bwd_f32(ctypes.byref(p), L.ptr(seqs), B, n, float(ctx.p_drop), 0,
+                                                          L.ptr(ctx.seed), ctypes.byref(cb), L.ptr(dout),
+                                                          L.ptr(g_item), L.ptr(ws), nbytes, L.stream_of(dev)),
+                    "gr_sasrec_train_tiled_bwd_f32")
+        else:
+            L.check(L.lib().gr_sasrec_train_bwd_f32(ctypes.byref(p), L.ptr(seqs), B, n, float(ctx.p_drop), 0,
+                                                    L.ptr(ctx.seed), ctypes.byref(cb), L.ptr(dout), L.ptr(g_item),
+                                                    L.stream_of(dev)), "gr_sasrec_train_bwd_f32")
+    vec = g_vec.sum(0)   # every parameter's gradient but the item table's, in parameter order
+    shapes = [(d,), (d,), (3 * d, d), (3 * d,), (d, d), (d,), (d,), (d,), (m, d), (m,), (d, m), (d,)] * nb
+    shapes += [(d,), (d,)]
+    grads, off = [], 0
+    for shp in shapes:
+        k = 1
+        for x in shp:
+            k *= x
+        grads.append(vec[off:off + k].view(shp))
+        off += k
+    # rows n.. of pos_emb get zeros (a pad kernel rather than a copy into a zeros tensor, which
+    # keeps memset / memcpy nodes out of a captured step's graph)
+    dpos = torch.nn.functional.pad(vec[off:off + n * d].view(n, d), (0, 0, 0, max_len - n))
+    return (None, None, None, None, g_item, dpos, *grads)
+
+
 class _SasTrain(torch.autograd.Function):
     """Train-mode SASRec forward (dropout on) and its backward on the kernels of sasrec_train.hip:
     one launch each.  The backward leaves every parameter gradient but the item table's as a
@@ -989,56 +1083,27 @@ class _SasTrain(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, seqs, binding, p_drop, seed_snap, *params):
-        B, n = seqs.shape
-        p = binding.p
-        d, m, nb, H = p.d, p.mlp, p.n_blocks, p.n_heads
-        dev = seqs.device
-        R = B * n
-        e = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)   # noqa: E731
-        bufs = {"xin": e(nb, R, d), "hs": e(nb, R, d), "qkv": e(nb, R, 3 * d), "prob": e(nb, B, H, n, n),
-                "os": e(nb, R, d), "x1": e(nb, R, d), "fs": e(nb, R, d), "zs": e(nb, R, m), "us": e(nb, R, m),
-                "xl": e(R, d)}
-        out = e(B, n, d)
-        err = err_flag(dev)
-        cb = L.SasrecTrainBufs(**{k: v.data_ptr() for k, v in bufs.items()})
-        with L.on(dev):
-            L.check(L.lib().gr_sasrec_train_fwd_f32(ctypes.byref(p), L.ptr(seqs), B, n, float(p_drop), 0,
-                                                    L.ptr(seed_snap), ctypes.byref(cb), L.ptr(out), L.ptr(err),
-                                                    L.stream_of(dev)), "gr_sasrec_train_fwd_f32")
-        _check_err(err)
-        ctx.binding, ctx.p_drop, ctx.bufs, ctx.seqs, ctx.seed = binding, p_drop, bufs, seqs, seed_snap
-        ctx.shapes = (B, n, d, m, nb, params[1].shape[0])
-        return out
+        return _sas_train_fwd(ctx, False, seqs, binding, p_drop, seed_snap, params)
 
     @staticmethod
     def backward(ctx, dout):
-        B, n, d, m, nb, max_len = ctx.shapes
-        bufs, seqs = ctx.bufs, ctx.seqs
-        dev = seqs.device
-        p = ctx.binding.p
-        vw = L.lib().gr_sasrec_train_vec_width(ctypes.byref(p), n)
-        g_vec = torch.empty((B, vw), dtype=torch.float32, device=dev)
-        g_item = torch.zeros((p.item_rows, d), dtype=torch.float32, device=dev)
-        cb = L.SasrecTrainBufs(g_vec=g_vec.data_ptr(), **{k: v.data_ptr() for k, v in bufs.items()})
-        dout = dout.contiguous().float()
-        with L.on(dev):
-            L.check(L.lib().gr_sasrec_train_bwd_f32(ctypes.byref(p), L.ptr(seqs), B, n, float(ctx.p_drop), 0,
-                                                    L.ptr(ctx.seed), ctypes.byref(cb), L.ptr(dout), L.ptr(g_item),
-                                                    L.stream_of(dev)), "gr_sasrec_train_bwd_f32")
-        vec = g_vec.sum(0)   # every parameter's gradient but the item table's, in parameter order
-        shapes = [(d,), (d,), (3 * d, d), (3 * d,), (d, d), (d,), (d,), (d,), (m, d), (m,), (d, m), (d,)] * nb
-        shapes += [(d,), (d,)]
-        grads, off = [], 0
-        for shp in shapes:
-            k = 1
-            for x in shp:
-                k *= x
-            grads.append(vec[off:off + k].view(shp))
-            off += k
-        # rows n.. of pos_emb get zeros (a pad kernel rather than a copy into a zeros tensor, which
-        # keeps memset / memcpy nodes out of a captured step's graph)
-        dpos = torch.nn.functional.pad(vec[off:off + n * d].view(n, d), (0, 0, 0, max_len - n))
-        return (None, None, None, None, g_item, dpos, *grads)
+        return _sas_train_bwd(ctx, False, dout)
+
+
+class _SasTrainTiled(torch.autograd.Function):
+    """``_SasTrain`` on the tiled kernels of sasrec_train_tiled.hip (d <= 128, n <= 256, mlp_layer <=
+    256): the same saved activations and dropout masks; the products are tiled launches over all
+    B * n rows, and the backward leaves ``gr_sasrec_train_tiled_parts`` partial rows (split-k chunks
+    of the rows) instead of one per sequence.  Both calls take a workspace, allocated like the
+    saved buffers (inside a captured step: from the graph's pool)."""
+
+    @staticmethod
+    def forward(ctx, seqs, binding, p_drop, seed_snap, *params):
+        return _sas_train_fwd(ctx, True, seqs, binding, p_drop, seed_snap, params)
+
+    @staticmethod
+    def backward(ctx, dout):
+        return _sas_train_bwd(ctx, True, dout)
 
 
 def sasrec_train_forward(model, log_seqs):
@@ -1046,10 +1111,22 @@ def sasrec_train_forward(model, log_seqs):
     forward with dropout on the kernels, differentiable in every parameter it reads."""
     seqs = log_seqs.to(torch.int64).contiguous()
     L.require_gpu(seqs)
+    n = seqs.shape[1]
+    mode = getattr(model, "train_kernels", "auto")
+    if mode not in ("auto", "sequence", "tiled"):
+        raise ValueError(f"train_kernels must be 'auto', 'sequence' or 'tiled', got {mode!r}")
+    if mode == "sequence" and not sasrec_train_fits_sequence(model, n):
+        raise RuntimeError("train_kernels = 'sequence': the one-workgroup-per-sequence kernels take n, d <= 64 and "
+                           f"mlp_layer <= 128 (got n {n}, d {model.d}, mlp_layer {model.mlp_layer})")
+    tiled = mode == "tiled" or (mode == "auto" and not sasrec_train_fits_sequence(model, n))
+    if tiled and not sasrec_train_fits_tiled(model, n):
+        raise RuntimeError("the tiled training kernels take n <= 256, d <= 128 and mlp_layer <= 256 "
+                           f"(got n {n}, d {model.d}, mlp_layer {model.mlp_layer})")
     seed = dropout_seed(seqs.device)
     snap = seed + 0              # this step's masks (forward and backward read the same word); a kernel, not a copy
     seed.add_(1)
-    return _SasTrain.apply(seqs, sasrec_binding(model), float(model.dropout), snap, *_train_params(model))
+    fn = _SasTrainTiled if tiled else _SasTrain
+    return fn.apply(seqs, sasrec_binding(model), float(model.dropout), snap, *_train_params(model))
 
 
 class SasTrainStepGraph:

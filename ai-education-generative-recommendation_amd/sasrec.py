@@ -57,10 +57,13 @@ class SASRec(nn.Module):
         """model.py:49-96: ``[B, n]`` item ids -> ``[B, n, d]`` final hidden states.
 
         Eval mode (or grad disabled): one C-ABI call, ``gr_sasrec_forward_f32``, no autograd graph.
-        Train mode with grad enabled (the SASRec/train.py:131 call), dropout active: the fused
-        training kernels of sasrec_train.hip when the shape fits them (``ops.sasrec_train_forward``:
-        one launch forward, one launch backward -- ``gr_sasrec_train_fwd_f32`` /
-        ``gr_sasrec_train_bwd_f32``), otherwise the same blocks as torch modules under autograd
+        Train mode with grad enabled (the SASRec/train.py:131 call), dropout active: the training
+        kernels when the shape fits them (``ops.sasrec_train_forward``) -- for n, d <= 64 and
+        mlp_layer <= 128 one launch forward and one backward with a sequence per workgroup
+        (sasrec_train.hip, ``gr_sasrec_train_fwd_f32`` / ``gr_sasrec_train_bwd_f32``), up to n 256,
+        d 128 and mlp_layer 256 the tiled kernels (sasrec_train_tiled.hip,
+        ``gr_sasrec_train_tiled_fwd_f32`` / ``_bwd_f32``; ``train_kernels`` picks a set) --
+        otherwise the same blocks as torch modules under autograd
         (``fused_train = False`` forces the latter).  The step's scoring, loss and negative sampling
         are kernels too (``ops.sampled_bce_loss``, ``ops.neg_samples``)."""
         if self.training and torch.is_grad_enabled():
@@ -68,10 +71,15 @@ class SASRec(nn.Module):
         with torch.no_grad():
             return ops.sasrec_forward(self._binding(log_seqs), log_seqs)
 
-    # Train-mode forward on the fused training kernels (ops.sasrec_train_forward: one launch
-    # forward, one backward) whenever the shape fits them (n, d <= 64, mlp_layer <= 128); False
-    # keeps the module-by-module autograd path below (used by the parity tests as the reference).
+    # Train-mode forward on the training kernels (ops.sasrec_train_forward) whenever the shape fits
+    # them (n <= 256, d <= 128, mlp_layer <= 256); False keeps the module-by-module autograd path
+    # below (used by the parity tests as the reference).
     fused_train = True
+    # Which training kernels: "auto" -- one workgroup per sequence (sasrec_train.hip: one launch
+    # forward, one backward) when n, d <= 64 and mlp_layer <= 128, the tiled kernels
+    # (sasrec_train_tiled.hip) otherwise; "tiled" forces the tiled kernels; "sequence" forces the
+    # per-sequence kernels.  A forced set raises on a shape it does not take.
+    train_kernels = "auto"
 
     def _forward_autograd(self, log_seqs):
         """model.py:58-96 as module calls: E[s] + P[0..n), then per block a pre-LN causal
@@ -80,7 +88,7 @@ class SASRec(nn.Module):
         n = log_seqs.shape[1]
         if n > self.pos_emb.weight.shape[0]:
             raise IndexError(f"sequence length {n} exceeds max_len {self.pos_emb.weight.shape[0]}")
-        if self.fused_train and ops.sasrec_train_supported(self, n):
+        if self.fused_train and (self.train_kernels != "auto" or ops.sasrec_train_supported(self, n)):
             return ops.sasrec_train_forward(self, log_seqs)
         pos = torch.arange(n, device=log_seqs.device)
         x = self.item_emb(log_seqs) + self.pos_emb(pos).unsqueeze(0)

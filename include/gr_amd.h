@@ -324,8 +324,10 @@ int gr_sasrec_rank_f32(const gr_sasrec_params* p, const int64_t* seqs, int64_t B
 
 /* SASRec training, the transformer part of one step (SASRec/train.py:131 `model.forward` in train
  * mode and the backward that `loss.backward()`, train.py:161-172, runs through model.py:49-96).
- * One workgroup per sequence; n <= 64, d <= 64 (d % num_heads == 0), mlp_layer <= 128, <= 8 blocks.
- * Dropout p (params['dropout']) on the attention probabilities, the FFN hidden layer and the FFN
+ * Two kernel sets with the same saved activations and dropout masks: gr_sasrec_train_fwd_f32 /
+ * _bwd_f32, one workgroup per sequence, n <= 64, d <= 64 (d % num_heads == 0), mlp_layer <= 128,
+ * <= 8 blocks; and gr_sasrec_train_tiled_fwd_f32 / _bwd_f32 below, n <= 256, d <= 128,
+ * mlp_layer <= 256.  Dropout p (params['dropout']) on the attention probabilities, the FFN hidden layer and the FFN
  * output, as nn.MultiheadAttention / nn.Dropout apply it; masks from a counter-based hash keyed by
  * seed ^ *seed_dev (seed_dev optional), the same for the forward and the backward of one step.
  * Buffers (device, caller-allocated, fp32): nb = n_blocks, R = B * n rows (sequence-major). */
@@ -340,7 +342,8 @@ typedef struct gr_sasrec_train_bufs {
   float* zs;     /* [nb, R, mlp]  FFN1 output before the ReLU                             */
   float* us;     /* [nb, R, mlp]  dropout(relu(FFN1)) = FFN2 input                        */
   float* xl;     /* [R, d]        last LayerNorm input                                    */
-  float* g_vec;  /* [B, gr_sasrec_train_vec_width] (written by the backward) per-sequence partial
+  float* g_vec;  /* [B, gr_sasrec_train_vec_width] (written by the backward; the tiled backward:
+                    [gr_sasrec_train_tiled_parts, ...] split-k partials) per-sequence partial
                     gradients in SASRec's parameter order: per block [ln_a w, ln_a b, in_proj w
                     (3d x d), in_proj b, out_proj w (d x d), out_proj b, ln_f w, ln_f b, ffn1 w
                     (mlp x d), ffn1 b, ffn2 w (d x mlp), ffn2 b], then [last ln w, last ln b], then
@@ -364,6 +367,28 @@ int gr_sasrec_train_bwd_f32(const gr_sasrec_params* p, const int64_t* seqs, int6
                             float p_drop, uint64_t seed, const uint64_t* seed_dev,
                             const gr_sasrec_train_bufs* bufs, const float* d_out, float* g_item,
                             void* stream);
+
+/* The tiled training path (sasrec_train_tiled.hip) for shapes beyond one workgroup per sequence:
+ * 1 <= d <= 128 (divisible by n_heads), 1 <= n <= min(256, max_len), 1 <= mlp <= 256, 1..8
+ * blocks, any B >= 1 with B * n * n_heads < 2^31, dropout in [0, 1).  Same computation, saved activations
+ * (gr_sasrec_train_bufs) and dropout masks as the pair above; the products run as tiled launches
+ * over all B * n rows, and the backward writes bufs.g_vec as [parts, gr_sasrec_train_vec_width]
+ * partial rows (split-k chunks of the rows; their sum over parts is every parameter's gradient
+ * but the item table's).  Both calls need a caller-owned workspace. */
+size_t gr_sasrec_train_tiled_workspace_bytes(const gr_sasrec_params* p, int64_t B, int32_t n);
+
+/* Partial rows of bufs.g_vec the tiled backward writes (>= 1; 0 for bad arguments). */
+int32_t gr_sasrec_train_tiled_parts(const gr_sasrec_params* p, int64_t B, int32_t n);
+
+int gr_sasrec_train_tiled_fwd_f32(const gr_sasrec_params* p, const int64_t* seqs, int64_t B, int32_t n,
+                                  float p_drop, uint64_t seed, const uint64_t* seed_dev,
+                                  const gr_sasrec_train_bufs* bufs, float* out, int32_t* err_flag,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+
+int gr_sasrec_train_tiled_bwd_f32(const gr_sasrec_params* p, const int64_t* seqs, int64_t B, int32_t n,
+                                  float p_drop, uint64_t seed, const uint64_t* seed_dev,
+                                  const gr_sasrec_train_bufs* bufs, const float* d_out, float* g_item,
+                                  void* workspace, size_t workspace_bytes, void* stream);
 
 /* Full-catalog (or catalog-shard) scoring logits[B, rows] = h[B, d] . table[rows, d]^T
  * (SASRec/model.py:107).  ld = row stride of logits. */
