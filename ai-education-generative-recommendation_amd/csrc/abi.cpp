@@ -40,11 +40,14 @@ static std::atomic<int64_t> g_topk_half{2};
 // attn_k16 (hd 64 / 128 attention: 1 = 32-query tiles over 16-key steps at two waves per SIMD,
 // 0 = the persistent 32 x 32-step kernel; a different fp32 chain, both within the logits tolerance)
 static std::atomic<int64_t> g_attn_k16{1};
+// rq_filter (index-only quantize calls at e = 32, codebooks up to 1024 codes: 1 = split-bf16 filter
+// passes and the exact formula on the near-minimum codes only, 0 = every distance exact)
+static std::atomic<int64_t> g_rq_filter{1};
 
 static const Opt kOpts[] = {
     {"rq_fused", &g_rq_fused, 0, 1},   {"sas_fused", &g_sas_fused, 0, 3}, {"sas_rowtile", &g_sas_rowtile, 0, 1},
     {"lin_wres", &g_lin_wres, 0, 1},   {"emb_proj", &g_emb_proj, 0, 1},   {"topk_half", &g_topk_half, 0, 2},
-    {"attn_k16", &g_attn_k16, 0, 1},
+    {"attn_k16", &g_attn_k16, 0, 1},   {"rq_filter", &g_rq_filter, 0, 1},
 };
 
 static const Opt* find_opt(const char* name) {

@@ -29,6 +29,8 @@
 // update from the LDS row of the winner.  Residuals stay in registers across levels.  Codebooks
 // larger than one LDS chunk are streamed in chunks.  e <= 64 (padded with zero features to 16, 32
 // or 64: zero terms at the end of the fma chain change nothing).
+#include <atomic>
+
 #include "gr_common.h"
 #include "rq_quant.h"
 
@@ -333,6 +335,388 @@ __global__ __launch_bounds__(RQ_W * 64) void rq_quantize_kernel(
   }
 }
 
+// ---- the filtered quantizer: index-only calls at e = 32 (option "rq_filter") ----
+//
+// The call returns the argmin only, so only distances that can be the minimum need the exact
+// formula.  Per level and 32-item tile:
+//   pass 1   a_k = cn_k - 2 r.c_k from split-bf16 operands (3 v_mfma_f32_32x32x16_bf16 per 16 k,
+//            the accumulator starting at cn_k, +inf for padding rows), running minimum m (v_min3)
+//   pass 2   code k is marked when a_k <= m + 2E (rq_filter_bound, rq_quant.h: the derivation of E
+//            and why the exact winner and its ties are marked).  Codebooks of at most 256 codes
+//            (LIVE): the tile's 8 x 16 values of a stay in registers between the passes, one item
+//            tile at a time.  Larger ones: the same MFMAs run again, 256 codes at a time.
+//   walk     every lane re-scores its own marked codes in increasing index order with the exact
+//            kernel's formula (one fma chain over k = 0..31 on the VALU, the order the fp32 MFMA
+//            runs and mkl_dot restates; ATen-order norms) under strict '<'; merge_min joins the
+//            lane halves; index store and residual update as in the exact kernel
+// A lane whose m + 2E is not finite (NaN / inf inputs, overflowing norms) marks every code, so its
+// walk is the exact kernel's loop and the non-finite behaviour carries over.
+// LDS: the level's codebook as bf16 hi = rne(c) and lo = rne(c - hi) in one 128-byte row per code
+// (slot 4 kind + 2 h + t holds, for lane half h and MFMA step t, features 16t + 2i + h (i < 4) and
+// 16t + 8 + 2(i - 4) + h: the features a lane's residual registers hold), swizzled like the fp32
+// image; the norms; and, when it fits (K <= 512), the fp32 image for the walk and the winner's row
+// (else those rows come from global memory).  Codebooks of more than 1024 codes, e != 32 and the
+// calls that return distances stay on rq_quantize_kernel.  Tile plan: 8 waves, tile t_begin + w + 8i
+// for wave w (no code-quarter split, no resident levels); GR_FMAXT tiles per wave in registers.
+#ifndef GR_FDIAG
+#define GR_FDIAG 0   // diagnostic builds only (scripts/build_variant.sh): 1 no walk, 2 no pass 2 and no
+#endif               // walk, 4 no pass at all: staging, norms and the residual update (wrong IDs in
+                     // all three), 3 counts the re-scored codes per item and level
+#ifndef GR_FSB
+#define GR_FSB 1   // 0: no scheduling barrier between the live pass's code tiles (spills; A/B builds)
+#endif
+#ifndef GR_FLIVE
+#define GR_FLIVE 1   // 0: recompute the MFMAs in pass 2 at every K (A/B builds)
+#endif
+#ifndef GR_FMAXT
+#define GR_FMAXT 2   // item tiles per wave held in registers (3: 238 VGPRs, 4 spills)
+#endif
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+constexpr int RQF_KMAX = 1024;       // codes per level the bf16 image holds (128 KiB)
+constexpr int RQF_F32_KMAX = 512;    // ... with the fp32 image beside it
+
+__device__ __forceinline__ void split_bf16(float x, __bf16& hi, __bf16& lo) {
+#pragma clang fp contract(off)
+  hi = (__bf16)x;
+  lo = (__bf16)(x - (float)hi);
+}
+
+// a + the three split products of one 32 x 32 tile over k = 0..31
+__device__ __forceinline__ f32x16 filter_tile(const bf16x8 (&ah)[2], const bf16x8 (&al)[2], const bf16x8 (&bh)[2],
+                                              const bf16x8 (&bl)[2], f32x16 acc) {
+#pragma unroll
+  for (int t = 0; t < 2; ++t) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[t], bh[t], acc, 0, 0, 0);
+#pragma unroll
+  for (int t = 0; t < 2; ++t) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[t], bl[t], acc, 0, 0, 0);
+#pragma unroll
+  for (int t = 0; t < 2; ++t) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[t], bh[t], acc, 0, 0, 0);
+  return acc;
+}
+
+template <bool LIVE>
+__global__ __launch_bounds__(RQ_W * 64) void rq_filter_kernel(
+    const float* __restrict__ z, int64_t n, int L, RQLevels lv, int kch, int f32_lds,
+    int64_t* __restrict__ idx_out, int tiles, uint32_t* __restrict__ cand_out) {
+#pragma clang fp contract(off)
+  constexpr int EP = 32, HQ = 4, W = RQ_W, NT = W * 64, MAXT = GR_FMAXT;
+  if (LIVE) f32_lds = 1;   // 256 codes: the fp32 image always fits
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  float* bimg = sm;                    // [kch] rows of 8 swizzled 16-byte slots: bf16 hi | lo
+  float* cns = bimg + kch * EP;        // [kch]
+  float* wmax = cns + kch;             // [W] per-wave max of the level's norms (+ padding to 16 floats)
+  float* fimg = wmax + 16;             // [kch][EP] the exact kernel's fp32 image (f32_lds)
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 31, h = lane >> 5;
+  const int t_begin = (int)((int64_t)blockIdx.x * tiles / gridDim.x);
+  const int t_end = (int)((int64_t)(blockIdx.x + 1) * tiles / gridDim.x);
+  const int my = (t_end - t_begin - w + W - 1) / W;   // this wave's tiles t_begin + w + i W (<= MAXT)
+
+  // residual of this lane's item: half h holds features 8j + 2s + h
+  f32x4 res[MAXT][HQ];
+#pragma unroll
+  for (int i = 0; i < MAXT; ++i) {
+    const int64_t item = (int64_t)(t_begin + w + i * W) * 32 + r;
+    const bool ok = i < my && item < n;
+    const int64_t ic = ok ? item : 0;
+#pragma unroll
+    for (int j = 0; j < HQ; ++j) {
+      const f32x4 lo = *reinterpret_cast<const f32x4*>(z + ic * EP + 8 * j);
+      const f32x4 hi = *reinterpret_cast<const f32x4*>(z + ic * EP + 8 * j + 4);
+      const f32x4 v = h ? f32x4{lo[1], lo[3], hi[1], hi[3]} : f32x4{lo[0], lo[2], hi[0], hi[2]};
+      res[i][j] = ok ? v : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+  }
+
+  for (int l = 0; l < L; ++l) {
+    const int K = lv.K[l];
+    const float* __restrict__ cb = lv.cb[l];
+    const int ct_n = (K + 31) >> 5;
+    __syncthreads();   // the previous level's images fully consumed
+    for (int f = tid; f < 2 * K; f += NT) {   // 16 features of one code -> the four bf16 slots of step t
+      const int c = f >> 1, t = f & 1;
+      float x[16];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(cb + (int64_t)c * EP + 16 * t + 4 * q);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) x[4 * q + i] = v[i];
+      }
+#pragma unroll
+      for (int hh = 0; hh < 2; ++hh) {
+        bf16x8 vh, vl;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          __bf16 a, b;
+          split_bf16(x[(i < 4 ? 2 * i : 8 + 2 * (i - 4)) + hh], a, b);
+          vh[i] = a;
+          vl[i] = b;
+        }
+        *reinterpret_cast<bf16x8*>(bimg + cb_off<EP>(c, 2 * hh + t)) = vh;
+        *reinterpret_cast<bf16x8*>(bimg + cb_off<EP>(c, 4 + 2 * hh + t)) = vl;
+      }
+    }
+    if (f32_lds) stage_rows<EP, NT, true>(cb, EP, 0, K, fimg, tid);
+    float cmax = 0.f;   // max of the level's norms (a NaN norm is skipped: its code can never win)
+    for (int c = tid; c < (LIVE ? 256 : ct_n * 32); c += NT) {
+      float s = __builtin_inff();   // codes past K can never win
+      if (c < K) {
+        const float* row = cb + (int64_t)c * EP;
+        s = aten_rowsq([&](int f) { return row[f]; }, EP);
+        cmax = fmaxf(cmax, s);
+      }
+      cns[c] = s;
+    }
+    cmax = xmax<32>(xmax<16>(xmax<8>(xmax<4>(xmax<2>(xmax<1>(cmax))))));
+    if (lane == 0) wmax[w] = cmax;
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < W; ++i) cmax = fmaxf(cmax, wmax[i]);
+
+    float rn[MAXT], m[MAXT];
+#pragma unroll
+    for (int i = 0; i < MAXT; ++i) {
+      if (!LIVE) rn[i] = rn_exact<EP>(res[i], EP, h);
+      m[i] = __builtin_inff();
+    }
+    // -2 r (exact) of tile i, split: the B operands of the level
+    auto split_res = [&](int i, bf16x8 (&bh)[2], bf16x8 (&bl)[2]) {
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          __bf16 a, b;
+          split_bf16(-2.f * res[i][2 * t + (q >> 2)][q & 3], a, b);
+          bh[t][q] = a;
+          bl[t][q] = b;
+        }
+    };
+    // this lane's operands of code tile ct: its code row's bf16 slots and the 16 norms of its rows
+    auto load_codes = [&](int ct, bf16x8 (&ah)[2], bf16x8 (&al)[2], f32x16& cnv) {
+      const int code = min(ct * 32 + r, K - 1);   // rows past K: any valid row (norm = inf)
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        ah[t] = *reinterpret_cast<const bf16x8*>(bimg + cb_off<EP>(code, 2 * h + t));
+        al[t] = *reinterpret_cast<const bf16x8*>(bimg + cb_off<EP>(code, 4 + 2 * h + t));
+      }
+#pragma unroll
+      for (int g4 = 0; g4 < 4; ++g4) {
+        const f32x4 q = *reinterpret_cast<const f32x4*>(cns + ct * 32 + 8 * g4 + 4 * h);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) cnv[4 * g4 + i] = q[i];
+      }
+    };
+    float thr[MAXT], best[MAXT];
+    int bi[MAXT];
+    bool allm[MAXT];
+    uint32_t ncand[MAXT];
+#pragma unroll
+    for (int i = 0; i < MAXT; ++i) {
+      best[i] = __builtin_inff();
+      bi[i] = 0x7fffffff;
+      ncand[i] = 0;
+    }
+    // the threshold of tile i from its lane halves' minima
+    auto set_thr = [&](int i) {
+      m[i] = fminf(m[i], __shfl_xor(m[i], 32));
+      thr[i] = m[i] + 2.f * rq_filter_bound(rn[i], cmax);
+      allm[i] = !(fabsf(thr[i]) < __builtin_inff());   // NaN / inf: every code is re-scored
+      if (GR_FDIAG == 2) bi[i] = __float_as_int(thr[i]) & 0xff;   // keeps pass 1 alive
+    };
+    auto min16 = [](float t, const f32x16& a) {
+#pragma unroll
+      for (int v = 0; v < 16; v += 2) t = fminf(fminf(t, a[v]), a[v + 1]);
+      return t;
+    };
+    // 16 mark bits shifted into k: the sign of th - a, SET when a > th (not marked)
+    auto mark16 = [](uint32_t k, const f32x16& a, float th) {
+      const f32x16 d = th - a;
+#pragma unroll
+      for (int v = 0; v < 16; ++v) k = __builtin_amdgcn_alignbit(k, __float_as_uint(d[v]), 31);
+      return k;
+    };
+    // The walk over 8 code tiles from g0: bit 31 - 16 (u & 1) - v of nm[u / 2] is CLEAR when register
+    // v of code tile g0 + u is marked.
+    auto walk = [&](int i, int g0, const uint32_t (&nm)[4]) {
+      if (GR_FDIAG == 1) {   // keep pass 2 alive without the walk
+        bi[i] = min(bi[i], (int)((nm[0] ^ nm[1] ^ nm[2] ^ nm[3]) >> 1));
+        return;
+      }
+      uint32_t cm[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) cm[q] = allm[i] ? 0xffffffffu : ~nm[q];
+      if (__builtin_amdgcn_ballot_w64((cm[0] | cm[1] | cm[2] | cm[3]) != 0) == 0) return;
+      // the item's whole residual in feature order: ev[q] = feature 2q, od[q] = feature 2q + 1
+      float ev[16], od[16];
+#pragma unroll
+      for (int j = 0; j < HQ; ++j)
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+          const float own = res[i][j][s], oth = __shfl_xor(own, 32);
+          ev[4 * j + s] = h ? oth : own;
+          od[4 * j + s] = h ? own : oth;
+        }
+      while (__builtin_amdgcn_ballot_w64((cm[0] | cm[1] | cm[2] | cm[3]) != 0) != 0) {
+        // the lane's lowest marked code: the highest bit of its first non-zero word
+        const int q = cm[0] ? 0 : cm[1] ? 1 : cm[2] ? 2 : 3;
+        const uint32_t wd = cm[0] ? cm[0] : cm[1] ? cm[1] : cm[2] ? cm[2] : cm[3];
+        const bool act = wd != 0;
+        const int p = 31 - __clz((int)(wd | 1u));
+        const uint32_t keep = ~(1u << p);
+#pragma unroll
+        for (int qq = 0; qq < 4; ++qq) cm[qq] = qq == q ? cm[qq] & keep : cm[qq];
+        const int v = 15 - (p & 15);
+        const int cd = (g0 + 2 * q + (p < 16 ? 1 : 0)) * 32 + (v & 3) + 8 * (v >> 2) + 4 * h;
+        if (act && cd < K) {
+          float cr[EP];   // the code's row in feature order
+          if (f32_lds) {
+#pragma unroll
+            for (int sl = 0; sl < 2 * HQ; ++sl) {
+              const f32x4 t = *reinterpret_cast<const f32x4*>(fimg + cb_off<EP>(cd, sl));
+#pragma unroll
+              for (int s = 0; s < 4; ++s) cr[8 * (sl % HQ) + 2 * s + sl / HQ] = t[s];
+            }
+          } else {
+#pragma unroll
+            for (int sl = 0; sl < EP / 4; ++sl) {
+              const f32x4 t = *reinterpret_cast<const f32x4*>(cb + (int64_t)cd * EP + 4 * sl);
+#pragma unroll
+              for (int s = 0; s < 4; ++s) cr[4 * sl + s] = t[s];
+            }
+          }
+          float chain = 0.f;
+#pragma unroll
+          for (int k = 0; k < EP; ++k) chain = fmaf(cr[k], (k & 1) ? od[k >> 1] : ev[k >> 1], chain);
+          const float dd = fmaf(-2.f, chain, rn[i] + cns[cd]);
+          const bool lt = dd < best[i];
+          bi[i] = lt ? cd : bi[i];
+          best[i] = lt ? dd : best[i];
+          ++ncand[i];
+        }
+      }
+    };
+    // merge the lane halves, write, update the residual
+    auto finish = [&](int i) {
+      float sec = 0.f;
+      merge_min<false>(best[i], sec, bi[i], __shfl_xor(best[i], 32), 0.f, __shfl_xor(bi[i], 32));
+      int b = bi[i];
+      if (b >= K || b < 0) b = 0;   // no finite distance (NaN/inf input): torch.argmin -> 0
+      const int64_t item = (int64_t)(t_begin + w + i * W) * 32 + r;
+      if (h == 0 && item < n) idx_out[item * L + l] = (int64_t)b;
+      if (GR_FDIAG == 3) {
+        const uint32_t tot = ncand[i] + __shfl_xor(ncand[i], 32);
+        if (h == 0 && item < n && cand_out) cand_out[item * L + l] = tot;
+      }
+      f32x4 cw[HQ];
+      if (f32_lds) {
+#pragma unroll
+        for (int j = 0; j < HQ; ++j) cw[j] = *reinterpret_cast<const f32x4*>(fimg + cb_off<EP>(b, HQ * h + j));
+      } else {
+#pragma unroll
+        for (int j = 0; j < HQ; ++j) {
+          const f32x4 lo = *reinterpret_cast<const f32x4*>(cb + (int64_t)b * EP + 8 * j);
+          const f32x4 hi = *reinterpret_cast<const f32x4*>(cb + (int64_t)b * EP + 8 * j + 4);
+          cw[j] = h ? f32x4{lo[1], lo[3], hi[1], hi[3]} : f32x4{lo[0], lo[2], hi[0], hi[2]};
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < HQ; ++j)
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+          const float xq = res[i][j][s] + (cw[j][s] - res[i][j][s]);   // vq.py:95
+          res[i][j][s] = res[i][j][s] - xq;                            // rq.py:47
+        }
+    };
+    if constexpr (LIVE) {
+      // K <= 256: a tile's 8 x 16 values of a stay in registers between the passes
+#pragma unroll
+      for (int i = 0; i < MAXT; ++i) {
+        if (i < my && GR_FDIAG == 4) {
+          rn[i] = 0.f;
+          finish(i);
+        } else if (i < my) {   // wave-uniform
+          f32x16 acc[8];
+          float t = __builtin_inff();
+          bf16x8 bh[2], bl[2];
+          split_res(i, bh, bl);
+          rn[i] = rn_exact<EP>(res[i], EP, h);
+#pragma unroll
+          for (int u = 0; u < 8; ++u)
+          {   // all 8 code tiles: the rows past K have the norm +inf
+            bf16x8 ah[2], al[2];
+            f32x16 cnv;
+            load_codes(u, ah, al, cnv);
+            acc[u] = filter_tile(ah, al, bh, bl, cnv);
+#if GR_FSB
+            t = min16(t, acc[u]);
+            __builtin_amdgcn_sched_barrier(0);   // no operand loads hoisted across code tiles: registers
+#endif
+          }
+#if !GR_FSB
+#pragma unroll
+          for (int u = 0; u < 8; ++u) t = min16(t, acc[u]);
+#endif
+          m[i] = t;
+          set_thr(i);
+          if (GR_FDIAG == 2) {
+            finish(i);
+            continue;
+          }
+          uint32_t nm[4];
+#pragma unroll
+          for (int u = 0; u < 8; ++u) {
+            nm[u >> 1] = mark16((u & 1) ? nm[u >> 1] : 0u, acc[u], thr[i]);
+            __builtin_amdgcn_sched_barrier(0);
+          }
+          walk(i, 0, nm);
+          finish(i);
+        }
+      }
+    } else {
+      bf16x8 bh[MAXT][2], bl[MAXT][2];
+#pragma unroll
+      for (int i = 0; i < MAXT; ++i) split_res(i, bh[i], bl[i]);
+      // pass 1: the minimum of a over the level's codes
+#pragma unroll 1
+      for (int ct = 0; ct < (GR_FDIAG == 4 ? 0 : ct_n); ++ct) {
+        bf16x8 ah[2], al[2];
+        f32x16 cnv;
+        load_codes(ct, ah, al, cnv);
+#pragma unroll
+        for (int i = 0; i < MAXT; ++i)
+          if (i < my) m[i] = min16(m[i], filter_tile(ah, al, bh[i], bl[i], cnv));   // wave-uniform
+      }
+#pragma unroll
+      for (int i = 0; i < MAXT; ++i) set_thr(i);
+      // pass 2 (the same MFMAs again) and the walk, 8 code tiles at a time
+      for (int g0 = 0; g0 < (GR_FDIAG == 2 || GR_FDIAG == 4 ? 0 : ct_n); g0 += 8) {
+        uint32_t nmk[MAXT][4];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          if (g0 + u < ct_n) {   // workgroup-uniform
+            bf16x8 ah[2], al[2];
+            f32x16 cnv;
+            load_codes(g0 + u, ah, al, cnv);
+#pragma unroll
+            for (int i = 0; i < MAXT; ++i)
+              if (i < my)
+                nmk[i][u >> 1] = mark16((u & 1) ? nmk[i][u >> 1] : 0u, filter_tile(ah, al, bh[i], bl[i], cnv), thr[i]);
+          } else {
+#pragma unroll
+            for (int i = 0; i < MAXT; ++i) nmk[i][u >> 1] = (((u & 1) ? nmk[i][u >> 1] : 0u) << 16) | 0xffffu;
+          }
+        }
+#pragma unroll
+        for (int i = 0; i < MAXT; ++i)
+          if (i < my) walk(i, g0, nmk[i]);
+      }
+#pragma unroll
+      for (int i = 0; i < MAXT; ++i)
+        if (i < my) finish(i);
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void rq_code_norms_kernel(const float* __restrict__ cb, int K,
                                                             int e, float* __restrict__ cn) {
   const int c = blockIdx.x * 256 + threadIdx.x;
@@ -393,9 +777,47 @@ static int launch_quantize_e(const float* z, int64_t n, int e, int L, const RQLe
   return check_launch("gr_rq_quantize_f32");
 }
 
+static std::atomic<int64_t> g_filter_launches{0};
+static std::atomic<uint32_t*> g_filter_counts{nullptr};   // GR_FDIAG == 3 builds: [n][L] re-scored codes
+
+// The filtered kernel takes index-only calls at e = 32 whose levels fit its bf16 image.
+static bool filter_ok(int e, int L, const RQLevels& lv, const float* best, const float* gap) {
+  if (e != 32 || best || gap || option("rq_filter") != 1) return false;
+  for (int l = 0; l < L; ++l)
+    if (lv.K[l] > RQF_KMAX) return false;
+  return true;
+}
+
+static int launch_filter(const float* z, int64_t n, int L, const RQLevels& lv, int64_t* idx, hipStream_t st) {
+  int kmax = 0;
+  for (int l = 0; l < L; ++l) kmax = lv.K[l] > kmax ? lv.K[l] : kmax;
+  const bool live = GR_FLIVE && kmax <= 256;   // the kernel then sweeps 256 rows at every level
+  const int kch = live ? 256 : (kmax + 31) & ~31;
+  const int f32_lds = kch <= RQF_F32_KMAX;
+  const size_t lds = (size_t)kch * 32 * 4 * (f32_lds ? 2 : 1) + (size_t)kch * 4 + 16 * 4;
+  const int64_t tiles = (n + 31) / 32;
+  // persistent, as launch_quantize_e: one workgroup per CU, more only when a range would exceed
+  // the register-resident residuals
+  int64_t grid = (int64_t)cu_count();
+  const int64_t min_grid = (tiles + RQ_W * GR_FMAXT - 1) / (RQ_W * GR_FMAXT);
+  if (grid < min_grid) grid = min_grid;
+  if (grid > tiles) grid = tiles;
+  if (grid > 0x7fffffffLL || tiles > 0x7fffffffLL) return fail(GR_ERR_UNSUPPORTED, "rq quantize: n too large");
+  auto k = live ? rq_filter_kernel<true> : rq_filter_kernel<false>;
+  if (lds > 64 * 1024 &&
+      hipFuncSetAttribute(reinterpret_cast<const void*>(k),
+                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    return fail(GR_ERR_HIP, "rq quantize: cannot raise the LDS limit");
+  hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(RQ_W * 64), lds, st, z, n, L, lv, kch, f32_lds,
+                     idx, (int)tiles, g_filter_counts.load());
+  g_filter_launches.fetch_add(1);
+  return check_launch("gr_rq_quantize_f32");
+}
+
 static int launch_quantize(const float* z, int64_t n, int e, int L, const RQLevels& lv,
                            int64_t* idx, float* best, float* gap, hipStream_t st) {
   if (n == 0) return GR_OK;
+  if (filter_ok(e, L, lv, best, gap)) return launch_filter(z, n, L, lv, idx, st);
   if (e <= 16) return launch_quantize_e<16>(z, n, e, L, lv, idx, best, gap, st);
   if (e <= 32) return launch_quantize_e<32>(z, n, e, L, lv, idx, best, gap, st);
   if (e <= 64) return launch_quantize_e<64>(z, n, e, L, lv, idx, best, gap, st);
@@ -440,6 +862,12 @@ extern "C" int32_t gr_mkl_plan(int64_t M, int32_t K, int32_t N, int32_t* kind, i
   if (kb) *kb = p.kb;
   return gr::mkl_plan_pinned(M, K, N) ? 1 : 0;
 }
+
+extern "C" float gr_rq_filter_bound_f32(float rn, float cmax2) { return gr::rq_filter_bound(rn, cmax2); }
+
+extern "C" int64_t gr_rq_filter_launches(void) { return gr::g_filter_launches.load(); }
+
+extern "C" void gr_rq_filter_diag_counts(uint32_t* counts) { gr::g_filter_counts.store(counts); }
 
 extern "C" int gr_rq_codebook_norms_f32(const float* codebook, int32_t K, int32_t e, float* cn_out,
                                         void* stream) {

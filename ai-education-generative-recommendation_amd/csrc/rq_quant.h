@@ -86,4 +86,36 @@ __device__ __forceinline__ void merge_min(float& best, float& second, int& bi, f
   bi = take ? oi : bi;
 }
 
+// ---- the filtered quantizer (rq_filter_kernel, rq.hip) ----
+//
+// a_k = cn_k - 2 r.c_k from split-bf16 operands (x = hi + lo, the products hi.hi + hi.lo + lo.hi
+// accumulated in fp32 by v_mfma_f32_32x32x16_bf16) approximates T_k = cn_k - 2 r.c_k in real
+// arithmetic, cn_k the ATen-order norm the exact formula uses; the exact kernel's distance is
+// D_k = fl(fl(rn + cn_k) - 2 chain_k).  rq_filter_bound returns E with
+//     |a_k - T_k| + |D_k - (rn + T_k)| <= E     for every code k of the level,
+// so for the exact winner k* (D_k* <= D_j) and any j:  a_k* <= a_j + 2E.  Every code within 2E of
+// the minimum of a is re-scored exactly, hence k* and every code that ties with it are.
+//
+// With R = |r|, C = max_k |c_k|, cn <= C^2, u = 2^-9 (bf16 RNE) and e <= 64:
+//   split:   |x - hi| <= u |x|, x - hi is an fp32 number, |x - hi - lo| <= u^2 |x|, |lo| <= 1.01 u |x|.
+//            r c - (hi hi + hi lo + lo hi) = (r c - (hi+lo)(hi+lo)) + lo lo, at most 3.01 u^2 |r||c|
+//            per feature, so (Cauchy-Schwarz) 2 x 3.01 x 2^-18 R C            <= 2^-15.4 R C
+//   MFMA:    the products are exact in fp32; 3 e/16 <= 12 instructions add at most 193 terms to
+//            cn in an unspecified order, every add rounded or truncated to fp32 (2^-23 relative):
+//            192 x 2^-23 x (cn + 2.02 R C)                       <= 2^-15.4 cn + 2^-14.4 R C
+//            (e = 32: half of that)
+//   exact:   chain: 64 x 2^-24 R C, doubled                                   <= 2^-17 R C
+//            rn + cn and the final fma, 2^-24 each of at most rn + cn + 2 R C <= 2^-22 (rn + cn)
+//   norms:   rn, cn stand for R^2, C^2 within 2^-18 relative (64 rounded adds): absorbed below
+//   tiny:    operands or products that are denormal or flushed move every term by at most 2^-126:
+//            at most 2^-119 + 2^-120 (R + C)
+//   total <= 2^-13.5 R C + 2^-15.3 (rn + C^2) + tiny; the constants below leave a factor >= 1.2 for
+//   the norms and for the rounding of m + 2E itself (2^-24 |m|, |m| <= C^2 + 2 R C).
+// A non-finite rn or Cmax^2 gives a non-finite E: the kernel then re-scores every code.
+__host__ __device__ inline float rq_filter_bound(float rn, float cmax2) {
+#pragma clang fp contract(off)
+  const float R = __builtin_sqrtf(rn), C = __builtin_sqrtf(cmax2);
+  return (0x1p-13f * (R * C) + 0x1p-15f * (rn + cmax2)) + 0x1p-116f * ((R + C) + 1.f);
+}
+
 }  // namespace gr

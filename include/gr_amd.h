@@ -75,6 +75,11 @@ const char* gr_last_error(void);
  *   "attn_k16"      1 (default): head width 128 attention on 32-query tiles over 16-key steps at
  *                   two waves per SIMD; 0: 32 x 32 steps at one wave per SIMD.  Different fp32
  *                   chains of the same attention (both within the logits tolerance).
+ *   "rq_filter"     1 (default): index-only quantize calls (gr_rq_quantize_f32 and the encode entry
+ *                   points with best_out = gap_out = NULL) at e_dim 32 and at most 1024 codes per
+ *                   level run the filtered kernel: a split-bf16 pass bounds every distance, and the
+ *                   exact fp32 formula runs only on the codes within the bound of the minimum;
+ *                   0: every distance exact.  The IDs are bitwise the same, exact ties included.
  * A last-position forward (predict, last_hidden) runs its final block as the one-query tail on
  * LN_a(X): q . K_j = (W_k^T q) . H_j (+ a term constant over j that cancels in the softmax) and
  * p . V = W_v (p . H) + b_v, so K|V of the B n rows are never projected (sas_tail_h2_kernel; the
@@ -198,6 +203,16 @@ int gr_mlp_exact_groups_f32(const float* x, int64_t n, int32_t n_linear, const i
  * this order.  Returns 1 when (M, K, N) lies in the envelope checked bit for bit against torch on
  * that host, 0 outside it (the order is then mkl_plan's best restatement, parity unpinned). */
 int32_t gr_mkl_plan(int64_t M, int32_t K, int32_t N, int32_t* kind, int32_t* kb);
+
+/* The filtered quantizer ("rq_filter").  gr_rq_filter_bound_f32: the bound E the kernel uses, from
+ * an item's |r|^2 and the level's largest |c|^2 (host arithmetic, no device): the split-bf16 value
+ * a_k = |c_k|^2 - 2 r.c_k is within E of the exact kernel's distance minus |r|^2, and every code with
+ * a_k <= min a + 2E is re-scored exactly.  gr_rq_filter_launches: launches of the filtered kernel by
+ * this process so far.  gr_rq_filter_diag_counts: a device buffer [n][L] (uint32) that diagnostic
+ * builds (-DGR_FDIAG=3) fill with the number of codes re-scored per item and level; NULL: none. */
+float gr_rq_filter_bound_f32(float rn, float cmax2);
+int64_t gr_rq_filter_launches(void);
+void gr_rq_filter_diag_counts(uint32_t* counts);
 
 /* MLPLayers.forward in train mode (RQ-VAE/models/layers.py:18-43, [Dropout -> Linear -> ReLU] x
  * (n_linear - 1), then Dropout -> Linear; RQVAE.forward under RQ-VAE/train.py:113).  Dropout p_drop
