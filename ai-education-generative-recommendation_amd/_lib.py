@@ -125,6 +125,9 @@ SIGNATURES = {
     "gr_score_topk_workspace_bytes": (_sz, [_i64, _i32, _i64, _i32]),
     "gr_score_topk_f32": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp,
                                          _vp, _vp, _sz, _vp]),
+    "gr_code_groups_workspace_bytes": (_sz, [_i64, _i32]),
+    "gr_code_groups_i64": (ctypes.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gr_code_segments_i64": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

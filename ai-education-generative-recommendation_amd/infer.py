@@ -12,6 +12,10 @@
    is still shared;
 4. ``np.save`` of the (N, L+1) code array and the ``_mapping.json`` index -> code table
    (infer.py:164-184).
+
+Step 2's grouping and step 3 run on host tuples by default (``collision_groups``, ``dedup_codes``:
+the literal restatement, quadratic in the shared codes) or, with ``grouping="device"``, on the GPU
+(``ops.code_groups``, csrc/codes.hip): the same integers with the codes resident on the device.
 """
 import collections
 import json
@@ -20,6 +24,7 @@ import os
 import numpy as np
 import torch
 
+from . import ops
 from .data import EmbDataset
 
 
@@ -42,13 +47,67 @@ def dedup_codes(codes):
     return codes_array
 
 
+def collision_groups_device(codes_t):
+    """``collision_groups`` of a device int64 [N, L] tensor on the GPU (``ops.code_groups``):
+    ``(rows [M], sizes [G])`` device tensors, the groups concatenated in the same order and the size
+    of each.  Slicing them to M and G reads the four stats words back once."""
+    g = ops.code_groups(codes_t)
+    return g.rows, g.sizes
+
+
+def dedup_codes_device(codes_t):
+    """``dedup_codes`` of a device int64 [N, L] tensor on the GPU: the [N, L+1] int64 device tensor
+    with the digit column.  No synchronisation."""
+    return torch.cat((codes_t, ops.code_groups(codes_t).digit[:, None]), 1)
+
+
+def collision_rate(codes_t):
+    """(N - distinct codes) / N of a device int64 [N, L] tensor -- the number RQ-VAE/train.py:127-151
+    gets by joining every row into a string and building a Python set."""
+    n = codes_t.shape[0]
+    if not n:
+        return 0.0
+    return (n - ops.code_groups(codes_t, listing=False).host()[0][0]) / n
+
+
+def _generate_codes_device(model, x, max_rounds, log, batch_size):
+    """``generate_codes``' rounds with the codes resident on the device: per round one small read of
+    the stats and group sizes (``get_indices_groups`` picks each group's MKL call order from its size
+    on the host), the gather of x and the scatter of the new codes on the device."""
+    codes = model.get_indices_batched(x, batch_size).clone()
+    for vq in model.rq.vq_layers[:-1]:                        # infer.py:109-110
+        vq.sk_epsilon = 0.0
+    rounds = 0
+    while True:
+        g = ops.code_groups(codes)
+        (distinct, max_count, _, n_groups), sizes = g.host()
+        if not n_groups or rounds == max_rounds:
+            break
+        if log:
+            log(f"Iteration {rounds}: Found {n_groups} collision groups")
+        rows = g.rows
+        codes[rows] = model.get_indices_groups(x[rows], sizes.tolist())
+        rounds += 1
+    tot = codes.shape[0]
+    stats = {"rounds": rounds, "max_conflicts": max_count if tot else 0,
+             "collision_rate": (tot - distinct) / tot if tot else 0.0}
+    final = torch.cat((codes, g.digit[:, None]), 1).cpu().numpy()
+    return np.ascontiguousarray(final[:, :-1]), final, stats
+
+
 @torch.no_grad()
-def generate_codes(model, embeddings, device, max_rounds=30, log=None, batch_size=64):
+def generate_codes(model, embeddings, device, max_rounds=30, log=None, batch_size=64, grouping="host"):
     """Steps 1-3 for ``embeddings`` [N, in_dim] (numpy or tensor).  Returns (codes [N, L] after the
     collision rounds, codes_array [N, L+1] with the dedup digit, stats).  ``batch_size``: the
-    reference DataLoader's (infer.py:85)."""
+    reference DataLoader's (infer.py:85).  ``grouping``: "host" groups and numbers the codes with
+    ``collision_groups`` / ``dedup_codes`` on host tuples; "device" keeps the codes on the GPU and
+    uses ``ops.code_groups`` (the same integers; the codes reach the host once, at the end)."""
+    if grouping not in ("host", "device"):
+        raise ValueError(f"generate_codes: grouping must be 'host' or 'device', got {grouping!r}")
     x = torch.as_tensor(np.asarray(embeddings, dtype=np.float32) if not torch.is_tensor(embeddings)
                         else embeddings, dtype=torch.float32).to(device)
+    if grouping == "device":
+        return _generate_codes_device(model, x, max_rounds, log, batch_size)
     codes = model.get_indices_batched(x, batch_size).cpu().numpy()
     for vq in model.rq.vq_layers[:-1]:                        # infer.py:109-110
         vq.sk_epsilon = 0.0
@@ -80,11 +139,11 @@ def save_codes(codes_array, output_file):
     return mapping_file
 
 
-def infer(params, model=None, data=None, log=print):
+def infer(params, model=None, data=None, log=print, grouping="host"):
     """RQ-VAE/infer.py:infer(params) with the same params keys (RQ-VAE/main.py:4-33).  The
     checkpoint ``<ckpt_dir>/best_collision_model.pth`` is read with ``weights_only=True`` (a
     reference checkpoint also pickles its args dict; pass ``model=`` to use an already-loaded
-    one)."""
+    one).  ``grouping``: ``generate_codes``' ("host" or "device")."""
     from .rqvae import RQVAE
     device = torch.device(params["device"])
     if data is None:
@@ -103,7 +162,7 @@ def infer(params, model=None, data=None, log=print):
         elif log:
             log(f"Warning: No checkpoint found at {ckpt_path}, using randomly initialized model")
     model = model.to(device).eval()
-    codes, codes_array, stats = generate_codes(model, data.embeddings, device, log=log)
+    codes, codes_array, stats = generate_codes(model, data.embeddings, device, log=log, grouping=grouping)
     if log:
         log(f"All indices number: {len(codes)}; max conflicts {stats['max_conflicts']}; "
             f"collision rate {stats['collision_rate']}")

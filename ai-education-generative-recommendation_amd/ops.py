@@ -639,6 +639,86 @@ def rq_quantize_sk(z, codebooks, sk_eps, sk_iters, group_sizes=None):
     return idx
 
 
+class CodeGroups:
+    """Result of ``code_groups``: everything is on the device and nothing has been synchronised.
+
+    ``leader`` / ``count`` / ``digit`` [n] int64 per row; ``stats`` [4] int64 = (distinct codes,
+    largest count, M = rows of shared codes, G = shared codes).  ``rows`` [M] and ``sizes`` [G] are
+    slices of buffers padded to n and n // 2 entries: taking them needs M and G on the host, so the
+    first access reads ``stats`` back (``host()``: the one device-to-host read, cached)."""
+    SIZES_HEAD = 8192   # group sizes that ride along with the stats in host()'s one read
+
+    def __init__(self, n, leader, count, digit, rows_buf, meta):
+        self.n, self.leader, self.count, self.digit = n, leader, count, digit
+        self._rows, self._meta, self._host = rows_buf, meta, None
+
+    @property
+    def stats(self):
+        return self._meta[:4]
+
+    def host(self):
+        """``((distinct, max_count, M, G), sizes)`` on the host (ints; sizes a numpy int64 array, None
+        without a listing): one read of the stats with the first ``SIZES_HEAD`` sizes behind them,
+        and a second read only when there are more groups than that."""
+        if self._host is None:
+            listing = self._rows is not None
+            head = self._meta[:4 + self.SIZES_HEAD if listing else 4].cpu()
+            st = tuple(int(v) for v in head[:4])
+            sizes = None
+            if listing:
+                g = st[3]
+                sizes = (head[4:4 + g] if g <= self.SIZES_HEAD else self._meta[4:4 + g].cpu()).numpy()
+            self._host = (st, sizes)
+        return self._host
+
+    @property
+    def rows(self):
+        if self._rows is None:
+            raise RuntimeError("code_groups(listing=False) has no group listing")
+        return self._rows[:self.host()[0][2]]
+
+    @property
+    def sizes(self):
+        if self._rows is None:
+            raise RuntimeError("code_groups(listing=False) has no group listing")
+        return self._meta[4:4 + self.host()[0][3]]
+
+
+def code_groups(codes, listing=True):
+    """Collision groups and dedup digit of ``codes`` [n, L] (RQ-VAE/infer.py:29-41 and :139-162) as a
+    ``CodeGroups``.  The hash build, the lookup and the segment pass over the sorted keys are HIP
+    (codes.hip); the sort of the packed ``leader << 32 | row`` keys between them is ``torch.sort``
+    on the device (the keys past M hold INT64_MAX, so no size has to reach the host).  Performs no
+    synchronisation.  ``listing=False``: leader / count / stats only (digit stays zero)."""
+    L.require_gpu(codes)
+    if codes.dim() != 2 or codes.dtype != torch.int64:
+        raise TypeError(f"code_groups takes an int64 [n, L] tensor, got {codes.dtype} {tuple(codes.shape)}")
+    codes = codes.contiguous()
+    n, levels = codes.shape
+    dev = codes.device
+    lib = L.lib()
+    leader, count, digit = (torch.empty(n, dtype=torch.int64, device=dev) for _ in range(3))
+    meta = (torch.empty if n else torch.zeros)(4 + max(n // 2, 1), dtype=torch.int64, device=dev)
+    rows_buf = torch.empty(n, dtype=torch.int64, device=dev) if listing else None
+    if n == 0:
+        if levels < 1:
+            raise RuntimeError("code_groups: codes need at least one level")
+        return CodeGroups(n, leader, count, digit, rows_buf, meta)
+    keys = torch.empty(n, dtype=torch.int64, device=dev)
+    nbytes = lib.gr_code_groups_workspace_bytes(n, levels)
+    wsp = L.workspace(nbytes, dev)
+    with L.on(dev):
+        L.check(lib.gr_code_groups_i64(L.ptr(codes), n, levels, L.ptr(leader), L.ptr(count), L.ptr(digit),
+                                       L.ptr(keys), L.ptr(meta), L.ptr(wsp), nbytes, L.stream_of(dev)),
+                "gr_code_groups_i64")
+        if listing:
+            keys = torch.sort(keys).values
+            L.check(lib.gr_code_segments_i64(L.ptr(keys), n, L.ptr(meta), L.ptr(count), L.ptr(rows_buf),
+                                             L.ptr(meta[4:]), L.ptr(digit), L.ptr(wsp), nbytes,
+                                             L.stream_of(dev)), "gr_code_segments_i64")
+    return CodeGroups(n, leader, count, digit, rows_buf, meta)
+
+
 class SasrecBinding:
     """Device-pointer view of a SASRec module's parameters (``gr_sasrec_params``).
 

@@ -525,6 +525,41 @@ int gr_neg_samples_dseed(const int64_t* seqs, int64_t B, int32_t n, int64_t item
                          uint64_t seed, const uint64_t* seed_dev, int64_t* out, int32_t* err_flag,
                          void* stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Semantic-ID emission: collision groups and dedup digit (RQ-VAE/infer.py:29-41 get_collision_item,
+ * infer.py:139-162 the dedup digit, RQ-VAE/train.py:127-151 the collision rate) for codes[n, levels]
+ * int64, 0 <= n < 2^31, 1 <= levels <= 16.  Rows are compared as whole rows of full int64 values.
+ * Pure integer work: every output is a function of the input alone (no arrival-order dependence).
+ *
+ * gr_code_groups_i64 replaces the per-row Python dict of get_collision_item and train.py's set of
+ * joined strings.  Per row r (all [n] int64):
+ *   leader[r] = the smallest row whose code equals row r's,
+ *   count[r]  = the rows that carry that code,
+ *   digit[r]  = 0 (gr_code_segments_i64 fills the rows of shared codes in).
+ * keys[n]: the rows with count > 1 as leader << 32 | row, in no particular order, in keys[0 .. M);
+ * keys[M .. n) = INT64_MAX, so an ascending sort of all n keys leaves the M real ones first.
+ * stats[4]: {distinct codes, largest count, M = rows with count > 1, G = codes with count > 1}.
+ * workspace: gr_code_groups_workspace_bytes(n, levels) bytes, 8-byte aligned (an open-addressing
+ * table of at least 2 n slots, cleared by the call itself); the query returns 0 for a bad shape and
+ * does not decrease with n.  The same workspace is large enough for gr_code_segments_i64.
+ * n = 0 succeeds and launches nothing (no output is written). */
+size_t gr_code_groups_workspace_bytes(int64_t n, int32_t levels);
+int gr_code_groups_i64(const int64_t* codes, int64_t n, int32_t levels, int64_t* leader, int64_t* count,
+                       int64_t* digit, int64_t* keys, int64_t* stats, void* workspace,
+                       size_t workspace_bytes, void* stream);
+
+/* The group listing from the ASCENDING-sorted keys of gr_code_groups_i64 (sorted_keys[n], the same
+ * stats / count / digit; M and G are read from stats on the device, so the host need not know them):
+ *   rows[n]      rows[0 .. M) = the rows with count > 1 ordered by leader (the code's first
+ *                appearance), then by row -- get_collision_item's groups concatenated; the rest -1,
+ *   sizes[n / 2] sizes[0 .. G) = the size of each group in the same order (the rest is not written),
+ *   digit[row]   = the row's position in its group (infer.py:151-162's `codes_array[idx, -1] = i`),
+ *                written for rows[0 .. M) only.
+ * workspace: at least 8 ceil(n / 256) bytes, 8-byte aligned.  n = 0 succeeds and launches nothing. */
+int gr_code_segments_i64(const int64_t* sorted_keys, int64_t n, const int64_t* stats, const int64_t* count,
+                         int64_t* rows, int64_t* sizes, int64_t* digit, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
