@@ -17,7 +17,13 @@
 //   L1  h1^T[256 x 32FP] = W1 . x^T   wave w owns features [32w, 32w+32) for all FP item tiles;
 //       W1 fragments go straight from L2 to registers, software-pipelined one 32-deep group ahead;
 //       the x chunk ([32FP x 64]) is shared through a double-buffered LDS image staged one chunk
-//       ahead (across pass boundaries too).  Item tile 0's fragments are read from that image one
+//       ahead (across pass boundaries too).  x and W1 are fetched with buffer loads: a scalar
+//       resource (for x one per pass and image half, its byte count ending at the last row that
+//       exists and belongs to the pass, so ragged tiles are zero-filled by the range check and no
+//       address past x is ever formed), a per-lane byte offset that never changes, and the chunk /
+//       k-group offset as a scalar -- the chunk loop does no vector address arithmetic, no selects
+//       and no register shuffling for the image write (4 VALU instructions per 64 MFMAs, from 33:
+//       profiles/r12/encoder_chunk_loop_isa.txt; 75 -> 69 cycles per MFMA per SIMD).  Item tile 0's fragments are read from that image one
 //       32-deep group before their MFMAs (FusedCtx::read_bxa) -- group 0's right behind the chunk
 //       barrier, with the last four MFMAs of the chunk before still to issue -- and item tile 1's
 //       under tile 0's first MFMAs, so no ds_read is waited for with the MFMA pipe empty.  At the
@@ -69,6 +75,7 @@ struct FusedCfg {
   static constexpr int XV = PI * 16 / NTH;
   static constexpr int LDS = 2 * PI * FXP + PI * P1 + PI * P2 + E * P3;
   static_assert(H1 == 32 * FWV && H2 == 128, "8-wave form: H1 = 256, H2 = 128");
+  static_assert(XV == FP, "x staging: a thread's float4 i is a row of item tile i (XSrc)");
 };
 
 // A 16-byte load from a pointer known to be global memory.  The weight and bias pointers of the later
@@ -79,19 +86,53 @@ __device__ __forceinline__ f32x4 ldg4(const float* p) {
   return *reinterpret_cast<const __attribute__((address_space(1))) f32x4*>(reinterpret_cast<uintptr_t>(p));
 }
 
-// Packed-order position of the 4 consecutive features k0..k0+3 (k0 % 4 == 0) of a 32-deep group:
-// feature 8j + 2s + h sits at 16h + 4j + s, so a float4 splits into two 8-byte halves.
-__device__ __forceinline__ void put_packed(float* row, int k0, const f32x4& v) {
-  const int g = k0 & ~31, q = k0 & 31, j = q >> 3, e2 = (q >> 1) & 2;
-  *reinterpret_cast<f32x2*>(row + g + 4 * j + e2) = f32x2{v[0], v[2]};
-  *reinterpret_cast<f32x2*>(row + g + 16 + 4 * j + e2) = f32x2{v[1], v[3]};
-}
-
 // x staging: thread f of the workgroup moves 16 bytes (features 4u..4u+3, u = f & 15) of item row
 // xrow(f) of a chunk.  The 16 lanes of a row are contiguous (256-byte global segments); the two rows
 // of a half-wave are 4 apart, 4 x FXP = 16 floats mod 64 banks, so their packed 8-byte LDS writes
-// ([0, 16) + [32, 48) and [16, 32) + [48, 64) of a row's window) never share a bank.
+// ([0, 16) + [32, 48) and [16, 32) + [48, 64) of a row's window) never share a bank.  The compiler
+// emits each 8-byte pair as ds_write2_b32 {v0 -> p, v2 -> p + 1} and {v1 -> p + 16, v3 -> p + 17}
+// (put_packed: scalar stores, so no register pair has to be assembled): the same addresses, lanes
+// and banks as the 8-byte writes.
+// xrow(f + 64 FWV) = xrow(f) + FT: a thread's second float4 is the same row of the image's upper half.
 __device__ __forceinline__ int xrow(int f) { return ((f >> 7) << 3) + ((f >> 5) & 3) + 4 * ((f >> 4) & 1); }
+
+// Packed-order position of the 4 consecutive features k0..k0+3 (k0 % 4 == 0) of a 32-deep group:
+// feature 8j + 2s + h sits at 16h + 4j + s, so a float4 {v0, v1, v2, v3} goes to p, p + 16, p + 1, p + 17.
+__device__ __forceinline__ int packed_pos(int k0) {
+  const int g = k0 & ~31, q = k0 & 31, j = q >> 3, e2 = (q >> 1) & 2;
+  return g + 4 * j + e2;
+}
+__device__ __forceinline__ void put_packed(float* p, const f32x4& v) {
+  p[0] = v[0];
+  p[16] = v[1];
+  p[1] = v[2];
+  p[17] = v[3];
+}
+
+// Global operands of layer 1 come through buffer resources (scalar base + byte count, a loop-invariant
+// per-lane byte offset, and a scalar offset for whatever moves from chunk to chunk), so the chunk loops
+// carry no vector address arithmetic, and a lane whose byte offset is at or past the count reads zeros
+// without touching memory (the hardware's range check; it sees the per-lane offset, not the scalar one).
+using rsrc_t = __amdgpu_buffer_rsrc_t;
+__device__ __forceinline__ rsrc_t make_rsrc(const float* p, int bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p), 0, bytes, 0x00020000);
+}
+__device__ __forceinline__ f32x4 buf_ld4(rsrc_t rs, int voff, int soff) {
+  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, 0));
+}
+
+// The x rows a pass stages, as two resources: half[i] serves every thread's float4 i, i.e. image rows
+// [FT i, FT i + FT).  A thread's byte offset into either is the same for the whole kernel,
+// FusedCtx::xvo = (xrow(tid) D0 + 4 (tid & 15)) floats: row xrow(tid) of the half, and what differs
+// between the halves and between the two image layouts is in the (scalar) base.  The byte count is
+// that of the half's rows that exist AND belong to the pass -- rows past n, past the workgroup's
+// range or of no pass at all are beyond it and read as zeros, and no address outside x is formed by
+// a load that passes the check: with r = xrow(tid) < rows, base + xvo + chunk offset lies inside row
+// r of the half (the chunk offset stays inside a row by the chunk counts of the loops).  The base is
+// per pass: n x D0 x 4 bytes does not fit a resource's 32-bit count from 1.4 M rows of 768 on.
+struct XSrc {
+  rsrc_t half[2];
+};
 
 // Per-workgroup state that lives across passes (x staging registers, W1 prefetch, LDS buffer).
 template <int H1, int H2>
@@ -104,27 +145,47 @@ struct FusedCtx {
   float* z_out;
   float *xs, *h1s, *h2s, *w3s;
   int tid, w, r, h;
-  const float* w1row;
+  rsrc_t w1rs;            // the packed W1
+  int w1vo;               // this lane's byte offset into it: row 32 w + r, operand half h
   f32x4 awc[4];           // W1 fragments of the current 32-deep group
   f32x4 awc2[4];          // k-split pass: the same for the second MKL block's chain
   f32x4 w2f[4];           // L2: W2 fragments of the first four 16-deep blocks (the same every pass)
   f32x4 xr[C::XV];
-  bool xok[C::XV];
   f32x4 bxa[4];           // L1: item tile 0's x fragments of the NEXT 32-deep group (read_bxa)
-  int buf;
-  // x chunk staging: [PI items x 64 k] = PI*16 float4, 16 threads per item row.  Rows past n
-  // (or past this workgroup's range) load a clamped valid row and are zeroed only when written
-  // to LDS: a branch or select right after the load would make hipcc wait for it early.
-  // ks: the pass is a k-split single tile -- image rows [FT, 2 FT) hold the same items at k + kb
-  __device__ __forceinline__ void gload_x(int tb, int c, bool ks) {
+  int xvo;                // this thread's byte offset into an XSrc half
+  // The x image is double-buffered.  Both LDS addresses a thread needs are carried, not rebuilt from a
+  // parity: xrd = this lane's fragment row in the buffer being READ, xwr = this thread's packed
+  // position in the buffer being WRITTEN (the other one), xflip = +- the buffer size.  flip() after
+  // the chunk barrier costs one vector add each.
+  const float* xrd;
+  float* xwr;
+  int xflip;
+  __device__ __forceinline__ void flip() {
+    xrd += xflip;
+    xwr -= xflip;
+    xflip = -xflip;
+  }
+  // The x source of the pass that starts at tile tb (tb < 0: no pass, every row reads as zero).
+  // ks: the k-split layout -- ONE tile, image rows [FT, 2 FT) hold the same items at k + csplit FXC
+  // (a k-split pass or a leftover-tile piece; the tile may lie past t_end).  Otherwise up to FP tiles
+  // of this workgroup's range, image row = row of the pass.
+  __device__ __forceinline__ XSrc xsrc_of(int tb, bool ks) const {
+    const int64_t row0 = (int64_t)(tb < 0 ? 0 : tb) * FT;
+    const int tl = ks ? 1 : (t_end - tb < FP ? t_end - tb : FP);
+    int64_t left = n - row0;
+    if (left > tl * FT) left = tl * FT;
+    const int rows = (tb < 0 || left < 0) ? 0 : (int)left;
+    const float* p = x + row0 * D0;
+    const int lo = rows < FT ? rows : FT;
+    XSrc s;
+    s.half[0] = make_rsrc(p, lo * D0 * 4);
+    s.half[1] = ks ? make_rsrc(p + csplit * FXC, lo * D0 * 4) : make_rsrc(p + (int64_t)FT * D0, (rows - lo) * D0 * 4);
+    return s;
+  }
+  // chunk c of s into the staging registers (soff = the chunk's byte offset inside a row)
+  __device__ __forceinline__ void gload_x(const XSrc& s, int soff) {
 #pragma unroll
-    for (int i = 0; i < C::XV; ++i) {
-      const int f = tid + C::NTH * i, it = xrow(f), k4 = (f & 15) * 4;
-      const int64_t item = (int64_t)tb * FT + (ks ? it % FT : it);
-      xok[i] = item < n && (ks || (tb + it / FT) < t_end);
-      xr[i] = *reinterpret_cast<const f32x4*>(x + (item < n ? item : n - 1) * D0 +
-                                              (int64_t)c * FXC + k4 + (ks && it >= FT ? csplit * FXC : 0));
-    }
+    for (int i = 0; i < C::XV; ++i) xr[i] = buf_ld4(s.half[i], xvo, soff);
   }
   // Item tile 0's fragments are read one 32-deep group ahead of their MFMAs: group 1's during group
   // 0 (the same image), group 0's right behind the barrier that publishes their image -- the next
@@ -133,17 +194,15 @@ struct FusedCtx {
   // of its own group is waited for with nothing queued on the MFMA pipe, by both waves of a SIMD at
   // once, since they leave the barrier together.
   __device__ __forceinline__ void read_bxa(int g) {
-    const float* xb = xs + buf * C::PI * FXP + r * FXP + 16 * h + g * 32;
+    const float* xb = xrd + g * 32;
 #pragma unroll
     for (int j = 0; j < 4; ++j) bxa[j] = *reinterpret_cast<const f32x4*>(xb + 4 * j);
   }
-  __device__ __forceinline__ void swrite_x(int b) {
+  // the staging registers -> the buffer being written (cur: the one being read, before its barrier)
+  __device__ __forceinline__ void swrite_x(bool cur = false) {
+    float* p = cur ? xwr - xflip : xwr;
 #pragma unroll
-    for (int i = 0; i < C::XV; ++i) {
-      const int f = tid + C::NTH * i;
-      put_packed(xs + b * C::PI * FXP + xrow(f) * FXP, (f & 15) * 4,
-                 xok[i] ? xr[i] : f32x4{0.f, 0.f, 0.f, 0.f});
-    }
+    for (int i = 0; i < C::XV; ++i) put_packed(p + i * FT * FXP, xr[i]);
   }
 };
 
@@ -280,7 +339,7 @@ template <int NP, int H1, int H2, bool KS = false>
 __device__ __forceinline__ void rq_fused_pass(FusedCtx<H1, H2>& cx, int tb, int next_tb, bool next_ks) {
 #pragma clang fp contract(off)
   using C = FusedCfg<H1, H2>;
-  constexpr int P1 = C::P1, PI = C::PI;
+  constexpr int P1 = C::P1;
   static_assert(!KS || NP == 2, "k-split pass: two chains");
   constexpr int NR = KS ? 1 : NP;        // item tiles of the pass (L2, L3, z)
   const int w = cx.w, r = cx.r, h = cx.h;
@@ -300,37 +359,30 @@ __device__ __forceinline__ void rq_fused_pass(FusedCtx<H1, H2>& cx, int tb, int 
   // W1 is software-pipelined one 32-deep group ahead (the prefetch wraps to group 0 at the end of
   // the pass: W1 is the same for every pass, only the first pass pays the latency).  The x chunk
   // after the current one is loaded during group 0 and written to the other LDS buffer at the end
-  // of group 1 — unconditionally (clamped rows, zero-filled): after the last chunk of the last pass
-  // the staged image is simply never read.  Each group body is one basic block whose global loads,
+  // of group 1 — unconditionally: rows that do not exist or are not this pass's lie past the x
+  // resource's byte count and come back as zeros without a memory access (XSrc), and after the last
+  // chunk of the last pass the staged image is simply never read.  The loads take a scalar resource,
+  // one kernel-long per-lane offset and a scalar chunk offset, the LDS addresses are carried
+  // (FusedCtx::flip), the float4 goes to LDS as two ds_write2_b32 of unrelated registers: the steady
+  // loop holds 4 VALU instructions per 64 MFMAs (the two flips and two address adds for the image's
+  // upper half, which is past ds_write2_b32's offset range).  Each group body is one basic block whose global loads,
   // LDS reads and LDS writes are interleaved one-by-one with its MFMAs (sched_group_barrier): with
   // two waves per SIMD a burst of memory instructions would stall MFMA issue behind the load queue.
   constexpr int M1 = 16 * NP;            // MFMAs per 32-deep group
-  const float* xsrc[C::XV];              // x rows of this pass / of the next pass (clamped)
-  const float* xnxt[C::XV];
-  bool xok_cur[C::XV], xok_nxt[C::XV];   // rows past n / past this workgroup's range -> zeros
-#pragma unroll
-  for (int i = 0; i < C::XV; ++i) {
-    const int f = cx.tid + C::NTH * i, it = xrow(f), k4 = (f & 15) * 4;
-    const int64_t a = (int64_t)tb * FT + (KS ? it % FT : it);
-    const int64_t b = next_tb < 0 ? cx.n : (int64_t)next_tb * FT + (next_ks ? it % FT : it);
-    xsrc[i] = cx.x + (a < cx.n ? a : cx.n - 1) * cx.D0 + k4 + (KS && it >= FT ? kbo : 0);
-    xnxt[i] = cx.x + (b < cx.n ? b : cx.n - 1) * cx.D0 + k4 + (next_ks && it >= FT ? kbo : 0);
-    xok_cur[i] = a < cx.n;
-    xok_nxt[i] = b < cx.n && (next_ks || (next_tb + it / FT) < cx.t_end);
-    if (b >= cx.n) xnxt[i] = cx.x + (cx.n - 1) * cx.D0 + k4;
-  }
+  // x of this pass and of the next one's chunk 0 (whose image layout may differ): scalar state only
+  const XSrc xcur = cx.xsrc_of(tb, KS), xnxt = cx.xsrc_of(next_tb, next_ks);
   auto group = [&](auto gsel, int c) {
     constexpr int g = decltype(gsel)::value;
     const int gi = 2 * c + g;
     const int gn = (gi + 1 == 2 * NC) ? 0 : gi + 1;
     f32x4 awn[4], awn2[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) awn[j] = *reinterpret_cast<const f32x4*>(cx.w1row + gn * 32 + 4 * j);
+    for (int j = 0; j < 4; ++j) awn[j] = buf_ld4(cx.w1rs, cx.w1vo, gn * 128 + 16 * j);
     if constexpr (KS) {
 #pragma unroll
-      for (int j = 0; j < 4; ++j) awn2[j] = *reinterpret_cast<const f32x4*>(cx.w1row + kbo + gn * 32 + 4 * j);
+      for (int j = 0; j < 4; ++j) awn2[j] = buf_ld4(cx.w1rs, cx.w1vo, (kbo + gn * 32) * 4 + 16 * j);
     }
-    const float* xb = cx.xs + cx.buf * PI * FXP + r * FXP + 16 * h + g * 32;
+    const float* xb = cx.xrd + g * 32;
     f32x4 bx[NP][4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) bx[0][j] = cx.bxa[j];   // read a group ahead (FusedCtx::read_bxa)
@@ -341,10 +393,11 @@ __device__ __forceinline__ void rq_fused_pass(FusedCtx<H1, H2>& cx, int tb, int 
     if constexpr (g == 0) {
       cx.read_bxa(1);                  // group 1's item tile 0: the same image, behind tile 1's reads
       asm volatile("" ::: "memory");   // x loads stay behind the W1 loads and LDS reads
+      // the chunk after this one, or the next pass's chunk 0: a scalar choice of resource and offset
       const bool same = c + 1 < NC;
+      const int so = same ? (c + 1) * FXC * 4 : 0;
 #pragma unroll
-      for (int i = 0; i < C::XV; ++i)
-        cx.xr[i] = *reinterpret_cast<const f32x4*>(same ? xsrc[i] + (c + 1) * FXC : xnxt[i]);
+      for (int i = 0; i < C::XV; ++i) cx.xr[i] = buf_ld4(same ? xcur.half[i] : xnxt.half[i], cx.xvo, so);
     }
 #pragma unroll
     for (int it = 0; it < NP; ++it)
@@ -353,16 +406,7 @@ __device__ __forceinline__ void rq_fused_pass(FusedCtx<H1, H2>& cx, int tb, int 
 #pragma unroll
         for (int s = 0; s < 4; ++s)
           acc1[it] = mfma32(KS && it == 1 ? cx.awc2[j][s] : cx.awc[j][s], bx[it][j][s], acc1[it]);
-    if constexpr (g == 1) {
-      const bool same = c + 1 < NC;
-#pragma unroll
-      for (int i = 0; i < C::XV; ++i) {
-        const int f = cx.tid + C::NTH * i;
-        const bool ok = same ? xok_cur[i] : xok_nxt[i];
-        put_packed(cx.xs + (cx.buf ^ 1) * PI * FXP + xrow(f) * FXP, (f & 15) * 4,
-                   ok ? cx.xr[i] : f32x4{0.f, 0.f, 0.f, 0.f});
-      }
-    }
+    if constexpr (g == 1) cx.swrite_x();
     // schedule: the W1 loads, item tile 1's LDS fragments and (group 0) item tile 0's of group 1
     // one per MFMA, then (group 0) the x loads, (group 1) the x image writes (two per float4) at the
     // end; group 1's last NDW MFMAs are placed by chunk(), behind the barrier and the reads after it
@@ -404,7 +448,7 @@ __device__ __forceinline__ void rq_fused_pass(FusedCtx<H1, H2>& cx, int tb, int 
     group(std::integral_constant<int, 0>{}, c);
     group(std::integral_constant<int, 1>{}, c);
     __syncthreads();
-    cx.buf ^= 1;
+    cx.flip();
     // the next group 0's item tile 0 fragments, from the image the barrier has just published, with
     // this chunk's last MFMAs (operands in registers) behind them
     cx.read_bxa(0);
@@ -422,7 +466,7 @@ __device__ __forceinline__ void rq_fused_pass(FusedCtx<H1, H2>& cx, int tb, int 
   if constexpr (KS) {
     // the second block's first W1 group (the previous pass's prefetch wrapped the first stream only)
 #pragma unroll
-    for (int j = 0; j < 4; ++j) cx.awc2[j] = *reinterpret_cast<const f32x4*>(cx.w1row + kbo + 4 * j);
+    for (int j = 0; j < 4; ++j) cx.awc2[j] = buf_ld4(cx.w1rs, cx.w1vo, kbo * 4 + 16 * j);
 #pragma unroll 1
     for (; c < NC; ++c) chunk(c);
     // block 0 = chain 0, block 1 = chain 1: y = (b1 + block 0) + block 1
@@ -490,26 +534,19 @@ template <int H1, int H2, int PF = 128>
 __device__ __forceinline__ void rq_piece_pass(FusedCtx<H1, H2>& cx, int tb, int fh, float* __restrict__ h1g,
                                               const float* __restrict__ W1) {
 #pragma clang fp contract(off)
-  using C = FusedCfg<H1, H2>;
-  constexpr int PI = C::PI;
   constexpr int NG = PF / 32;          // feature groups of the piece
   const int w = cx.w, r = cx.r, h = cx.h, fg = w % NG, blk = (w / NG) & 1;
   const bool act = w < 2 * NG;         // wave-uniform
   const int NC = cx.NC / 2, kbo = cx.csplit * FXC;
   const int f0 = PF * fh + 32 * fg;    // this wave's first feature
-  const float* w1row = W1 + (int64_t)(f0 + r) * cx.D0 + 16 * h + blk * kbo;
+  // this wave's W1 rows (of its k block) through the kernel's W1 resource; the waves that only stage
+  // x carry an offset past its end (zeros, no memory access)
+  const int w1vo = act ? ((f0 + r) * cx.D0 + 16 * h + blk * kbo) * 4 : 0x7ffffff0;
   f32x4 awc[4];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) awc[j] = act ? *reinterpret_cast<const f32x4*>(w1row + 4 * j) : f32x4{0.f, 0.f, 0.f, 0.f};
-  const float* xsrc[C::XV];
-  bool xok[C::XV];
-#pragma unroll
-  for (int i = 0; i < C::XV; ++i) {
-    const int f = cx.tid + C::NTH * i, it = xrow(f), k4 = (f & 15) * 4;
-    const int64_t a = (int64_t)tb * FT + it % FT;
-    xsrc[i] = cx.x + (a < cx.n ? a : cx.n - 1) * cx.D0 + k4 + (it >= FT ? kbo : 0);
-    xok[i] = a < cx.n;
-  }
+  for (int j = 0; j < 4; ++j) awc[j] = buf_ld4(cx.w1rs, w1vo, 16 * j);
+  const XSrc xcur = cx.xsrc_of(tb, true);
+  const int xbo = blk * FT * FXP;   // image rows of this wave's k block
   f32x16 acc;
 #pragma unroll
   for (int v = 0; v < 16; ++v) acc[v] = 0.f;
@@ -522,35 +559,24 @@ __device__ __forceinline__ void rq_piece_pass(FusedCtx<H1, H2>& cx, int tb, int 
       const int gn = gi + 1 < 2 * NC ? gi + 1 : gi;
       f32x4 awn[4];
 #pragma unroll
-      for (int j = 0; j < 4; ++j)
-        awn[j] = act ? *reinterpret_cast<const f32x4*>(w1row + gn * 32 + 4 * j) : f32x4{0.f, 0.f, 0.f, 0.f};
-      const float* xb = cx.xs + cx.buf * PI * FXP + (blk * FT + r) * FXP + 16 * h + g * 32;
+      for (int j = 0; j < 4; ++j) awn[j] = buf_ld4(cx.w1rs, w1vo, gn * 128 + 16 * j);
+      const float* xb = cx.xrd + xbo + g * 32;
       f32x4 bx[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) bx[j] = *reinterpret_cast<const f32x4*>(xb + 4 * j);
-      if (g == 0 && more) {
-#pragma unroll
-        for (int i = 0; i < C::XV; ++i) cx.xr[i] = *reinterpret_cast<const f32x4*>(xsrc[i] + (c + 1) * FXC);
-      }
+      if (g == 0 && more) cx.gload_x(xcur, (c + 1) * FXC * 4);
       if (act) {
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
           for (int s = 0; s < 4; ++s) acc = mfma32(awc[j][s], bx[j][s], acc);
       }
-      if (g == 1 && more) {
-#pragma unroll
-        for (int i = 0; i < C::XV; ++i) {
-          const int f = cx.tid + C::NTH * i;
-          put_packed(cx.xs + (cx.buf ^ 1) * PI * FXP + xrow(f) * FXP, (f & 15) * 4,
-                     xok[i] ? cx.xr[i] : f32x4{0.f, 0.f, 0.f, 0.f});
-        }
-      }
+      if (g == 1 && more) cx.swrite_x();
 #pragma unroll
       for (int j = 0; j < 4; ++j) awc[j] = awn[j];
     }
     __syncthreads();
-    cx.buf ^= 1;
+    cx.flip();
   }
   // block 1's sums -> LDS (the h1 image is free here), then y = (b1 + block 0) + block 1, ReLU
   float* hand = cx.h1s + (fg * 64 + (cx.tid & 63)) * 16;
@@ -613,20 +639,24 @@ __global__ __launch_bounds__(64 * FWV, 1) void rq_encoder_kernel(
   }
   const int tid = threadIdx.x, lane = tid & 63;
   cx.tid = tid; cx.w = tid >> 6; cx.r = lane & 31; cx.h = lane >> 5;
-  cx.w1row = W1 + (int64_t)(cx.w * 32 + cx.r) * D0 + 16 * cx.h;
+  cx.w1rs = make_rsrc(W1, H1 * D0 * 4);
+  cx.w1vo = ((cx.w * 32 + cx.r) * D0 + 16 * cx.h) * 4;
 #pragma unroll
-  for (int j = 0; j < 4; ++j) cx.awc[j] = *reinterpret_cast<const f32x4*>(cx.w1row + 4 * j);
+  for (int j = 0; j < 4; ++j) cx.awc[j] = buf_ld4(cx.w1rs, cx.w1vo, 16 * j);
+  cx.xvo = (xrow(tid) * D0 + 4 * (tid & 15)) * 4;
+  cx.xrd = cx.xs + cx.r * FXP + 16 * cx.h;
+  cx.xwr = cx.xs + C::PI * FXP + xrow(tid) * FXP + packed_pos(4 * (tid & 15));
+  cx.xflip = C::PI * FXP;
 #pragma unroll
   for (int u = 0; u < 4; ++u)
     cx.w2f[u] = *reinterpret_cast<const f32x4*>(W2 + (int64_t)(cx.w * 16 + (lane & 15)) * H1 + 4 * (lane >> 4) + 16 * u);
-  cx.buf = 0;
   // an odd last tile runs as a k-split pass when MKL's block edge halves the chunks (in = 768)
   const bool kso = 2 * csplit == cx.NC;
   const bool ks = kso && ((t_end - t_begin) & 1);
   const int ptile = piece0 >= 0 ? q * G + piece0 / pq : -1;
   // the first chunk of the first tile (k-split layout for a single k-split tile or a piece)
-  cx.gload_x(pieces_only ? ptile : t_begin, 0, pieces_only || (ks && t_end - t_begin == 1));
-  cx.swrite_x(0);
+  cx.gload_x(cx.xsrc_of(pieces_only ? ptile : t_begin, pieces_only || (ks && t_end - t_begin == 1)), 0);
+  cx.swrite_x(true);
   __syncthreads();
   cx.read_bxa(0);   // the first pass's first group (unused when the workgroup runs pieces only)
   int tb = t_begin;
@@ -641,8 +671,8 @@ __global__ __launch_bounds__(64 * FWV, 1) void rq_encoder_kernel(
   for (int pc = piece0; pc >= 0 && pc < npieces; pc += G) {
     const int t = q * G + pc / pq;
     if (pc != piece0) {   // a second piece: stage its first chunk (k-split layout)
-      cx.gload_x(t, 0, true);
-      cx.swrite_x(cx.buf);
+      cx.gload_x(cx.xsrc_of(t, true), 0);
+      cx.swrite_x(true);
       __syncthreads();
     }
     float* dst = h1g + (int64_t)(pc / pq) * FT * H1;
@@ -751,6 +781,7 @@ int gr_rq_encoder_fused_launch(const float* x, int64_t n, int32_t n_linear, cons
   using namespace gr;
   if (n_linear != 3 || dims[3] != 32 || dims[0] % FXC != 0 || !biases) return GR_ERR_UNSUPPORTED;
   if (!(dims[1] == 256 && dims[2] == 128)) return GR_ERR_UNSUPPORTED;
+  if (dims[0] > (1 << 20)) return GR_ERR_UNSUPPORTED;   // W1 and an x pass are addressed with 32-bit byte offsets
   // MKL's order of this call (n rows): a k-block chain per layer, at most two blocks in layer 1
   const MklPlan p1 = mkl_plan(n, dims[0], 256);
   if (p1.kind != MKL_CHAIN || mkl_plan(n, 256, 128).kind != MKL_CHAIN || mkl_plan(n, 128, 32).kind != MKL_CHAIN)
