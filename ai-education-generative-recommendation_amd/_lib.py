@@ -128,6 +128,10 @@ SIGNATURES = {
     "gr_code_groups_workspace_bytes": (_sz, [_i64, _i32]),
     "gr_code_groups_i64": (ctypes.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "gr_code_segments_i64": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gr_kmeans_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "gr_kmeans_form": (_i32, [_i64, _i32, _i32]),
+    "gr_kmeans_f32": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, ctypes.c_uint64, _i32, _i32, ctypes.c_double,
+                                     _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -44,10 +44,14 @@ static std::atomic<int64_t> g_attn_k16{1};
 // passes and the exact formula on the near-minimum codes only, 0 = every distance exact)
 static std::atomic<int64_t> g_rq_filter{1};
 
+// kmeans_small (1: gr_kmeans_f32 in one launch of one workgroup when the rows fit in LDS, 0: always
+// one launch per phase over row tiles; the same phase code either way)
+static std::atomic<int64_t> g_kmeans_small{1};
+
 static const Opt kOpts[] = {
     {"rq_fused", &g_rq_fused, 0, 1},   {"sas_fused", &g_sas_fused, 0, 3}, {"sas_rowtile", &g_sas_rowtile, 0, 1},
     {"lin_wres", &g_lin_wres, 0, 1},   {"emb_proj", &g_emb_proj, 0, 1},   {"topk_half", &g_topk_half, 0, 2},
-    {"attn_k16", &g_attn_k16, 0, 1},   {"rq_filter", &g_rq_filter, 0, 1},
+    {"attn_k16", &g_attn_k16, 0, 1},   {"rq_filter", &g_rq_filter, 0, 1}, {"kmeans_small", &g_kmeans_small, 0, 1},
 };
 
 static const Opt* find_opt(const char* name) {

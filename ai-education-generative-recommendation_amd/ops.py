@@ -3,6 +3,7 @@
 Each function takes/returns torch tensors on a ROCm device, enqueues on the current stream and
 never synchronises.  Argument checking mirrors the ATen errors the reference would raise.
 """
+import collections
 import ctypes
 import itertools
 import os
@@ -717,6 +718,57 @@ def code_groups(codes, listing=True):
                                              L.ptr(meta[4:]), L.ptr(digit), L.ptr(wsp), nbytes,
                                              L.stream_of(dev)), "gr_code_segments_i64")
     return CodeGroups(n, leader, count, digit, rows_buf, meta)
+
+
+KMeansResult = collections.namedtuple("KMeansResult", "centers labels inertia n_iter")
+KMEANS_ENVELOPE = "1 <= e <= 64 features, 1 <= n_clusters <= 1024, n_clusters <= n < 2**31 rows"
+
+
+def kmeans(x, n_clusters, max_iter=10, tol=1e-4, seed=None, init=None, trials=None, with_labels=True):
+    """scikit-learn's ``KMeans(n_clusters, max_iter=max_iter, tol=tol).fit(x)`` as the reference calls
+    it (RQ-VAE/models/layers.py:69-82: greedy k-means++ seeding, one initialisation, Lloyd with
+    empty-cluster relocation and both stop rules) in one C-ABI call, ``gr_kmeans_f32``: a
+    ``KMeansResult`` of ``centers`` [K, e] fp32, ``labels`` [n] int64 and ``inertia`` (fp64 scalar)
+    against those centres, and ``n_iter`` (int32 scalar), all on the device; nothing synchronises.
+
+    ``seed``: the k-means++ draws are a function of it and of ``x`` only, and the sums are taken in a
+    fixed order, so the same seed gives the same bits.  ``None`` draws one from torch's default
+    generator (``torch.manual_seed`` makes the run repeatable).  ``init`` [K, e] skips the seeding;
+    with ``max_iter=0`` the call returns the labels and inertia of ``init``.  ``trials``: candidates
+    per seeding round (default scikit-learn's ``2 + floor(ln K)``; 1 is plain D^2 sampling).
+    ``with_labels=False`` leaves ``labels`` None (no [n] int64 buffer; the codebook init needs none)."""
+    L.require_gpu(x)
+    if x.dim() != 2:
+        raise RuntimeError(f"kmeans takes [n, e] rows, got {tuple(x.shape)}")
+    x = L.as_f32(x.detach())
+    n, e = x.shape
+    K = int(n_clusters)
+    if n < K:
+        raise ValueError(f"n_samples={n} should be >= n_clusters={K}.")
+    lib = L.lib()
+    nbytes = lib.gr_kmeans_workspace_bytes(n, e, K)
+    if nbytes == 0:
+        raise RuntimeError(f"kmeans: x {tuple(x.shape)} with n_clusters={K} is outside the kernels' envelope "
+                           f"({KMEANS_ENVELOPE}); there is no CPU fallback")
+    dev = x.device
+    if init is not None:
+        L.require_gpu(init)
+        init = L.as_f32(init.detach())
+        if tuple(init.shape) != (K, e):
+            raise RuntimeError(f"kmeans: init must be [{K}, {e}], got {tuple(init.shape)}")
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    centers = torch.empty((K, e), dtype=torch.float32, device=dev)
+    labels = torch.empty(n, dtype=torch.int64, device=dev) if with_labels else None
+    inertia = torch.empty((), dtype=torch.float64, device=dev)
+    n_iter = torch.empty((), dtype=torch.int32, device=dev)
+    wsp = L.workspace(nbytes, dev)
+    with L.on(dev):
+        L.check(lib.gr_kmeans_f32(L.ptr(x), n, e, K, L.ptr(init), int(seed) & (2 ** 64 - 1),
+                                  0 if trials is None else int(trials), int(max_iter), float(tol), L.ptr(centers),
+                                  L.ptr(labels), L.ptr(inertia), L.ptr(n_iter), L.ptr(wsp), nbytes,
+                                  L.stream_of(dev)), "gr_kmeans_f32")
+    return KMeansResult(centers, labels, inertia, n_iter)
 
 
 class SasrecBinding:

@@ -198,9 +198,24 @@ class VectorQuantizer(nn.Module):
         z_q = self.embedding(indices)
         return z_q.view(shape) if shape is not None else z_q
 
+    # "host": scikit-learn on the host, the reference's own call (the default); "device": ops.kmeans
+    # on the kernels, seeded by kmeans_seed (None: torch's default generator).  RQVAE.set_kmeans sets both.
+    kmeans_backend = "host"
+    kmeans_seed = None
+
     def init_emb(self, data):
-        """vq.py:39-47 + layers.py:69-82: codebook <- scikit-learn KMeans(n_e, max_iter) centres of the
-        first training batch's latents (host, once; the reference's own call)."""
+        """vq.py:39-47 + layers.py:69-82: codebook <- KMeans(n_e, max_iter) centres of the first
+        training batch's latents.  ``kmeans_backend`` "host": scikit-learn (host, once; the
+        reference's own call); "device": ``ops.kmeans``, the centres copied into the codebook on
+        the device without a synchronisation."""
+        if self.kmeans_backend == "device":
+            res = ops.kmeans(data.detach(), self.n_e, max_iter=self.kmeans_iters, seed=self.kmeans_seed,
+                             with_labels=False)
+            self.embedding.weight.data.copy_(res.centers)
+            self.initted = True
+            return
+        if self.kmeans_backend != "host":
+            raise ValueError(f"kmeans_backend must be 'host' or 'device', got {self.kmeans_backend!r}")
         from sklearn.cluster import KMeans
         centers = KMeans(n_clusters=self.n_e, max_iter=self.kmeans_iters).fit(
             data.detach().cpu().numpy()).cluster_centers_
@@ -384,6 +399,18 @@ class RQVAE(nn.Module):
         weights on every call -- for callers that write weights through ``.data`` without calling
         ops.weights_changed()."""
         self.__dict__["_gr_frozen"] = bool(frozen)
+        return self
+
+    def set_kmeans(self, backend="device", seed=None):
+        """Where every level's k-means init (``kmeans_init=True``) runs: "host" (default: scikit-learn,
+        the reference's call) or "device" (``ops.kmeans`` on the kernels: no host round trip in the
+        first forward).  With ``seed``, level l is seeded ``seed + l``, so the same seed gives the
+        same codebooks; without, each level draws its seed from torch's default generator."""
+        if backend not in ("host", "device"):
+            raise ValueError(f"kmeans backend must be 'host' or 'device', got {backend!r}")
+        for l, q in enumerate(self.rq.vq_layers):
+            q.kmeans_backend = backend
+            q.kmeans_seed = None if seed is None else int(seed) + l
         return self
 
     def call_plans(self, n):

@@ -80,6 +80,10 @@ const char* gr_last_error(void);
  *                   level run the filtered kernel: a split-bf16 pass bounds every distance, and the
  *                   exact fp32 formula runs only on the codes within the bound of the minimum;
  *                   0: every distance exact.  The IDs are bitwise the same, exact ties included.
+ *   "kmeans_small"  1 (default): gr_kmeans_f32 runs the whole k-means in one launch of one
+ *                   workgroup when n <= 256, n K e <= 2^20 (e padded) and the rows and
+ *                   the workspace fit in LDS; 0: always one launch per phase over row tiles.  Both forms
+ *                   run the same phase code in the same order: bitwise the same results.
  * A last-position forward (predict, last_hidden) runs its final block as the one-query tail on
  * LN_a(X): q . K_j = (W_k^T q) . H_j (+ a term constant over j that cancels in the softmax) and
  * p . V = W_v (p . H) + b_v, so K|V of the B n rows are never projected (sas_tail_h2_kernel; the
@@ -559,6 +563,43 @@ int gr_code_groups_i64(const int64_t* codes, int64_t n, int32_t levels, int64_t*
 int gr_code_segments_i64(const int64_t* sorted_keys, int64_t n, const int64_t* stats, const int64_t* count,
                          int64_t* rows, int64_t* sizes, int64_t* digit, void* workspace,
                          size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------ */
+/* Codebook k-means init (RQ-VAE/models/layers.py:69-82 kmeans(): scikit-learn's
+ * KMeans(n_clusters = K, max_iter).fit(x).cluster_centers_, the call behind vq.py:39-47 init_emb)
+ * for fp32 rows x[n, e], 1 <= e <= 64, 1 <= K <= 1024, K <= n < 2^31 (GR_ERR_UNSUPPORTED outside;
+ * n < K is GR_ERR_ARG, scikit-learn's ValueError).  The whole run -- greedy k-means++ seeding, up to
+ * max_iter Lloyd iterations, the final labels -- is enqueued by this one call; both stop rules are
+ * evaluated on the device, and iterations enqueued past convergence do nothing.
+ *   seeding   the first centre is a uniform row; each later one is the best (lowest resulting
+ *             potential) of `trials` rows drawn with probability proportional to D^2, the squared
+ *             distance to the nearest chosen centre (trials = 0: scikit-learn's 2 + floor(ln K);
+ *             1: plain D^2 sampling; at most 16).  The draws are a counter-based hash of
+ *             (seed, round, trial): a function of the seed and the data only.  Every centre is a row
+ *             of x, and a row with D^2 = 0 is never drawn while one with D^2 > 0 exists.
+ *             init_centers[K, e] (optional) replaces the seeding.
+ *   E step    label = first index of the minimum of sum_f (x_f - c_f)^2 (direct form, fp32).
+ *   M step    centre = mean of its members, summed in fp64 in a fixed order (no float atomics):
+ *             the same inputs give the same bits on every run.
+ *   empties   scikit-learn's relocation: the empty clusters in ascending id, the j-th taking the
+ *             j-th farthest row (distance to its assigned old centre descending, ties to the lower
+ *             row), which leaves its donor's sum and count; labels stay; a cluster whose count ends
+ *             at 0 keeps its old centre.
+ *   stop      when an E step repeats the previous labels, or when the summed squared centre shift
+ *             is <= tol * mean over features of var(x).
+ * Outputs (device): centers_out[K, e]; labels_out[n] (optional) and *inertia_out (optional, fp64)
+ * of the rows against the returned centres; *n_iter_out (optional) = Lloyd iterations run.
+ * max_iter = 0 with init_centers returns the labels and inertia of the given centres.
+ * workspace: gr_kmeans_workspace_bytes(n, e, K) bytes, 16-byte aligned (0 for a shape outside the
+ * envelope).  Option "kmeans_small" (gr_set_option) chooses the launch form; gr_kmeans_form
+ * returns the form a call of this shape takes under the option in force: 1 = one workgroup,
+ * 0 = tiled, -1 = outside the envelope. */
+size_t gr_kmeans_workspace_bytes(int64_t n, int32_t e, int32_t K);
+int32_t gr_kmeans_form(int64_t n, int32_t e, int32_t K);
+int gr_kmeans_f32(const float* x, int64_t n, int32_t e, int32_t K, const float* init_centers,
+                  uint64_t seed, int32_t trials, int32_t max_iter, double tol, float* centers_out,
+                  int64_t* labels_out, double* inertia_out, int32_t* n_iter_out, void* workspace,
+                  size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
