@@ -10,6 +10,17 @@ static thread_local std::string g_last_error;
 void set_error(const std::string& msg) { g_last_error = msg; }
 void clear_error() { g_last_error.clear(); }
 
+int cu_count() {
+  static int cus = 0;
+  if (!cus) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
+      cus = 256;
+  }
+  return cus;
+}
+
 // Path switches (gr_set_option), read by the launchers at each call.  Each selects between two
 // kernel paths that give BITWISE the same results (the tests run both), except attn_k16: two fp32
 // chains of the hd 128 attention, both tested against the oracle within the logits tolerance.

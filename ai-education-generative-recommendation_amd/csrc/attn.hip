@@ -149,7 +149,7 @@ __global__ __launch_bounds__(256, 2) void attn_mfma_kernel(const float* __restri
         if (!LAZY || kt == myq[U0 + u] || kt * 32 + 32 > n) {
 #pragma unroll
           for (int v = 0; v < 16; ++v) {
-            const int key = kt * 32 + (v & 3) + 8 * (v >> 2) + 4 * h;
+            const int key = kt * 32 + mfma32_row(v, h);
             if (key > qi || key >= n) S[u][v] = -INFINITY;
             tmax = fmaxf(tmax, S[u][v]);
           }
@@ -346,7 +346,7 @@ __global__ __launch_bounds__(64) void attn_persist_kernel(const float* __restric
       if (kt == qt || kt * 32 + 32 > n) {
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
-          const int key = kt * 32 + (v & 3) + 8 * (v >> 2) + 4 * h;
+          const int key = kt * 32 + mfma32_row(v, h);
           if (key > qi || key >= n) S[v] = -INFINITY;
           tmax = fmaxf(tmax, S[v]);
         }

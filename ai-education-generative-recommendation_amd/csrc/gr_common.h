@@ -19,6 +19,10 @@ void clear_error();
 // Tuning / path options (gr_set_option); read by the launchers at each call.
 int64_t option(const char* name);
 
+// Compute units of the current device (queried once; 256 when the query fails): the launch plans
+// size their grids by it.
+int cu_count();
+
 inline int fail(int code, const std::string& msg) {
   set_error(msg);
   return code;
@@ -57,6 +61,8 @@ __device__ __forceinline__ void set_err(int32_t* err, int32_t code) {
 __device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
 }
+// Row of D register v in lane half hh = l >> 5.
+__device__ __forceinline__ int mfma32_row(int v, int hh) { return (v & 3) + 8 * (v >> 2) + 4 * hh; }
 
 // sum(x**2, dim=1) of a row in ATen's CPU order (the |r|^2 / |c|^2 terms of RQ-VAE/models/vq.py:71-72;
 // oracle/rq_exact.c rqx_rowsq): s = x*x rounded; lane j of 8-float vector v accumulates into
@@ -219,12 +225,55 @@ __device__ __forceinline__ float mkl_dot(MklPlan p, XA xa, WA wa, int K, float b
 // k-block width of a long call (>= 256 rows) for inner size K: mkl_plan's MKL_CHAIN width.
 __host__ __device__ inline int mkl_kblock(int K) { return mkl_plan(1 << 20, K, 256).kb; }
 
-// The scoring chain's feature order (score.hip, rank_fused.hip, score_topk.hip): a d-vector is read
-// as d / 8 float4 groups per lane, lane half hh of group gq holding features 8 gq + 4 hh .. +3, and
-// step (gq, s) of the v_mfma_f32_32x32x2_f32 chain adds feature 8 gq + s (lane half 0) then
-// 8 gq + 4 + s (lane half 1).  For d >= 32 this is the "32 g + 8 q + 4 hh" order of rounds 1-4
-// (gq = 4 g + q); d = 16 is the same chain over two groups.
-__device__ __forceinline__ int sc_feat(int gq, int hh) { return 8 * gq + 4 * hh; }
+// splitmix64 finaliser: the one hash under the negative sampler's stream, the k-means seeding draws
+// and every dropout mask (tests/test_neg_sample.py test_mix64_pinned).
+__device__ __forceinline__ uint64_t mix64(uint64_t z) {
+  z += 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+// 24-bit uniform in [0, 1) from the top bits of a hash word.
+__device__ __forceinline__ float u01_24(uint64_t z) { return (float)(z >> 40) * (1.0f / 16777216.0f); }
+
+// SASRec training dropout (sasrec_train.hip, sasrec_train_tiled.hip: both kernel sets draw the same
+// masks).  An element is kept when a counter-based hash of (seed, sequence, site, element) is >= p
+// and scaled by 1 / (1 - p); the seed is seed0 ^ *seed_dev so a captured step replays with fresh masks.
+struct SasDrop {
+  float p_drop, keep_scale;
+  uint64_t seed0;
+  const uint64_t* seed_dev;
+};
+
+// DR: a SasDrop, or a kernel-argument struct that carries SasDrop's four fields under the same names
+// (sasrec_train.hip's Args, whose layout is part of its kernels' register allocation).
+template <typename DR>
+__device__ __forceinline__ uint64_t sas_seed_of(const DR& dr) {
+  return dr.seed_dev ? dr.seed0 ^ *dr.seed_dev : dr.seed0;
+}
+
+// keep factor of element idx at dropout site `site` of sequence b: 0 or 1 / (1 - p)
+template <typename DR>
+__device__ __forceinline__ float sas_keep(const DR& dr, uint64_t seed, int64_t b, int site, uint32_t idx) {
+  if (dr.p_drop <= 0.f) return 1.f;
+  const uint64_t key = ((uint64_t)site << 32) | idx;
+  const uint64_t z = mix64(seed ^ mix64((uint64_t)b ^ mix64(key)));
+  return u01_24(z) >= dr.p_drop ? dr.keep_scale : 0.f;
+}
+
+// Wave-wide sum / max through __shfl_xor, offsets 32 .. 1 (the order fixes the sum's rounding).
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
 
 // Butterfly steps on the VALU: xsum<O>(v) = v + (v of lane ^ O), xmax<O>(v) = fmaxf(v, that), each
 // bitwise the "v op __shfl_xor(v, O)" it replaces (both ops commute) without the ds_bpermute round

@@ -106,16 +106,9 @@ inline KmShape km_shape(int64_t n, int e, int K) {
   return s;
 }
 
-__device__ __forceinline__ uint64_t km_mix64(uint64_t z) {   // splitmix64 finaliser (neg_sample.hip)
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-// Uniform in [0, 1): a function of (seed, round, trial) only.
+// Uniform in [0, 1): a function of (seed, round, trial) only (gr_common.h mix64).
 __device__ __forceinline__ double km_u01(uint64_t seed, int round, int trial) {
-  const uint64_t h = km_mix64(km_mix64(seed ^ km_mix64((uint64_t)round)) + (uint64_t)trial);
+  const uint64_t h = mix64(mix64(seed ^ mix64((uint64_t)round)) + (uint64_t)trial);
   return (double)(h >> 11) * 0x1.0p-53;
 }
 

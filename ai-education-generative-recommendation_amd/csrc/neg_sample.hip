@@ -13,13 +13,6 @@
 
 namespace gr {
 
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {   // splitmix64 finaliser
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
 constexpr int NS_MAX_ROUNDS = 4096;
 constexpr int NS_MAX_NEG = 1024;
 

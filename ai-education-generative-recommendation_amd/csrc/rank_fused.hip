@@ -6,7 +6,7 @@
 //   rank[u]  = count_gt(thr = pairs) + 1
 //
 // Both kernels evaluate every logit with EXACTLY the instruction sequence of the scoring kernel
-// (score.hip): the same v_mfma_f32_32x32x2_f32 operand layout and k order (gr_common.h sc_feat), so
+// (score.hip): the same v_mfma_f32_32x32x2_f32 operand layout and k order (score_chain.h), so
 // t[u] is bitwise the logit the full scoring would have produced and the target never counts
 // itself (SURVEY §7 hard part 3).  d = 16, 32, 64 or 128.
 //
@@ -15,7 +15,7 @@
 // one contiguous catalog slice walked in 64-item chunks (table chunk staged in LDS, prefetched into
 // registers one chunk ahead); per-lane counters, reduced over the 32 item lanes at the end, one
 // atomic add per (user, slice).
-#include "gr_common.h"
+#include "score_chain.h"
 
 namespace gr {
 
@@ -28,32 +28,11 @@ __global__ __launch_bounds__(64) void score_pairs_kernel(const float* __restrict
                                                          int64_t rows, const int64_t* __restrict__ ids,
                                                          int mask_col0, float* __restrict__ out,
                                                          int32_t* err) {
-  constexpr int NQ = D / 8;
   const int lane = threadIdx.x, r = lane & 31, hh = lane >> 5;
   const int64_t u0 = (int64_t)blockIdx.x * 32;
   const int64_t u = u0 + r;
-  const int64_t uc = u < B ? u : B - 1;
-  int64_t t = ids[uc];
-  if (t < 0 || t >= rows) {
-    if (u < B) set_err(err, 1);
-    t = 0;
-  }
-  f32x16 acc;
-#pragma unroll
-  for (int v = 0; v < 16; ++v) acc[v] = 0.f;
-  // A: user r of the tile; B: the target row of user r (column r of the tile)
-#pragma unroll
-  for (int gq = 0; gq < NQ; ++gq) {
-    const f32x4 a = *reinterpret_cast<const f32x4*>(h + uc * D + sc_feat(gq, hh));
-    const f32x4 b = *reinterpret_cast<const f32x4*>(table + t * D + sc_feat(gq, hh));
-#pragma unroll
-    for (int s = 0; s < 4; ++s) acc = mfma32(a[s], b[s], acc);
-  }
-  // diagonal: row (v&3) + 8(v>>2) + 4hh == column r
-  float d = 0.f;
-#pragma unroll
-  for (int v = 0; v < 16; ++v)
-    if ((v & 3) + 8 * (v >> 2) + 4 * hh == r) d = acc[v];
+  const int64_t t = sc_pair_target(ids, u, B, rows, err);
+  const float d = sc_pair_logit<D>(h, u, B, table, t, r, hh);
   if (u < B && ((r >> 2) & 1) == hh) out[u] = (mask_col0 && t == 0) ? RK_MASK : d;
 }
 
@@ -65,6 +44,12 @@ constexpr int RK_UT = 1;
 // score_pairs_kernel's MFMA tile (the same operands in the same order: bitwise its values) instead of
 // read from thr -- one launch less per rank call (gr_sasrec_rank_f32).  Every slice of a user block
 // recomputes its users' pairs (one short MFMA chain per 32 users).
+//
+// The pairs tile is score_chain.h's.  The fragment load, chunk staging and chunk chain below are
+// score_chain.h's sc_load_user / ScStage / sc_chunk_chain<D, 2, false> written out in place: calling
+// the helpers changed this kernel's register allocation and measured outside the parent build's
+// spread at d = 16 (profiles/r14/ab_chain_all_shared.txt), so the kernel keeps its own text and
+// machine code; the torch.equal tests pin it to the definition.
 template <int D, bool PAIRS = false>
 __global__ __launch_bounds__(256, 2) void score_count_kernel(const float* __restrict__ h, int64_t B,
                                                             const float* __restrict__ table,
@@ -76,9 +61,9 @@ __global__ __launch_bounds__(256, 2) void score_count_kernel(const float* __rest
                                                             const int64_t* __restrict__ ids = nullptr,
                                                             int32_t* err = nullptr) {
   constexpr int NQ = D / 8;
-  constexpr int P = D + 4;
-  constexpr int LV = RK_CHUNK * D / 4 / 256;
-  static_assert(LV >= 1 && RK_CHUNK * D / 4 % 256 == 0, "chunk staging assumes d % 16 == 0");
+  using Stage = ScStage<D, RK_CHUNK>;
+  constexpr int P = Stage::P;
+  static_assert(Stage::FULL, "chunk staging assumes d % 16 == 0");
   __shared__ __attribute__((aligned(16))) float tab[2][RK_CHUNK * P];
   const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, hh = lane >> 5;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -97,46 +82,30 @@ __global__ __launch_bounds__(256, 2) void score_count_kernel(const float* __rest
     const int64_t u = u0 + ut * 32 + r;
     const int64_t uc = u < B ? u : B - 1;
 #pragma unroll
-    for (int gq = 0; gq < NQ; ++gq) {
+    for (int gq = 0; gq < NQ; ++gq) {   // score_chain.h sc_load_user, in place (see above)
       const f32x4 v = *reinterpret_cast<const f32x4*>(h + uc * D + sc_feat(gq, hh));
       hf[ut][gq] = u < B ? v : f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    if (PAIRS) {   // score_pairs_kernel's tile: A = the users, B = their target rows; the diagonal
-      int64_t t = ids[uc];
-      if (t < 0 || t >= rows) {
-        if (u < B) set_err(err, 1);
-        t = 0;
-      }
-      f32x16 pacc;
-#pragma unroll
-      for (int v = 0; v < 16; ++v) pacc[v] = 0.f;
-#pragma unroll
-      for (int gq = 0; gq < NQ; ++gq) {
-        const f32x4 a = *reinterpret_cast<const f32x4*>(h + uc * D + sc_feat(gq, hh));
-        const f32x4 bt = *reinterpret_cast<const f32x4*>(table + t * D + sc_feat(gq, hh));
-#pragma unroll
-        for (int s = 0; s < 4; ++s) pacc = mfma32(a[s], bt[s], pacc);
-      }
-      float dg = 0.f;   // user r's target logit, on the lane half with ((r >> 2) & 1) == hh
-#pragma unroll
-      for (int v = 0; v < 16; ++v)
-        if ((v & 3) + 8 * (v >> 2) + 4 * hh == r) dg = pacc[v];
+    if (PAIRS) {   // score_pairs_kernel's tile: user r's target logit on its diagonal lane
+      const int64_t t = sc_pair_target(ids, u, B, rows, err);
+      float dg = sc_pair_logit<D>(h, u, B, table, t, r, hh);
       if (mask_col0 && t == 0) dg = RK_MASK;
 #pragma unroll
-      for (int v = 0; v < 16; ++v) {   // register v's user (v&3) + 8(v>>2) + 4hh: from its diagonal lane
-        const int uu = (v & 3) + 8 * (v >> 2) + 4 * hh;
+      for (int v = 0; v < 16; ++v) {   // register v's user mfma32_row(v, hh): from its diagonal lane
+        const int uu = mfma32_row(v, hh);
         th[ut][v] = __shfl(dg, uu + 32 * ((uu >> 2) & 1));
       }
     } else {
 #pragma unroll
       for (int v = 0; v < 16; ++v) {
-        const int64_t uu = u0 + ut * 32 + (v & 3) + 8 * (v >> 2) + 4 * hh;
+        const int64_t uu = u0 + ut * 32 + mfma32_row(v, hh);
         th[ut][v] = thr[uu < B ? uu : B - 1];
       }
     }
   }
+  constexpr int LV = Stage::LV;
   f32x4 st[LV];
-  auto gload = [&](int64_t c) {
+  auto gload = [&](int64_t c) {   // ScStage::gload / swrite, in place
 #pragma unroll
     for (int i = 0; i < LV; ++i) {
       const int f = tid + 256 * i, row = f / (D / 4), col = (f % (D / 4)) * 4;
@@ -164,7 +133,7 @@ __global__ __launch_bounds__(256, 2) void score_count_kernel(const float* __rest
 #pragma unroll 1
   for (int64_t c = c_begin; c < c_end; ++c) {
     if (c + 1 < c_end) gload(c + 1);
-    f32x16 acc[UT][2];
+    f32x16 acc[UT][2];   // sc_chunk_chain<D, 2, false>, in place
 #pragma unroll
     for (int ut = 0; ut < UT; ++ut)
 #pragma unroll
@@ -219,7 +188,7 @@ __global__ __launch_bounds__(256, 2) void score_count_kernel(const float* __rest
       int x = cnt[ut][v];
 #pragma unroll
       for (int o = 1; o < 32; o <<= 1) x += __shfl_xor(x, o);
-      const int64_t u = u0 + ut * 32 + (v & 3) + 8 * (v >> 2) + 4 * hh;
+      const int64_t u = u0 + ut * 32 + mfma32_row(v, hh);
       // slice sl adds into copy sl % copies: at most ceil(slices / copies) adds per address (a
       // short batch split over every CU's slices would otherwise queue hundreds of adds on one word)
       if (r == 0 && u < B && x) atomicAdd(&cnt_out[(int64_t)(sl % copies) * B + u], (unsigned long long)x);
@@ -242,17 +211,6 @@ __global__ __launch_bounds__(256) void count_copies_kernel(unsigned long long* _
 
 constexpr int RK_COPIES = 16;   // count copies in the workspace form
 
-static int cu_count() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-      cus = 256;
-  }
-  return cus;
-}
-
 }  // namespace gr
 
 extern "C" int gr_score_pairs_f32(const float* h, int64_t B, int32_t d, const float* table,
@@ -269,16 +227,13 @@ int gr_score_pairs_launch(const float* h, int64_t B, int32_t d, const float* tab
   if (B < 0 || rows < 1) return fail(GR_ERR_ARG, "gr_score_pairs_f32: bad shape");
   if (B == 0) return GR_OK;
   if (!h || !table || !ids || !out) return fail(GR_ERR_ARG, "gr_score_pairs_f32: null pointer");
-  if (d != 16 && d != 32 && d != 64 && d != 128)
-    return fail(GR_ERR_UNSUPPORTED, "gr_score_pairs_f32: d must be 16, 32, 64 or 128");
-  if (!aligned16(h) || !aligned16(table)) return fail(GR_ERR_ARG, "gr_score_pairs_f32: h / table not 16-byte aligned");
+  if (int rc = sc_check("gr_score_pairs_f32", d, h, table)) return rc;
   const unsigned grid = (unsigned)((B + 31) / 32);
-  switch (d) {
-    case 16: hipLaunchKernelGGL(score_pairs_kernel<16>, dim3(grid), dim3(64), 0, st, h, B, table, rows, ids, mask_col0, out, err_flag); break;
-    case 32: hipLaunchKernelGGL(score_pairs_kernel<32>, dim3(grid), dim3(64), 0, st, h, B, table, rows, ids, mask_col0, out, err_flag); break;
-    case 64: hipLaunchKernelGGL(score_pairs_kernel<64>, dim3(grid), dim3(64), 0, st, h, B, table, rows, ids, mask_col0, out, err_flag); break;
-    default: hipLaunchKernelGGL(score_pairs_kernel<128>, dim3(grid), dim3(64), 0, st, h, B, table, rows, ids, mask_col0, out, err_flag); break;
-  }
+  sc_dispatch_d(d, [&](auto dd) {
+    constexpr int DD = decltype(dd)::value;
+    hipLaunchKernelGGL(score_pairs_kernel<DD>, dim3(grid), dim3(64), 0, st, h, B, table, rows, ids, mask_col0,
+                       out, err_flag);
+  });
   return check_launch("gr_score_pairs_f32");
 }
 
@@ -294,15 +249,10 @@ static int count_launch(const float* h, int64_t B, int32_t d, const float* table
   if (B < 0 || rows < 0) return fail(GR_ERR_ARG, "gr_score_count_gt_f32: bad shape");
   if (B == 0) return GR_OK;
   if (!h || !table || !(thresholds || pair_ids) || !counts_out) return fail(GR_ERR_ARG, "gr_score_count_gt_f32: null pointer");
-  if (d != 16 && d != 32 && d != 64 && d != 128)
-    return fail(GR_ERR_UNSUPPORTED, "gr_score_count_gt_f32: d must be 16, 32, 64 or 128");
-  if (!aligned16(h) || !aligned16(table)) return fail(GR_ERR_ARG, "gr_score_count_gt_f32: h / table not 16-byte aligned");
+  if (int rc = sc_check("gr_score_count_gt_f32", d, h, table)) return rc;
   const int64_t ublocks = (B + 128 * RK_UT - 1) / (128 * RK_UT);
   const int64_t chunks = (rows + RK_CHUNK - 1) / RK_CHUNK;
-  const int64_t per_cu = 2;   // resident workgroups per CU (registers, LDS)
-  int64_t slices = per_cu * cu_count() / ublocks;   // rounded down: every workgroup resident at once
-  if (slices > chunks) slices = chunks;
-  if (slices < 1) slices = 1;
+  const int64_t slices = sc_slices(2, ublocks, chunks);   // two resident workgroups per CU (registers, LDS)
   if (ublocks * slices > 0x7fffffffLL) return fail(GR_ERR_UNSUPPORTED, "gr_score_count_gt_f32: grid too large");
   // the workspace form (a zeroed buffer of RK_COPIES copies) when many slices share each user: the
   // counts go to slice % RK_COPIES and one more launch sums the copies
@@ -317,20 +267,15 @@ static int count_launch(const float* h, int64_t B, int32_t d, const float* table
   }
   const int nc = copies ? RK_COPIES : 1;
   const dim3 g((unsigned)(ublocks * slices)), b(256);
-#define GR_CNT(DD)                                                                                           \
-  if (pair_ids)                                                                                              \
-    hipLaunchKernelGGL((score_count_kernel<DD, true>), g, b, 0, st, h, B, table, rows, thresholds, mask_col0, \
-                       cnt, (int)ublocks, (int)slices, nc, pair_ids, err);                                   \
-  else                                                                                                       \
-    hipLaunchKernelGGL((score_count_kernel<DD, false>), g, b, 0, st, h, B, table, rows, thresholds, mask_col0, \
-                       cnt, (int)ublocks, (int)slices, nc, nullptr, nullptr)
-  switch (d) {
-    case 16: GR_CNT(16); break;
-    case 32: GR_CNT(32); break;
-    case 64: GR_CNT(64); break;
-    default: GR_CNT(128); break;
-  }
-#undef GR_CNT
+  sc_dispatch_d(d, [&](auto dd) {
+    constexpr int DD = decltype(dd)::value;
+    if (pair_ids)
+      hipLaunchKernelGGL((score_count_kernel<DD, true>), g, b, 0, st, h, B, table, rows, thresholds, mask_col0,
+                         cnt, (int)ublocks, (int)slices, nc, pair_ids, err);
+    else
+      hipLaunchKernelGGL((score_count_kernel<DD, false>), g, b, 0, st, h, B, table, rows, thresholds, mask_col0,
+                         cnt, (int)ublocks, (int)slices, nc, nullptr, nullptr);
+  });
   int rc = check_launch("gr_score_count_gt_f32");
   if (rc || !copies) return rc;
   hipLaunchKernelGGL(count_copies_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, cnt, B, RK_COPIES,

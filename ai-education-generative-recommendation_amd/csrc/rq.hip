@@ -725,17 +725,6 @@ __global__ __launch_bounds__(256) void rq_code_norms_kernel(const float* __restr
   cn[c] = aten_rowsq([&](int f) { return row[f]; }, e);
 }
 
-static int cu_count() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-      cus = 256;
-  }
-  return cus;
-}
-
 static int launch_norms(const float* cb, int K, int e, float* cn, hipStream_t st) {
   hipLaunchKernelGGL(rq_code_norms_kernel, dim3((K + 255) / 256), dim3(256), 0, st, cb, K, e, cn);
   return check_launch("gr_rq_codebook_norms_f32");

@@ -29,13 +29,8 @@ namespace mt {
 
 constexpr int NT = 256;   // 4 waves, one output tile each
 
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {   // splitmix64 finaliser
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
+// The MLP's dropout: keyed by (site, flat element index) on the shared hash (gr_common.h mix64,
+// u01_24); not the SASRec gr::SasDrop, which also keys by sequence.
 struct Drop {
   float p, scale;
   uint64_t seed;
@@ -45,8 +40,7 @@ struct Drop {
     if (p <= 0.f) return 1.f;
     const uint64_t key = ((uint64_t)site << 44) ^ (uint64_t)(m * K + k);
     const uint64_t z = mix64(seed ^ mix64(key));
-    const float u = (float)(z >> 40) * (1.0f / 16777216.0f);   // 24-bit uniform in [0, 1)
-    return u >= p ? scale : 0.f;
+    return u01_24(z) >= p ? scale : 0.f;
   }
 };
 
@@ -163,7 +157,7 @@ __global__ __launch_bounds__(NT) void mlp_fwd_kernel(const float* __restrict__ X
   const Drop dr = make_drop(p, seed_dev, site_next);
 #pragma unroll
   for (int v = 0; v < 16; ++v) {
-    const int64_t i = ti * 32 + (v & 3) + 8 * (v >> 2) + 4 * h;
+    const int64_t i = ti * 32 + mfma32_row(v, h);
     if (i < M) {
       float u = acc[v] + bj;
       if (relu) u = (u < 0.f ? 0.f : u) * dr.keep(i, j, N);
@@ -201,7 +195,7 @@ __global__ __launch_bounds__(NT) void mlp_bwd_kernel(const float* __restrict__ X
     if (k >= K) return;
 #pragma unroll
     for (int v = 0; v < 16; ++v) {
-      const int64_t n = ti * 32 + (v & 3) + 8 * (v >> 2) + 4 * h;
+      const int64_t n = ti * 32 + mfma32_row(v, h);
       if (n < N) dW[n * K + k] = acc[v];
     }
     return;
@@ -221,7 +215,7 @@ __global__ __launch_bounds__(NT) void mlp_bwd_kernel(const float* __restrict__ X
     const Drop dr = make_drop(p, seed_dev, site);
 #pragma unroll
     for (int v = 0; v < 16; ++v) {
-      const int64_t m = ti * 32 + (v & 3) + 8 * (v >> 2) + 4 * h;
+      const int64_t m = ti * 32 + mfma32_row(v, h);
       if (m < M) {
         float gx = acc[v];
         if (dx_mode == 1) gx = Xd[m * K + k] > 0.f ? gx * dr.scale : 0.f;

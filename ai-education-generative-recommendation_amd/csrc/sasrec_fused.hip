@@ -125,7 +125,7 @@ __device__ __forceinline__ void layernorm(f32x16 (&y)[DT][TT], const f32x16 (&x)
     for (int ft = 0; ft < DT; ++ft)
 #pragma unroll
       for (int v = 0; v < 16; ++v) {
-        const int f = 32 * ft + (v & 3) + 8 * (v >> 2) + 4 * h;
+        const int f = 32 * ft + mfma32_row(v, h);
         const float t = x[ft][tt][v] - mean;
         var = (EXACT || f < d) ? fmaf(t, t, var) : var;
       }
@@ -359,7 +359,7 @@ __global__ __launch_bounds__(256) void sasrec_fused_kernel(const SasFusedArgs a,
           for (int ft = 0; ft < DT; ++ft)
 #pragma unroll
             for (int v = 0; v < 16; ++v) {
-              const int f = 32 * ft + (v & 3) + 8 * (v >> 2) + 4 * h;
+              const int f = 32 * ft + mfma32_row(v, h);
               sc[f] = Hn[ft][tt][v];
               sc[64 + f] = X[ft][tt][v];
             }
@@ -566,7 +566,7 @@ __global__ __launch_bounds__(256) void sasrec_fused_kernel(const SasFusedArgs a,
           for (int kt = 0; kt <= qt; ++kt)
 #pragma unroll
             for (int v = 0; v < 16; ++v) {
-              const int kj = 32 * kt + (v & 3) + 8 * (v >> 2) + 4 * h;
+              const int kj = 32 * kt + mfma32_row(v, h);
               if (kt == qt && kj > qi) S[kt][v] = -INFINITY;
               m = fmaxf(m, S[kt][v]);
             }
@@ -739,7 +739,7 @@ __device__ __forceinline__ void attn_tile(f32x16 (&O)[DT][1], const f32x16 (&Q)[
     for (int kt = 0; kt <= QT; ++kt)
 #pragma unroll
       for (int v = 0; v < 16; ++v) {
-        const int kj = 32 * kt + (v & 3) + 8 * (v >> 2) + 4 * h;
+        const int kj = 32 * kt + mfma32_row(v, h);
         if (kt == QT && kj > qi) S[kt][v] = -INFINITY;
         m = fmaxf(m, S[kt][v]);
       }
@@ -853,7 +853,7 @@ __global__ __launch_bounds__(256, 2) void sasrec_fused2_kernel(const SasFusedArg
           for (int ft = 0; ft < DT; ++ft)
 #pragma unroll
             for (int v = 0; v < 16; ++v) {
-              const int f = 32 * ft + (v & 3) + 8 * (v >> 2) + 4 * h;
+              const int f = 32 * ft + mfma32_row(v, h);
               sc[f] = Hn[ft][0][v];
               sc[64 + f] = X[ft][0][v];
             }

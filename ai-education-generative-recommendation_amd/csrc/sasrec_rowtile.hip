@@ -181,7 +181,7 @@ __device__ __forceinline__ void rt_project(const float* img, const float* __rest
     for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
       for (int v = 0; v < 16; ++v) {
-        const int row = 32 * rt + (v & 3) + 8 * (v >> 2) + 4 * h;
+        const int row = 32 * rt + mfma32_row(v, h);
         if (row < rows_left) out[(int64_t)row * nout + c] = acc[rt][v] + bv;
       }
   }
@@ -377,7 +377,7 @@ __global__ __launch_bounds__(512, 4) void post_attn8_kernel(const RowTileArgs a,
       const float bv = a.bn[pc];
 #pragma unroll
       for (int v = 0; v < 16; ++v) {
-        const int row = 32 * prt + (v & 3) + 8 * (v >> 2) + 4 * h;
+        const int row = 32 * prt + mfma32_row(v, h);
         if (row < left) out[(int64_t)row * a.nout + pc] = acc[v] + bv;
       }
     }

@@ -45,33 +45,10 @@ struct Args {
   int vwidth;   // floats per sequence in buf.g_vec
 };
 
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {   // splitmix64 finaliser
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-// keep factor of element idx at dropout site `site` of sequence b: 0 or 1 / (1 - p)
-__device__ __forceinline__ float keep(const Args& a, uint64_t seed, int64_t b, int site, uint32_t idx) {
-  if (a.p_drop <= 0.f) return 1.f;
-  const uint64_t key = ((uint64_t)site << 32) | idx;
-  const uint64_t z = mix64(seed ^ mix64((uint64_t)b ^ mix64(key)));
-  const float u = (float)(z >> 40) * (1.0f / 16777216.0f);   // 24-bit uniform in [0, 1)
-  return u >= a.p_drop ? a.keep_scale : 0.f;
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
+// The dropout masks are gr_common.h's sas_seed_of() / sas_keep(), shared with
+// sasrec_train_tiled.hip and read straight from Args' p_drop, keep_scale, seed0 and seed_dev
+// (SasDrop's fields under SasDrop's names).  An embedded SasDrop moves the kernel arguments and with
+// them both kernels' register allocation (profiles/r14/isa_identity.txt).
 
 // C[r][c] (r < R, c < Cn) = (ACC ? C : 0) + (sum_k A(r,k) B(k,c) + bias[c]) * post
 // with A(r,k) = A[r*sar + k*sak], B(k,c) = Bm[k*sbk + c*sbc]; operands in LDS or global memory,
@@ -127,7 +104,7 @@ __device__ __forceinline__ void mm(float* C, int ldc, const float* A, int sar, i
     const int col = tc * 32 + i32;
 #pragma unroll
     for (int v = 0; v < 16; ++v) {
-      const int row = tr * 32 + (v & 3) + 8 * (v >> 2) + 4 * h;
+      const int row = tr * 32 + mfma32_row(v, h);
       if (row < R && col < Cn) {
         float x = acc[v];
         if (bias) x += bias[col];
@@ -268,7 +245,7 @@ __global__ __launch_bounds__(NT) void sas_train_fwd_kernel(const Args a, const i
   const int n = a.n, d = a.d, m = a.mlp, H = a.heads, hd = d / H, d3 = 3 * d;
   const int pd = d + 1, pw = (d3 > m ? d3 : m) + 1, pn = n + 1;   // odd LDS pitches: conflict-free columns
   const int64_t b = blockIdx.x;
-  const uint64_t seed = a.seed_dev ? a.seed0 ^ *a.seed_dev : a.seed0;
+  const uint64_t seed = sas_seed_of(a);
   float* X = sm;                       // [n][pd] residual stream
   float* Hb = X + n * pd;              // [n][pd] LN output / attention output / FFN2 output
   float* BIG = Hb + n * pd;            // [n][pw] Q|K|V, then the FFN hidden layer
@@ -317,7 +294,7 @@ __global__ __launch_bounds__(NT) void sas_train_fwd_kernel(const Args a, const i
         const float pr = e / wave_sum(e);
         if (lane < n) {
           g.prob[o.pp + ((int64_t)hh * n + i) * n + lane] = pr;
-          S[i * pn + lane] = pr * keep(a, seed, b, 3 * bk, (uint32_t)((hh * n + i) * n + lane));
+          S[i * pn + lane] = pr * sas_keep(a, seed, b, 3 * bk, (uint32_t)((hh * n + i) * n + lane));
         }
       }
       __syncthreads();
@@ -339,7 +316,7 @@ __global__ __launch_bounds__(NT) void sas_train_fwd_kernel(const Args a, const i
     __syncthreads();
     for (int idx = tid; idx < n * m; idx += NT) {                                  // dropout(relu)
       const int i = idx / m, c = idx - i * m;
-      BIG[i * pw + c] = fmaxf(BIG[i * pw + c], 0.f) * keep(a, seed, b, 3 * bk + 1, (uint32_t)idx);
+      BIG[i * pw + c] = fmaxf(BIG[i * pw + c], 0.f) * sas_keep(a, seed, b, 3 * bk + 1, (uint32_t)idx);
     }
     __syncthreads();
     copy_out(g.us + o.rm, BIG, pw, n, m);
@@ -347,7 +324,7 @@ __global__ __launch_bounds__(NT) void sas_train_fwd_kernel(const Args a, const i
     __syncthreads();
     for (int idx = tid; idx < n * d; idx += NT) {                                  // x + dropout(y) (model.py:94)
       const int i = idx / d, f = idx - i * d;
-      X[i * pd + f] += Hb[i * pd + f] * keep(a, seed, b, 3 * bk + 2, (uint32_t)idx);
+      X[i * pd + f] += Hb[i * pd + f] * sas_keep(a, seed, b, 3 * bk + 2, (uint32_t)idx);
     }
     __syncthreads();
   }
@@ -362,7 +339,7 @@ __global__ __launch_bounds__(NT) void sas_train_bwd_kernel(const Args a, const i
   const int n = a.n, d = a.d, m = a.mlp, H = a.heads, hd = d / H, d3 = 3 * d;
   const int pd = d + 1, pw = (d3 > m ? d3 : m) + 1, pn = n + 1;
   const int64_t b = blockIdx.x;
-  const uint64_t seed = a.seed_dev ? a.seed0 ^ *a.seed_dev : a.seed0;
+  const uint64_t seed = sas_seed_of(a);
   float* DX = sm;                      // [n][pd] gradient of the residual stream
   float* T = DX + n * pd;              // [n][pd] dY, df, dO, dh
   float* G1 = T + n * pd;              // [n][pw] dU / dZ, then dQ|dK|dV
@@ -389,7 +366,7 @@ __global__ __launch_bounds__(NT) void sas_train_bwd_kernel(const Args a, const i
     // FFN output: x2 = x1 + dropout(y), y = u W2^T + b2
     for (int idx = tid; idx < n * d; idx += NT) {
       const int i = idx / d, f = idx - i * d;
-      T[i * pd + f] = DX[i * pd + f] * keep(a, seed, b, 3 * bk + 2, (uint32_t)idx);
+      T[i * pd + f] = DX[i * pd + f] * sas_keep(a, seed, b, 3 * bk + 2, (uint32_t)idx);
     }
     __syncthreads();
     col_sums(gvb + vo.b2, T, pd, n, d);                                              // db2
@@ -398,7 +375,7 @@ __global__ __launch_bounds__(NT) void sas_train_bwd_kernel(const Args a, const i
     __syncthreads();
     for (int idx = tid; idx < n * m; idx += NT) {                                   // through dropout and relu
       const int i = idx / m, c = idx - i * m;
-      G1[i * pw + c] = g.zs[o.rm + idx] > 0.f ? G1[i * pw + c] * keep(a, seed, b, 3 * bk + 1, (uint32_t)idx) : 0.f;
+      G1[i * pw + c] = g.zs[o.rm + idx] > 0.f ? G1[i * pw + c] * sas_keep(a, seed, b, 3 * bk + 1, (uint32_t)idx) : 0.f;
     }
     __syncthreads();
     col_sums(gvb + vo.b1, G1, pw, n, m);                                             // db1
@@ -416,7 +393,7 @@ __global__ __launch_bounds__(NT) void sas_train_bwd_kernel(const Args a, const i
       const float* P = g.prob + o.pp + (int64_t)hh * n * n;
       for (int idx = tid; idx < n * n; idx += NT) {                                 // P' = P * keep
         const int i = idx / n, j = idx - i * n;
-        PS[i * pn + j] = P[idx] * keep(a, seed, b, 3 * bk, (uint32_t)(hh * n * n + idx));
+        PS[i * pn + j] = P[idx] * sas_keep(a, seed, b, 3 * bk, (uint32_t)(hh * n * n + idx));
       }
       __syncthreads();
       mm<false>(G1 + 2 * d + hh * hd, pw, PS, 1, pn, T + hh * hd, pd, 1, n, hd, n); // dV = P'^T dO
@@ -426,7 +403,7 @@ __global__ __launch_bounds__(NT) void sas_train_bwd_kernel(const Args a, const i
       for (int i = wv; i < n; i += NT / 64) {                                       // softmax backward
         const bool on = lane <= i && lane < n;
         const float pr = on ? P[i * n + lane] : 0.f;
-        const float dp = on ? PS[i * pn + lane] * keep(a, seed, b, 3 * bk, (uint32_t)((hh * n + i) * n + lane)) : 0.f;
+        const float dp = on ? PS[i * pn + lane] * sas_keep(a, seed, b, 3 * bk, (uint32_t)((hh * n + i) * n + lane)) : 0.f;
         const float sdp = wave_sum(dp * pr);
         if (lane < n) PS[i * pn + lane] = on ? pr * (dp - sdp) : 0.f;
       }

@@ -2,9 +2,9 @@
 // (sasrec_train.hip: n, d <= 64, mlp_layer <= 128): d <= 128, n <= 256, mlp_layer <= 256.
 //
 // The same computation (SASRec/model.py:49-96 in train mode and its backward), the same saved
-// activations (gr_sasrec_train_bufs) and the same dropout masks (keep() below is sasrec_train.hip's,
-// keyed by seed, sequence, site and element), but tiled over all B * n rows instead of held in one
-// workgroup's LDS:
+// activations (gr_sasrec_train_bufs) and the same dropout masks (gr_common.h SasDrop / sas_keep(),
+// shared with sasrec_train.hip: keyed by seed, sequence, site and element), but tiled over all
+// B * n rows instead of held in one workgroup's LDS:
 //   - every product is one launch of gemm_kernel: 64 x 64 output tiles on v_mfma_f32_32x32x2_f32,
 //     operands staged through LDS from any (row stride, k stride) layout, a two-level batch index
 //     (sequence, head) for the attention products, causal tile / k-range skipping, and an epilogue
@@ -32,44 +32,6 @@ static_assert(NMAX <= 4 * 64 && DMAX <= 2 * 64, "softmax rows hold four keys per
 constexpr int MAXPARTS = 32;           // partial rows of g_vec
 constexpr int PART_ROWS = 256;          // at least this many rows per part
 
-struct Drop {
-  float p_drop, keep_scale;
-  uint64_t seed0;
-  const uint64_t* seed_dev;
-};
-
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {   // splitmix64 finaliser
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-__device__ __forceinline__ uint64_t seed_of(const Drop& dr) {
-  return dr.seed_dev ? dr.seed0 ^ *dr.seed_dev : dr.seed0;
-}
-
-// keep factor of element idx at dropout site `site` of sequence b: 0 or 1 / (1 - p) (sasrec_train.hip keep())
-__device__ __forceinline__ float keep(const Drop& dr, uint64_t seed, int64_t b, int site, uint32_t idx) {
-  if (dr.p_drop <= 0.f) return 1.f;
-  const uint64_t key = ((uint64_t)site << 32) | idx;
-  const uint64_t z = mix64(seed ^ mix64((uint64_t)b ^ mix64(key)));
-  const float u = (float)(z >> 40) * (1.0f / 16777216.0f);   // 24-bit uniform in [0, 1)
-  return u >= dr.p_drop ? dr.keep_scale : 0.f;
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 // ---- the product kernel --------------------------------------------------------------------
 // C[z](r, c) = epilogue(sum_k A[z](r, k) B[z](k, c)), r < M, c < N, k in the batch's k range.
 // A[z](r, k) = A[zo * sAo + zi * sAi + r * sar + k * sak] with z = zo * zdiv + zi, B and C alike.
@@ -92,7 +54,7 @@ struct Gemm {
   const float* R;   // E_RES / E_FFN2: the residual; E_DZ: the FFN1 pre-activation (pitch ldc)
   float* C2;        // E_FFN1: dropout(relu(.)) beside the pre-activation
   int site, n;      // dropout site; rows per sequence
-  Drop dr;
+  SasDrop dr;
 };
 
 template <int EPI>
@@ -167,11 +129,11 @@ __global__ __launch_bounds__(GT) void gemm_kernel(const Gemm g) {
   const int64_t col = (int64_t)tc * TN + wc * 32 + i32;
   if (col >= g.N) return;
   uint64_t seed = 0;
-  if (EPI == E_FFN1 || EPI == E_FFN2 || EPI == E_DZ) seed = seed_of(g.dr);
+  if (EPI == E_FFN1 || EPI == E_FFN2 || EPI == E_DZ) seed = sas_seed_of(g.dr);
   const float bias = g.bias ? g.bias[col] : 0.f;
 #pragma unroll
   for (int v = 0; v < 16; ++v) {
-    const int64_t row = (int64_t)tr * TM + wr * 32 + (v & 3) + 8 * (v >> 2) + 4 * h;
+    const int64_t row = (int64_t)tr * TM + wr * 32 + (v & 3) + 8 * (v >> 2) + 4 * h;   // (mfma32_row here moves the register allocation)
     if (row >= g.M) continue;
     const int64_t o = row * g.ldc + col;
     float x = acc[v] + bias;
@@ -182,7 +144,7 @@ __global__ __launch_bounds__(GT) void gemm_kernel(const Gemm g) {
     } else {
       const int64_t b = row / g.n;
       const uint32_t idx = (uint32_t)((row - b * g.n) * g.N + col);
-      const float kf = keep(g.dr, seed, b, g.site, idx);
+      const float kf = sas_keep(g.dr, seed, b, g.site, idx);
       if (EPI == E_FFN1) {
         C[o] = x;
         g.C2[o] = fmaxf(x, 0.f) * kf;
@@ -243,12 +205,12 @@ __global__ __launch_bounds__(GT) void ln_fwd_kernel(const float* __restrict__ X,
 }
 
 // LayerNorm backward of one row: DX = (ACC ? DX : 0) + dLN/dx; the row's (mean, rstd) go to stats
-// for the dgamma / dbeta column sums; dy_out (optional) = new DX * keep(site, i * d + f): the
+// for the dgamma / dbeta column sums; dy_out (optional) = new DX * sas_keep(site, i * d + f): the
 // gradient of the FFN output of the block below.
 __global__ __launch_bounds__(GT) void ln_bwd_kernel(const float* __restrict__ X, const float* __restrict__ DY,
                                                     float* __restrict__ DX, int acc, const float* __restrict__ w,
                                                     float* __restrict__ stats, float* __restrict__ dy_out, int site,
-                                                    int n, int64_t rows, int d, float eps, const Drop dr) {
+                                                    int n, int64_t rows, int d, float eps, const SasDrop dr) {
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * (GT / 64) + (threadIdx.x >> 6);
   if (row >= rows) return;
@@ -284,7 +246,7 @@ __global__ __launch_bounds__(GT) void ln_bwd_kernel(const float* __restrict__ X,
     stats[2 * row] = mean;
     stats[2 * row + 1] = rstd;
   }
-  const uint64_t seed = dy_out ? seed_of(dr) : 0;
+  const uint64_t seed = dy_out ? sas_seed_of(dr) : 0;
   const int64_t b = row / n;
   const int i = (int)(row - b * n);
 #pragma unroll
@@ -294,7 +256,7 @@ __global__ __launch_bounds__(GT) void ln_bwd_kernel(const float* __restrict__ X,
       float v = rstd * (dxh[t] - s1 - xh[t] * s2);
       if (acc) v += DX[row * d + f];
       DX[row * d + f] = v;
-      if (dy_out) dy_out[row * d + f] = v * keep(dr, seed, b, site, (uint32_t)(i * d + f));
+      if (dy_out) dy_out[row * d + f] = v * sas_keep(dr, seed, b, site, (uint32_t)(i * d + f));
     }
   }
 }
@@ -302,7 +264,7 @@ __global__ __launch_bounds__(GT) void ln_bwd_kernel(const float* __restrict__ X,
 // causal softmax of one query row of one (sequence, head): S holds the scaled scores of keys j <= i;
 // P (the saved probabilities, zero past i) overwrites them, PK = P * keep (site, (h n + i) n + j)
 __global__ __launch_bounds__(GT) void softmax_fwd_kernel(float* __restrict__ P, float* __restrict__ PK, int64_t rows,
-                                                         int n, int H, int site, const Drop dr) {
+                                                         int n, int H, int site, const SasDrop dr) {
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * (GT / 64) + (threadIdx.x >> 6);
   if (row >= rows) return;
@@ -310,7 +272,7 @@ __global__ __launch_bounds__(GT) void softmax_fwd_kernel(float* __restrict__ P, 
   const int i = (int)(row - bh * n);
   const int64_t b = bh / H;
   const int hh = (int)(bh - b * H);
-  const uint64_t seed = seed_of(dr);
+  const uint64_t seed = sas_seed_of(dr);
   float sv[4], mx = -__builtin_inff();
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
@@ -332,7 +294,7 @@ __global__ __launch_bounds__(GT) void softmax_fwd_kernel(float* __restrict__ P, 
     if (j < n) {
       const float pr = sv[t] / sum;
       P[row * n + j] = pr;
-      PK[row * n + j] = pr * keep(dr, seed, b, site, (uint32_t)((hh * n + i) * n + j));
+      PK[row * n + j] = pr * sas_keep(dr, seed, b, site, (uint32_t)((hh * n + i) * n + j));
     }
   }
 }
@@ -341,7 +303,7 @@ __global__ __launch_bounds__(GT) void softmax_fwd_kernel(float* __restrict__ P, 
 // zero past i; PK = P * keep for dV = P'^T dO
 __global__ __launch_bounds__(GT) void softmax_bwd_kernel(const float* __restrict__ P, float* __restrict__ DS,
                                                          float* __restrict__ PK, int64_t rows, int n, int H, int site,
-                                                         const Drop dr) {
+                                                         const SasDrop dr) {
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * (GT / 64) + (threadIdx.x >> 6);
   if (row >= rows) return;
@@ -349,13 +311,13 @@ __global__ __launch_bounds__(GT) void softmax_bwd_kernel(const float* __restrict
   const int i = (int)(row - bh * n);
   const int64_t b = bh / H;
   const int hh = (int)(bh - b * H);
-  const uint64_t seed = seed_of(dr);
+  const uint64_t seed = sas_seed_of(dr);
   float pr[4], dp[4], kf[4], sdp = 0.f;
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
     const int j = lane + 64 * t;
     const bool on = j <= i;
-    kf[t] = on ? keep(dr, seed, b, site, (uint32_t)((hh * n + i) * n + j)) : 0.f;
+    kf[t] = on ? sas_keep(dr, seed, b, site, (uint32_t)((hh * n + i) * n + j)) : 0.f;
     pr[t] = on ? P[row * n + j] : 0.f;
     dp[t] = on ? DS[row * n + j] * kf[t] : 0.f;
     sdp = fmaf(dp[t], pr[t], sdp);
@@ -554,7 +516,7 @@ extern "C" int gr_sasrec_train_tiled_fwd_f32(const gr_sasrec_params* p, const in
   const int64_t R = B * n, BH = B * H;
   const int64_t nn = (int64_t)n * n;
   float* PK = static_cast<float*>(workspace) + w.pk;
-  const Drop dr{p_drop, 1.f / (1.f - p_drop), seed, seed_dev};
+  const SasDrop dr{p_drop, 1.f / (1.f - p_drop), seed, seed_dev};
   const float q_scale = sqrtf(1.f / (float)hd);   // F.multi_head_attention_forward: q * sqrt(1 / E)
   const unsigned eb = (unsigned)((R * d + GT - 1) / GT);
 
@@ -645,7 +607,7 @@ extern "C" int gr_sasrec_train_tiled_bwd_f32(const gr_sasrec_params* p, const in
   float* base = static_cast<float*>(workspace);
   float *DX = base + w.dx, *T = base + w.t, *Y = base + w.y, *G1 = base + w.g1, *stats = base + w.stats;
   float *PK = base + w.pk, *DS = base + w.ds;
-  const Drop dr{p_drop, 1.f / (1.f - p_drop), seed, seed_dev};
+  const SasDrop dr{p_drop, 1.f / (1.f - p_drop), seed, seed_dev};
   const float q_scale = sqrtf(1.f / (float)hd);
   const VOff vo = voff(d, m);
   const int S = parts_of(R);

@@ -19,11 +19,11 @@
 //       - store waves stream the table rows of the NEXT chunk HBM -> LDS and write the PREVIOUS
 //         chunk's logits to HBM as whole, aligned 128-byte lines of each row (the 32 items that
 //         fill a line straddle two chunks of the ring); one barrier per chunk hands over.
-// Every logit is the same k-ordered fp32 fma chain whatever its position (gr_common.h sc_feat: step
+// Every logit is the same k-ordered fp32 fma chain whatever its position (score_chain.h: step
 // s of float4 group gq takes feature 8 gq + s, then 8 gq + 4 + s), so a target's logit recomputed in
 // any shard or batch position is bit-identical — the strict '>' rank never counts the target itself
 // (SURVEY §7 hard part 3).
-#include "gr_common.h"
+#include "score_chain.h"
 
 namespace gr {
 
@@ -40,14 +40,6 @@ __device__ __forceinline__ int line_shift(uint32_t pbase, int ul, int64_t ld) {
   return (int)((32u - ((pbase + (uint32_t)((int64_t)ul * ld)) & 31u)) & 31u);
 }
 
-// Table-chunk staging by 256 threads: float4 slot f of a chunk is row f / (D/4), column 4 (f % (D/4));
-// d = 16 leaves half the threads idle.
-template <int D> struct ScStage {
-  static constexpr int NF = SC_CHUNK * D / 4;
-  static constexpr int LV = (NF + 255) / 256;
-  static constexpr bool FULL = NF % 256 == 0;   // every thread stages LV whole float4s: no guard
-};
-
 // The ring kernel (see the header): 4 compute + 4 store waves, one workgroup per CU; the XCD's
 // workgroups share one user block and sweep the catalog.
 template <int D>
@@ -55,15 +47,16 @@ __global__ __launch_bounds__(512, 1) void score_kernel(const float* __restrict__
                                                    const float* __restrict__ table, int64_t rows,
                                                    float* __restrict__ out, int64_t ld,
                                                    int ublocks, int slices) {
+  using Stage = ScStage<D, SC_CHUNK>;
   constexpr int NQ = D / 8;                        // float4 feature groups (sc_feat)
-  constexpr int P = D + 4;                         // LDS table row pitch (floats)
+  constexpr int P = Stage::P;                      // LDS table row pitch (floats)
   constexpr int CW = 4, SC_USERS = 256;            // compute waves; users per workgroup
   constexpr int UT = SC_USERS / (32 * CW);         // 32-user MFMA tiles per compute wave
   constexpr int UPW = 32 * UT;                     // users per compute wave
   constexpr int SWN = 4;                           // store waves
   constexpr int RPW = SC_USERS / SWN;              // logits rows per store wave
   constexpr int SI = RPW / 8;                      // store instructions (8 rows each) per line
-  constexpr int LV = ScStage<D>::LV;               // float4 per staging thread per chunk (256 threads)
+  constexpr int LV = Stage::LV;                    // float4 per staging thread per chunk (256 threads)
   constexpr int RW = SC_RING * SC_CHUNK;           // ring width per user row (items)
   __shared__ __attribute__((aligned(16))) float tab[2][SC_CHUNK * P];
   __shared__ __attribute__((aligned(16))) float ring[SC_USERS * RW];
@@ -90,15 +83,7 @@ __global__ __launch_bounds__(512, 1) void score_kernel(const float* __restrict__
     const int64_t u0 = ubase + wave * UPW;
     f32x4 hf[UT][NQ];   // lane (r, hh) of user tile ut: h[u][sc_feat(gq, hh) .. +3]
 #pragma unroll
-    for (int ut = 0; ut < UT; ++ut) {
-      const int64_t u = u0 + ut * 32 + r;
-      const int64_t uc = u < B ? u : B - 1;   // clamped load, zeroed below
-#pragma unroll
-      for (int gq = 0; gq < NQ; ++gq) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(h + uc * D + sc_feat(gq, hh));
-        hf[ut][gq] = u < B ? v : f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-    }
+    for (int ut = 0; ut < UT; ++ut) sc_load_user<D>(hf[ut], h, u0 + ut * 32 + r, B, hh);
     // ring position of item r of chunk 0 for each of the lane's 32 rows (register v of user
     // tile ut holds row 64 wave + 32 ut + rho(v) + 4 hh): (r - a) mod RW
     int rpos[UT][16];
@@ -106,7 +91,7 @@ __global__ __launch_bounds__(512, 1) void score_kernel(const float* __restrict__
     for (int ut = 0; ut < UT; ++ut)
 #pragma unroll
       for (int v = 0; v < 16; ++v) {
-        const int ul = wave * UPW + ut * 32 + (v & 3) + 8 * (v >> 2) + 4 * hh;
+        const int ul = wave * UPW + ut * 32 + mfma32_row(v, hh);
         const int p = r - line_shift(pbase, ul, ld);
         rpos[ut][v] = ul * RW + (p < 0 ? p + RW : p);
       }
@@ -134,7 +119,7 @@ __global__ __launch_bounds__(512, 1) void score_kernel(const float* __restrict__
       for (int ut = 0; ut < UT; ++ut)
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
-          const int ul_end = (wave * UPW + ut * 32 + (v & 3) + 8 * (v >> 2) + 4 * hh + 1) * RW;
+          const int ul_end = (wave * UPW + ut * 32 + mfma32_row(v, hh) + 1) * RW;
           const int p = rpos[ut][v] + cm;
           ring[p >= ul_end ? p - RW : p] = acc[ut][v];
         }
@@ -156,14 +141,14 @@ __global__ __launch_bounds__(512, 1) void score_kernel(const float* __restrict__
         const int f = stid + 256 * i, row = f / (D / 4), col = (f % (D / 4)) * 4;
         int64_t item = c * SC_CHUNK + row;
         item = item < rows ? item : rows - 1;   // past-the-end items are never stored
-        if (ScStage<D>::FULL || f < ScStage<D>::NF) st[sb][i] = *reinterpret_cast<const f32x4*>(table + item * D + col);
+        if (Stage::FULL || f < Stage::NF) st[sb][i] = *reinterpret_cast<const f32x4*>(table + item * D + col);
       }
     };
     auto swrite = [&](int b, int sb) {
 #pragma unroll
       for (int i = 0; i < LV; ++i) {
         const int f = stid + 256 * i, row = f / (D / 4), col = (f % (D / 4)) * 4;
-        if (ScStage<D>::FULL || f < ScStage<D>::NF) *reinterpret_cast<f32x4*>(&tab[b][row * P + col]) = st[sb][i];
+        if (Stage::FULL || f < Stage::NF) *reinterpret_cast<f32x4*>(&tab[b][row * P + col]) = st[sb][i];
       }
     };
     gload(c_begin, 0);
@@ -253,11 +238,11 @@ __global__ __launch_bounds__(256, 2) void score_direct_kernel(const float* __res
                                                             const float* __restrict__ table, int64_t rows,
                                                             float* __restrict__ out, int64_t ld,
                                                             int ublocks, int slices, int slice_major) {
-  // feature groups as (g, q): g over 32-deep groups, q over float4 slots (sc_feat(4 g + q, hh));
-  // the nested form keeps rounds 1-4's register layout and schedule at d >= 32
+  // feature groups as (g, q): g over 32-deep groups, q over float4 slots (group gq = QN g + q of
+  // score_chain.h); the nested loops keep rounds 1-4's schedule at d >= 32
   constexpr int KG = D >= 32 ? D / 32 : 1, QN = D >= 32 ? 4 : D / 8;
-  constexpr int P = D + 4;
-  constexpr int LV = ScStage<D>::LV;
+  using Stage = ScStage<D, SC_CHUNK>;
+  constexpr int P = Stage::P;
   __shared__ __attribute__((aligned(16))) float tab[2][SC_CHUNK * P];
   const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, hh = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -270,6 +255,10 @@ __global__ __launch_bounds__(256, 2) void score_direct_kernel(const float* __res
   const int64_t c_begin = chunks * sl / slices, c_end = chunks * (sl + 1) / slices;
   if (c_begin >= c_end) return;
   const int64_t u0 = (int64_t)ub * (128 * UT) + wave * (32 * UT);
+  // Fragment load and chunk staging: score_chain.h's sc_load_user / ScStage written out in place.
+  // Calling the helpers changed this kernel's schedule and measured outside the parent build's
+  // spread at d = 32 and 64 (profiles/r14/ab_chain_all_shared.txt), so it keeps its own text and
+  // machine code; test_score_layouts_identical pins it to the other forms.
   f32x4 hf[UT][KG][QN];
 #pragma unroll
   for (int ut = 0; ut < UT; ++ut) {
@@ -285,6 +274,7 @@ __global__ __launch_bounds__(256, 2) void score_direct_kernel(const float* __res
   }
   // row pointers of the lane's 32 rows (register v of user tile ut), column r
   const bool full_rows = u0 + 32 * UT <= B;
+  constexpr int LV = Stage::LV;
   f32x4 st[LV];
   auto gload = [&](int64_t c) {
 #pragma unroll
@@ -292,14 +282,14 @@ __global__ __launch_bounds__(256, 2) void score_direct_kernel(const float* __res
       const int f = tid + 256 * i, row = f / (D / 4), col = (f % (D / 4)) * 4;
       int64_t item = c * SC_CHUNK + row;
       item = item < rows ? item : rows - 1;
-      if (ScStage<D>::FULL || f < ScStage<D>::NF) st[i] = *reinterpret_cast<const f32x4*>(table + item * D + col);
+      if (Stage::FULL || f < Stage::NF) st[i] = *reinterpret_cast<const f32x4*>(table + item * D + col);
     }
   };
   auto swrite = [&](int b) {
 #pragma unroll
     for (int i = 0; i < LV; ++i) {
       const int f = tid + 256 * i, row = f / (D / 4), col = (f % (D / 4)) * 4;
-      if (ScStage<D>::FULL || f < ScStage<D>::NF) *reinterpret_cast<f32x4*>(&tab[b][row * P + col]) = st[i];
+      if (Stage::FULL || f < Stage::NF) *reinterpret_cast<f32x4*>(&tab[b][row * P + col]) = st[i];
     }
   };
   gload(c_begin);
@@ -313,7 +303,7 @@ __global__ __launch_bounds__(256, 2) void score_direct_kernel(const float* __res
   int64_t pk = -1;   // chunk held in prev (-1: none)
   auto store_one = [&](int t) {   // register t of prev: user tile t >> 4, register t & 15
     const int ut = t >> 4, v = t & 15;
-    const int rl = 32 * ut + (v & 3) + 8 * (v >> 2) + 4 * hh;
+    const int rl = 32 * ut + mfma32_row(v, hh);
     const int64_t col = pk * SC_CHUNK + r;
     float* op = obase + pk * SC_CHUNK + (int64_t)rl * ld;
     if (full_rows && pk * SC_CHUNK + SC_CHUNK <= rows) {
@@ -383,11 +373,10 @@ __global__ __launch_bounds__(256, 2) void score_rot_kernel(const float* __restri
                                                          const float* __restrict__ table, int64_t rows,
                                                          float* __restrict__ out, int64_t ld,
                                                          int ublocks, int slices, int slice_major) {
-  // feature groups as (g, q): g over 32-deep groups, q over float4 slots (sc_feat(4 g + q, hh));
-  // the nested form keeps rounds 1-4's register layout and schedule at d >= 32
+  // feature groups as (g, q), as in score_direct_kernel
   constexpr int KG = D >= 32 ? D / 32 : 1, QN = D >= 32 ? 4 : D / 8;
-  constexpr int P = D + 4;
-  constexpr int LV = ScStage<D>::LV;
+  using Stage = ScStage<D, SC_CHUNK>;
+  constexpr int P = Stage::P;
   __shared__ __attribute__((aligned(16))) float tab[2][SC_CHUNK * P];
   const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, hh = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -398,19 +387,9 @@ __global__ __launch_bounds__(256, 2) void score_rot_kernel(const float* __restri
   const int64_t c_begin = chunks * sl / slices, c_end = chunks * (sl + 1) / slices;
   if (c_begin >= c_end) return;
   const int64_t u0 = (int64_t)ub * 256 + wave * 64;
-  f32x4 hf[2][KG][QN];
+  f32x4 hf[2][D / 8];
 #pragma unroll
-  for (int ut = 0; ut < 2; ++ut) {
-    const int64_t u = u0 + ut * 32 + r;
-    const int64_t uc = u < B ? u : B - 1;
-#pragma unroll
-    for (int g = 0; g < KG; ++g)
-#pragma unroll
-      for (int q = 0; q < QN; ++q) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(h + uc * D + 32 * g + 8 * q + 4 * hh);
-        hf[ut][g][q] = u < B ? v : f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-  }
+  for (int ut = 0; ut < 2; ++ut) sc_load_user<D>(hf[ut], h, u0 + ut * 32 + r, B, hh);
   const bool full_rows = u0 + 64 <= B;
   // per register v: row rl(v) of user tile 0 (tile 1's row rl + 32 has the same line offset o,
   // 32 ld = 0 mod 32, and its store offset is 32 ld floats further: a scalar)
@@ -420,7 +399,7 @@ __global__ __launch_bounds__(256, 2) void score_rot_kernel(const float* __restri
   const int64_t ldm = ld & 31;
 #pragma unroll
   for (int v = 0; v < 16; ++v) {
-    const int rl = (v & 3) + 8 * (v >> 2) + 4 * hh;
+    const int rl = mfma32_row(v, hh);
     const int o = (int)((pw + (uint32_t)(((u0 + rl) & 31) * ldm)) & 31u);
     rot_addr[v] = (32 * hh + ((r - o) & 31)) * 4;
     if (PREOFF) voff[v] = (int)(((int64_t)rl * ld + 32 - o + r) * 4);
@@ -430,23 +409,9 @@ __global__ __launch_bounds__(256, 2) void score_rot_kernel(const float* __restri
   const int lane_c = (int)(16 * hh * ld) - 128 * hh + 128;
   const int ut_off = (int)(32 * ld * 4);
   const auto rs = __builtin_amdgcn_make_buffer_rsrc(out + u0 * ld - 32, 0, -1, 0x00020000);
-  f32x4 st[LV];
-  auto gload = [&](int64_t c) {
-#pragma unroll
-    for (int i = 0; i < LV; ++i) {
-      const int f = tid + 256 * i, row = f / (D / 4), col = (f % (D / 4)) * 4;
-      int64_t item = c * SC_CHUNK + row;
-      item = item < rows ? item : rows - 1;
-      if (ScStage<D>::FULL || f < ScStage<D>::NF) st[i] = *reinterpret_cast<const f32x4*>(table + item * D + col);
-    }
-  };
-  auto swrite = [&](int b) {
-#pragma unroll
-    for (int i = 0; i < LV; ++i) {
-      const int f = tid + 256 * i, row = f / (D / 4), col = (f % (D / 4)) * 4;
-      if (ScStage<D>::FULL || f < ScStage<D>::NF) *reinterpret_cast<f32x4*>(&tab[b][row * P + col]) = st[i];
-    }
-  };
+  f32x4 st[Stage::LV];
+  auto gload = [&](int64_t c) { Stage::gload(st, table, rows, c, tid); };
+  auto swrite = [&](int b) { Stage::swrite(tab[b], st, tid); };
   gload(c_begin);
   swrite(0);
   if (c_begin + 1 < c_end) gload(c_begin + 1);
@@ -501,7 +466,7 @@ __global__ __launch_bounds__(256, 2) void score_rot_kernel(const float* __restri
         for (int s4 = 0; s4 < 4; ++s4) {
           const int step = (g * QN + q) * 4 + s4;
 #pragma unroll
-          for (int ut = 0; ut < 2; ++ut) acc[ut] = mfma32(hf[ut][g][q][s4], bt[s4], acc[ut]);
+          for (int ut = 0; ut < 2; ++ut) acc[ut] = mfma32(hf[ut][g * QN + q][s4], bt[s4], acc[ut]);
           if (inter && step % EVERY == 0) {
 #pragma unroll
             for (int e = 0; e < PER; ++e) store_reg(r1, r2, k - 1, (step / EVERY) * PER + e, true);
@@ -570,32 +535,19 @@ __global__ __launch_bounds__(256, 2) void score_rot_kernel(const float* __restri
 int gr_score_launch(const float* h, int64_t B, int32_t d, const float* table, int64_t rows,
                     float* logits, int64_t ld, hipStream_t st) {
   using namespace gr;
-  if (d != 16 && d != 32 && d != 64 && d != 128) return GR_ERR_UNSUPPORTED;
-  if (!aligned16(h) || !aligned16(table) || (reinterpret_cast<uintptr_t>(logits) & 3))
+  // (no message: the caller falls back to the general product for these)
+  if (!sc_d_ok(d) || !aligned16(h) || !aligned16(table) || (reinterpret_cast<uintptr_t>(logits) & 3))
     return GR_ERR_UNSUPPORTED;
   if (B == 0 || rows == 0) return GR_OK;
   if (ld < rows || 256LL * ld * 4 >= (1LL << 31))
     return fail(GR_ERR_UNSUPPORTED, "gr_score_f32: row stride outside [rows, 2^21)");
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-      cus = 256;
-  }
   // calls of <= 128 users (the reference's eval batch, evaluate.py:13): the direct kernel with one
   // 32-user tile per wave (128 users per workgroup), every wave busy
   const bool ut1 = B <= 128;
   const int64_t ublocks = ut1 ? 1 : (B + 255) / 256;
   const int64_t chunks = (rows + SC_CHUNK - 1) / SC_CHUNK;
   // direct / rotated kernels: two workgroups per CU; the ring kernel: one
-  auto slices_for = [&](int per_cu) {
-    // all workgroups resident at once: rounded down (rounding up put the last few in a second round)
-    int64_t sl = per_cu * cus / ublocks;
-    if (sl > chunks) sl = chunks;
-    return sl < 1 ? (int64_t)1 : sl;
-  };
-  const int64_t sl2 = slices_for(2);
+  const int64_t sl2 = sc_slices(2, ublocks, chunks);
   if (ublocks * sl2 > 0x7fffffffLL) return fail(GR_ERR_UNSUPPORTED, "gr_score_f32: grid too large");
   const dim3 g2((unsigned)(ublocks * sl2)), blk(256);
   // An XCD's workgroups share catalog slices across the user blocks (each table chunk read from
@@ -610,40 +562,30 @@ int gr_score_launch(const float* h, int64_t B, int32_t d, const float* table, in
   // lines (B 2048: 593 vs 393 us) and the rotated whole-line kernel runs (412 us;
   // profiles/r04/ab_predict_contiguous.txt), or at d = 128 (where the rotated form spills) the ring.
   const bool fits_mall = (double)B * (double)ld * 4.0 <= 160e6;
-#define GR_SC_DIRECT(DD, NTS)                                                                             \
-  if (ut1)                                                                                                \
-    hipLaunchKernelGGL((score_direct_kernel<DD, NTS, 1>), g2, blk, 0, st, h, B, table, rows, logits, ld, \
-                       (int)ublocks, (int)sl2, smaj);                                                     \
-  else                                                                                                    \
-    hipLaunchKernelGGL((score_direct_kernel<DD, NTS, 2>), g2, blk, 0, st, h, B, table, rows, logits, ld, \
-                       (int)ublocks, (int)sl2, smaj)
-#define GR_SC_SWITCH(M, ...)            \
-  switch (d) {                          \
-    case 16: M(16, __VA_ARGS__); break; \
-    case 32: M(32, __VA_ARGS__); break; \
-    case 64: M(64, __VA_ARGS__); break; \
-    default: M(128, __VA_ARGS__); break; \
-  }
-  if (lines_aligned) {
-    GR_SC_SWITCH(GR_SC_DIRECT, true)
-    return check_launch("gr_score_f32 (direct)");
-  }
-  if (fits_mall) {   // cached stores: L2 / the Infinity Cache merge the two halves of each line
-    GR_SC_SWITCH(GR_SC_DIRECT, false)
-    return check_launch("gr_score_f32 (direct, cached stores)");
-  }
-#undef GR_SC_DIRECT
-#undef GR_SC_SWITCH
-  switch (d) {   // rotated whole-line stores
-    case 16: hipLaunchKernelGGL((score_rot_kernel<16, true>), g2, blk, 0, st, h, B, table, rows, logits, ld, (int)ublocks, (int)sl2, smaj); break;
-    case 32: hipLaunchKernelGGL((score_rot_kernel<32, true>), g2, blk, 0, st, h, B, table, rows, logits, ld, (int)ublocks, (int)sl2, smaj); break;
-    case 64: hipLaunchKernelGGL((score_rot_kernel<64, true>), g2, blk, 0, st, h, B, table, rows, logits, ld, (int)ublocks, (int)sl2, smaj); break;
-    default: {
-      const int64_t sl1 = slices_for(1);
-      hipLaunchKernelGGL(score_kernel<128>, dim3((unsigned)(ublocks * sl1)), dim3(512), 0, st, h, B, table, rows,
+  return sc_dispatch_d(d, [&](auto dd) {
+    constexpr int D = decltype(dd)::value;
+    auto direct = [&](auto nts, const char* what) {
+      constexpr bool NTS = decltype(nts)::value;
+      if (ut1)
+        hipLaunchKernelGGL((score_direct_kernel<D, NTS, 1>), g2, blk, 0, st, h, B, table, rows, logits, ld,
+                           (int)ublocks, (int)sl2, smaj);
+      else
+        hipLaunchKernelGGL((score_direct_kernel<D, NTS, 2>), g2, blk, 0, st, h, B, table, rows, logits, ld,
+                           (int)ublocks, (int)sl2, smaj);
+      return check_launch(what);
+    };
+    if (lines_aligned) return direct(std::true_type{}, "gr_score_f32 (direct)");
+    // cached stores: L2 / the Infinity Cache merge the two halves of each line
+    if (fits_mall) return direct(std::false_type{}, "gr_score_f32 (direct, cached stores)");
+    if constexpr (D == 128) {
+      const int64_t sl1 = sc_slices(1, ublocks, chunks);
+      hipLaunchKernelGGL(score_kernel<D>, dim3((unsigned)(ublocks * sl1)), dim3(512), 0, st, h, B, table, rows,
                          logits, ld, (int)ublocks, (int)sl1);
       return check_launch("gr_score_f32 (ring)");
+    } else {   // rotated whole-line stores
+      hipLaunchKernelGGL((score_rot_kernel<D, true>), g2, blk, 0, st, h, B, table, rows, logits, ld, (int)ublocks,
+                         (int)sl2, smaj);
+      return check_launch("gr_score_f32 (rotated lines)");
     }
-  }
-  return check_launch("gr_score_f32 (rotated lines)");
+  });
 }

@@ -4,7 +4,7 @@
 // column) — without writing the [B, rows] logits (4 MB per user at 1M items) and without reading
 // them back.
 //
-// Every logit is the scoring kernel's exact fp32 chain (score.hip, gr_common.h sc_feat): step s of
+// Every logit is the scoring kernel's exact fp32 chain (score_chain.h, the definition): step s of
 // float4 group gq takes feature 8 gq + s (lane half 0), then 8 gq + 4 + s (lane half 1).  Here the
 // operands are swapped — table rows are the MFMA A operand and users the B operand — so the
 // accumulator holds S^T[item][user]: lane (r, h) of user tile ut owns user 64w + 32ut + r and
@@ -22,7 +22,7 @@
 #include <cmath>
 #include <cstring>
 
-#include "gr_common.h"
+#include "score_chain.h"
 #include "topk_list.h"
 
 namespace gr {
@@ -38,10 +38,10 @@ __global__ __launch_bounds__(256, 2) void score_topk_kernel(
     const float* __restrict__ h, int64_t B, const float* __restrict__ table, int64_t rows,
     const float* __restrict__ thr, int mask_col0, float* __restrict__ cv, unsigned* __restrict__ cpart,
     int64_t seg_stride, int ublocks, int slices) {
-  constexpr int NQ = D / 8;                  // float4 feature groups per lane (gr_common.h sc_feat)
-  constexpr int P = D + 4;
-  constexpr int LV = TK_CHUNK * D / 4 / 256;
-  static_assert(LV >= 1 && TK_CHUNK * D / 4 % 256 == 0, "chunk staging assumes d % 16 == 0");
+  constexpr int NQ = D / 8;                  // float4 feature groups per lane (score_chain.h)
+  using Stage = ScStage<D, TK_CHUNK>;
+  constexpr int P = Stage::P, LV = Stage::LV;
+  static_assert(Stage::FULL, "chunk staging assumes d % 16 == 0");
   __shared__ __attribute__((aligned(16))) float tab[2][TK_CHUNK * P];
   const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, hh = lane >> 5;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -54,20 +54,14 @@ __global__ __launch_bounds__(256, 2) void score_topk_kernel(
   // B operand: the users (lane r = user), as in the scoring kernel's A operand
   f32x4 hf[NQ];
   const int64_t u = u0 + r;
-  {
-    const int64_t uc = u < B ? u : B - 1;
-#pragma unroll
-    for (int gq = 0; gq < NQ; ++gq) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(h + uc * D + sc_feat(gq, hh));
-      hf[gq] = u < B ? v : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-  }
+  sc_load_user<D>(hf, h, u, B, hh);
   const float th = thr ? thr[u < B ? u : B - 1] : 0.f;
   int cgt = 0;
 
   f32x4 st[LV];
   // chunk c through a buffer resource over its own rows (base and size scalar): float4 f at byte
-  // 16 f, rows past the catalog read as zero (masked below) -- no 64-bit address or clamp per load
+  // 16 f (score_chain.h's slot map), rows past the catalog read as zero (masked below) -- no 64-bit
+  // address or clamp per load
   auto gload = [&](int64_t c) {
     const int64_t left = (rows - c * TK_CHUNK) * D * 4;
     const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(table + c * TK_CHUNK * D), 0,
@@ -77,13 +71,7 @@ __global__ __launch_bounds__(256, 2) void score_topk_kernel(
     for (int i = 0; i < LV; ++i)
       st[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, 16 * (tid + 256 * i), 0, 0));
   };
-  auto swrite = [&](int b) {
-#pragma unroll
-    for (int i = 0; i < LV; ++i) {
-      const int f = tid + 256 * i, row = f / (D / 4), col = (f % (D / 4)) * 4;
-      *reinterpret_cast<f32x4*>(&tab[b][row * P + col]) = st[i];
-    }
-  };
+  auto swrite = [&](int b) { Stage::swrite(tab[b], st, tid); };
   if (v_begin < v_end) {
     gload(v_begin);
     swrite(0);
@@ -94,28 +82,14 @@ __global__ __launch_bounds__(256, 2) void score_topk_kernel(
   for (int64_t vc = v_begin; vc < v_end; ++vc) {
     if (vc + 1 < v_end) gload(vc + 1);
     f32x16 acc[2];
-#pragma unroll
-    for (int it = 0; it < 2; ++it)
-#pragma unroll
-      for (int v = 0; v < 16; ++v) acc[it][v] = 0.f;
-    const float* tb = &tab[buf][r * P + 4 * hh];
-#pragma unroll
-    for (int gq = 0; gq < NQ; ++gq) {
-      f32x4 bt[2];
-#pragma unroll
-      for (int it = 0; it < 2; ++it) bt[it] = *reinterpret_cast<const f32x4*>(tb + it * 32 * P + 8 * gq);
-#pragma unroll
-      for (int s4 = 0; s4 < 4; ++s4)
-#pragma unroll
-        for (int it = 0; it < 2; ++it) acc[it] = mfma32(bt[it][s4], hf[gq][s4], acc[it]);
-    }
+    sc_chunk_chain<D, 2, true>(acc, hf, &tab[buf][r * P + 4 * hh]);
     const int c0 = (int)(vc * TK_CHUNK);
     if (c0 + TK_CHUNK > rows || (mask_col0 && c0 == 0)) {   // catalog ends: masks
 #pragma unroll
       for (int it = 0; it < 2; ++it)
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
-          const int col = c0 + 32 * it + (v & 3) + 8 * (v >> 2) + 4 * hh;
+          const int col = c0 + 32 * it + mfma32_row(v, hh);
           if (mask_col0 && col == 0) acc[it][v] = TK_MASK;
           if (col >= rows) acc[it][v] = __int_as_float(0x7fc00000);   // NaN: fails every test
         }
@@ -282,9 +256,9 @@ __global__ __launch_bounds__(256, 2) void topk_select_kernel(const float* __rest
   TopList<KC> best;
   best.init();
   // Re-scoring on the VALU: one lane per row (two tiles per wave pass), each logit as the fmaf chain
-  // the MFMA evaluates (v_mfma_f32_32x32x2_f32 is an exact fp32 fma chain: per float4 group gq and
-  // element s, the lane-half-0 feature 8 gq + s, then the lane-half-1 feature 8 gq + 4 + s) --
-  // bitwise the tile pass's logit, at 1/8 of the MFMA tile's work.
+  // the MFMA evaluates, in the order score_chain.h defines (v_mfma_f32_32x32x2_f32 is an exact fp32
+  // fma chain: per float4 group gq and element s, the lane-half-0 feature 8 gq + s, then the
+  // lane-half-1 feature 8 gq + 4 + s) -- bitwise the tile pass's logit, at 1/8 of the MFMA tile's work.
   for (int64_t b0 = 0; b0 < (slow ? T : 1); b0 += 256) {
     if (slow) {
       __syncthreads();
@@ -337,17 +311,6 @@ __global__ __launch_bounds__(256, 2) void topk_select_kernel(const float* __rest
   });
 }
 
-static int cu_count() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-      cus = 256;
-  }
-  return cus;
-}
-
 static int kc_for(int k) { return k <= 4 ? 4 : k <= 10 ? 10 : 16; }
 
 // Launch plan and workspace: user blocks of 128 (one 32-user tile per wave), catalog slices sized
@@ -364,9 +327,7 @@ static TileWs tile_ws(int64_t B, int64_t rows, int d) {
   // floor: ublocks x slices stays within the two resident workgroups per CU (rounding up put the
   // last few workgroups in a second round: 3,000 users = 24 user blocks x 22 slices = 528 > 512,
   // 1161 vs 831 us on a 125k-row shard, profiles/r05/ab_topk_split.txt)
-  int64_t sl = 2 * cu_count() / w.ublocks;
-  if (sl > w.chunks) sl = w.chunks;
-  w.slices = sl < 1 ? 1 : sl;
+  w.slices = sc_slices(2, w.ublocks, w.chunks);
   // tile maxima per user: 32-row tiles, or 16-row half tiles -- half the rows the select kernel
   // re-scores (~11 tiles x 16 rows x 4d bytes per user) for twice the maxima, written once and read
   // twice (2 x 4 x 3 bytes more per chunk and user): half tiles where that nets (a C5 shard: 165 ->
@@ -399,18 +360,6 @@ static int run_topk(const TileWs& tw, hipStream_t st, const float* h, int64_t B,
   return check_launch("gr_score_topk_f32 (select)");
 }
 
-template <int KC>
-static int run_topk_d(int d, const TileWs& tw, hipStream_t st, const float* h, int64_t B, const float* table,
-                      int64_t rows, const float* thr, int mask_col0, int k, int64_t id_offset, float* tmax,
-                      unsigned* cpart, unsigned long long* cnt, float* vals_out, int64_t* ids_out) {
-  switch (d) {
-    case 16: return run_topk<16, KC>(tw, st, h, B, table, rows, thr, mask_col0, k, id_offset, tmax, cpart, cnt, vals_out, ids_out);
-    case 32: return run_topk<32, KC>(tw, st, h, B, table, rows, thr, mask_col0, k, id_offset, tmax, cpart, cnt, vals_out, ids_out);
-    case 64: return run_topk<64, KC>(tw, st, h, B, table, rows, thr, mask_col0, k, id_offset, tmax, cpart, cnt, vals_out, ids_out);
-    default: return run_topk<128, KC>(tw, st, h, B, table, rows, thr, mask_col0, k, id_offset, tmax, cpart, cnt, vals_out, ids_out);
-  }
-}
-
 }  // namespace gr
 
 extern "C" size_t gr_score_topk_workspace_bytes(int64_t B, int32_t d, int64_t rows, int32_t k) {
@@ -430,12 +379,11 @@ extern "C" int gr_score_topk_f32(const float* h, int64_t B, int32_t d, const flo
   if (!h || !table || !vals_out || !ids_out) return fail(GR_ERR_ARG, "gr_score_topk_f32: null pointer");
   if ((thresholds == nullptr) != (counts_out == nullptr))
     return fail(GR_ERR_ARG, "gr_score_topk_f32: thresholds and counts_out go together");
-  if (d != 16 && d != 32 && d != 64 && d != 128)
-    return fail(GR_ERR_UNSUPPORTED, "gr_score_topk_f32: d must be 16, 32, 64 or 128");
+  if (int rc = sc_check_d("gr_score_topk_f32", d)) return rc;
   if (k > 16) return fail(GR_ERR_UNSUPPORTED, "gr_score_topk_f32: k > 16");
   if (rows >= (1LL << 31) - 4096) return fail(GR_ERR_UNSUPPORTED, "gr_score_topk_f32: rows >= 2^31");
   if (B > 65535) return fail(GR_ERR_UNSUPPORTED, "gr_score_topk_f32: B > 65535");
-  if (!aligned16(h) || !aligned16(table)) return fail(GR_ERR_ARG, "gr_score_topk_f32: h / table not 16-byte aligned");
+  if (int rc = sc_check_aligned("gr_score_topk_f32", h, table)) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (rows == 0) {   // nothing to rank: every entry is padding
     if (counts_out && gr_fill32_launch(counts_out, 0u, B * 2, st) != GR_OK)
@@ -458,9 +406,16 @@ extern "C" int gr_score_topk_f32(const float* h, int64_t B, int32_t d, const flo
   auto* tmax = reinterpret_cast<float*>(base);
   auto* cpart = reinterpret_cast<unsigned*>(base + tw.tmax);
   auto* cnt = reinterpret_cast<unsigned long long*>(counts_out);
-  switch (kc_for(k)) {
-    case 4: return run_topk_d<4>(d, tw, st, h, B, table, rows, thresholds, mask_col0, k, id_offset, tmax, cpart, cnt, vals_out, ids_out);
-    case 10: return run_topk_d<10>(d, tw, st, h, B, table, rows, thresholds, mask_col0, k, id_offset, tmax, cpart, cnt, vals_out, ids_out);
-    default: return run_topk_d<16>(d, tw, st, h, B, table, rows, thresholds, mask_col0, k, id_offset, tmax, cpart, cnt, vals_out, ids_out);
-  }
+  return sc_dispatch_d(d, [&](auto dd) {
+    constexpr int D = decltype(dd)::value;
+    auto run = [&](auto kc) {
+      return run_topk<D, decltype(kc)::value>(tw, st, h, B, table, rows, thresholds, mask_col0, k, id_offset, tmax,
+                                              cpart, cnt, vals_out, ids_out);
+    };
+    switch (kc_for(k)) {
+      case 4: return run(std::integral_constant<int, 4>{});
+      case 10: return run(std::integral_constant<int, 10>{});
+      default: return run(std::integral_constant<int, 16>{});
+    }
+  });
 }

@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 
 
 @pytest.mark.parametrize("B,d,rows", [(300, 64, 10001), (64, 128, 5000), (257, 32, 1000), (1, 64, 70),
-                                      (70, 64, 64)])
+                                      (70, 64, 64), (33, 16, 65)])
 def test_pairs_and_count_equal_materialised_logits(B, d, rows, dev):
     from gr_amd import ops
     g = torch.Generator().manual_seed(B * d + rows)
