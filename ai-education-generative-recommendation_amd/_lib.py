@@ -44,6 +44,19 @@ class SasrecTrainBufs(ctypes.Structure):
     _fields_ = [(f, _vp) for f in ("xin", "hs", "qkv", "prob", "os", "x1", "fs", "zs", "us", "xl", "g_vec")]
 
 
+GR_TIGER_MAX_LAYERS = 4
+
+
+class TigerParams(ctypes.Structure):
+    """Mirror of ``gr_tiger_params`` (include/gr_amd.h)."""
+    _fields_ = [(f, _i32) for f in ("vocab", "d_model", "d_kv", "n_heads", "d_ff", "n_enc", "n_dec", "n_buckets",
+                                    "pad_id", "eos_id", "fill_id", "reserved")] + \
+               [("eps", _f32), ("lm_scale", _f32)] + \
+               [(f, _vp) for f in ("shared", "lm_head", "enc_rel", "dec_rel", "enc_final_ln", "dec_final_ln",
+                                   "enc_bucket", "dec_bucket")] + \
+               [("enc", (_vp * 8) * GR_TIGER_MAX_LAYERS), ("dec", (_vp * 13) * GR_TIGER_MAX_LAYERS)]
+
+
 # (name, restype, argtypes) for every entry point of include/gr_amd.h
 SIGNATURES = {
     "gr_version": (ctypes.c_char_p, []),
@@ -132,6 +145,10 @@ SIGNATURES = {
     "gr_kmeans_form": (_i32, [_i64, _i32, _i32]),
     "gr_kmeans_f32": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, ctypes.c_uint64, _i32, _i32, ctypes.c_double,
                                      _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gr_tiger_workspace_bytes": (_sz, [ctypes.POINTER(TigerParams), _i64, _i32, _i32, _i32]),
+    "gr_tiger_generate_f32": (ctypes.c_int, [ctypes.POINTER(TigerParams), _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp,
+                                             _vp, _vp, _vp, _sz, _vp]),
+    "gr_beam_hits_i64": (ctypes.c_int, [_vp, _i64, _i32, _i32, _i64, _vp, _i32, _vp, _vp]),
 }
 
 _lib = None

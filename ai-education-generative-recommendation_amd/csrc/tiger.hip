@@ -1,0 +1,737 @@
+// TIGER generative retrieval (include/gr_amd.h: gr_tiger_generate_f32, gr_beam_hits_i64).
+//
+// Two launches, one workgroup per user in each:
+//   tiger_encoder_kernel  T5 encoder over the user's S tokens with the [S, d_model] activations in
+//                         LDS and the weights streamed from L2 (the whole model is under 1 MB); the
+//                         relative bias is expanded once into an [H, 2S-1] LDS table; the kernel ends
+//                         by projecting every decoder layer's cross-attention K and V, once per user.
+//   tiger_search_kernel   all max_length - 1 decode steps of the beam search in one loop: the decoder
+//                         blocks on the running beams' newest token, lm_head, fp32 log-softmax, the
+//                         selection of the 2 * num_beams continuations and the running / finished
+//                         bookkeeping of transformers' _beam_search, all in LDS.  Self-attention K/V
+//                         of (layer, position, beam) stay where they were written: a beam carries
+//                         the slot of each of its ancestors, so the library's cache reorder between
+//                         steps is a copy of <= 8 small integers per beam.
+// Every product is an fp32 fma chain over k in order; nothing is approximated.
+#include <atomic>
+
+#include "gr_common.h"
+
+namespace gr {
+namespace {
+
+// One workgroup per user owns a compute unit's LDS, so its waves are all the latency hiding there is:
+// the search kernel runs 16 of them; the encoder 8, which is what its per-wave probability rows leave
+// room for next to S = 128 rows of activations.
+constexpr int TG_ENC_THREADS = 512, TG_SRCH_THREADS = 1024;
+#define TG_THREADS ((int)blockDim.x)
+#define TG_WAVES ((int)blockDim.x >> 6)
+constexpr int TG_MAX_S = 128, TG_MAX_BEAMS = 32, TG_MAX_V = 128, TG_MAX_T = 8;
+constexpr float TG_NEG = -1.0e9f;
+constexpr int64_t TG_MAX_USERS = 1 << 21;   // one workgroup of 1024 threads each, under HIP's 2^32 threads per launch
+// Makes a uniform value opaque to the optimiser at this point: what is derived from it is recomputed
+// after it (a few scalar operations) instead of being hoisted out of the surrounding loop and held in
+// scalar registers across it.
+#define TG_OPAQUE(x) asm volatile("" : "+s"(x))
+constexpr int TG_SRCH_STATE = 2048;   // floats of LDS the search kernel's small state takes
+
+enum { E_LN0, E_Q, E_K, E_V, E_O, E_LN1, E_WI, E_WO };
+enum { D_LN0, D_Q, D_K, D_V, D_O, D_LN1, D_CQ, D_CK, D_CV, D_CO, D_LN2, D_WI, D_WO };
+
+// out[r * ldo + n] (op)= sum_k in[r * ldi + k] * W[n * K + k] for r < rows, n < N.  K % 4 == 0, W 16-byte
+// aligned.  MODE 0: store, 1: add into out (the residual), 2: store relu.  One item = one column and
+// four rows: the lanes of a wave share the rows (LDS broadcast) and differ in the weight row.
+template <int MODE>
+__device__ __forceinline__ void tg_gemm(float* out, int ldo, const float* in, int ldi,
+                                        const float* __restrict__ W, int N, int K, int rows) {
+  constexpr int RB = 4;
+  const int nrb = (rows + RB - 1) / RB;
+  for (int it = threadIdx.x; it < N * nrb; it += TG_THREADS) {
+    const int n = it % N, r0 = (it / N) * RB;
+    float acc[RB] = {0.f, 0.f, 0.f, 0.f};
+    const float4* w4 = reinterpret_cast<const float4*>(W + (size_t)n * K);
+    const float* xr[RB];
+#pragma unroll
+    for (int i = 0; i < RB; ++i) xr[i] = in + (size_t)min(r0 + i, rows - 1) * ldi;
+    for (int k = 0; k < K; k += 4) {
+      const float4 w = w4[k >> 2];
+#pragma unroll
+      for (int i = 0; i < RB; ++i) {
+        float a = acc[i];
+        a = fmaf(xr[i][k], w.x, a);
+        a = fmaf(xr[i][k + 1], w.y, a);
+        a = fmaf(xr[i][k + 2], w.z, a);
+        a = fmaf(xr[i][k + 3], w.w, a);
+        acc[i] = a;
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < RB; ++i) {
+      if (r0 + i < rows) {
+        float* o = out + (size_t)(r0 + i) * ldo + n;
+        if (MODE == 0) *o = acc[i];
+        else if (MODE == 1) *o += acc[i];
+        else *o = fmaxf(acc[i], 0.f);
+      }
+    }
+  }
+}
+
+// T5LayerNorm of rows [rows, D] (D <= 64): out = w * (x * rsqrt(mean(x^2) + eps)) * scale; a wave per row.
+__device__ __forceinline__ void tg_rmsnorm(float* out, const float* x, const float* __restrict__ w, int rows,
+                                           int D, float eps, float scale) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  for (int r = wave; r < rows; r += TG_WAVES) {
+    const float v = lane < D ? x[r * D + lane] : 0.f;
+    const float ms = wave_sum(v * v) / (float)D;
+    if (lane < D) out[r * D + lane] = w[lane] * (v * rsqrtf(ms + eps)) * scale;
+  }
+}
+
+__device__ __forceinline__ int tg_token(int64_t id, int vocab) {
+  return (int)(id < 0 ? 0 : (id >= vocab ? vocab - 1 : id));
+}
+
+// Sum over the 64 / dkv lane groups that share a channel (lane % dkv): offsets dkv .. 32.
+__device__ __forceinline__ float tg_group_sum(float v, int dkv) {
+  for (int o = dkv; o < 64; o <<= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+#define TG_ENC_PTRS \
+  const int inner = H * dkv, dkp = dkv + 1; \
+  const EncLayout L = enc_layout(S, D, inner, dkv, H, dff, TG_ENC_THREADS / 64); \
+  float* x = lds + L.x; \
+  float* xn = lds + L.xn; \
+  float* ao = lds + L.ao; \
+  float* hq = lds + L.hb; \
+  float* hk = hq + S * dkp; \
+  float* hv = hk + S * dkp; \
+  float* bias = lds + L.bias; \
+  float* prow = lds + L.prow; \
+  int* kmask = reinterpret_cast<int*>(lds + L.mask); \
+  (void)x; (void)xn; (void)ao; (void)hq; (void)hk; (void)hv; (void)bias; (void)prow; (void)kmask; (void)dkp;
+
+struct EncLayout {
+  int x, xn, ao, hb, bias, prow, mask, total;   // float offsets
+  int hb_floats;
+};
+
+__host__ __device__ inline EncLayout enc_layout(int S, int D, int inner, int dkv, int H, int dff, int waves) {
+  EncLayout L;
+  const int dkp = dkv + 1;
+  L.x = 0;
+  L.xn = L.x + S * D;
+  L.ao = L.xn + S * D;
+  // ao | q k v of one head; the same floats hold the feed-forward's hidden rows, a tile of rows at a time
+  int region = S * inner + 3 * S * dkp;
+  if (region < dff) region = dff;
+  L.hb = L.ao + S * inner;
+  L.hb_floats = region;
+  L.bias = L.ao + region;
+  L.prow = L.bias + H * (2 * S - 1);
+  L.mask = L.prow + waves * S;
+  L.total = L.mask + S;
+  return L;
+}
+
+__global__ __launch_bounds__(TG_ENC_THREADS) void tiger_encoder_kernel(gr_tiger_params p, const int64_t* __restrict__ ids,
+                                                                   const int64_t* __restrict__ amask, int S,
+                                                                   float* __restrict__ cross, float* __restrict__ enc_out) {
+  extern __shared__ __align__(16) float lds[];
+  int D = p.d_model, dkv = p.d_kv, H = p.n_heads, dff = p.d_ff;
+
+  // The layers' weight pointers go through LDS: read where they are used, they do not stay in
+  // scalar registers across the kernel (the argument struct holds 80 of them).
+  __shared__ const float* wtab[GR_TIGER_MAX_LAYERS * 13];
+  const int64_t u = blockIdx.x;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+
+  __shared__ int cint[2];
+  __shared__ float ceps;
+  for (int e = tid; e < p.n_enc * 8; e += TG_THREADS) wtab[e] = p.enc[e / 8][e % 8];
+  for (int e = tid; e < p.n_dec * 2; e += TG_THREADS)
+    wtab[GR_TIGER_MAX_LAYERS * 8 + e] = p.dec[e / 2][e % 2 ? D_CV : D_CK];
+  if (tid == 0) {
+    wtab[GR_TIGER_MAX_LAYERS * 8 + 8] = p.enc_final_ln;
+    cint[0] = p.n_enc;
+    cint[1] = p.n_dec;
+    ceps = p.eps;
+  }
+  {
+  TG_ENC_PTRS
+  for (int e = tid; e < S * D; e += TG_THREADS) {
+    const int tok = tg_token(ids[u * S + e / D], p.vocab);
+    x[e] = p.shared[(size_t)tok * D + e % D];
+  }
+  for (int j = tid; j < S; j += TG_THREADS) kmask[j] = amask ? (amask[u * S + j] != 0) : 1;
+  for (int e = tid; e < H * (2 * S - 1); e += TG_THREADS) {
+    const int h = e / (2 * S - 1), r = e % (2 * S - 1) - (S - 1);   // r = key - query
+    bias[e] = p.enc_rel[p.enc_bucket[r + 127] * H + h];
+  }
+  }
+  __syncthreads();
+
+  for (int l = 0; l < cint[0]; ++l) {
+    TG_OPAQUE(D); TG_OPAQUE(dkv); TG_OPAQUE(H); TG_OPAQUE(dff); TG_OPAQUE(S);
+    TG_ENC_PTRS
+    const float eps = ceps;
+    const float* const* W = wtab + l * 8;
+    tg_rmsnorm(xn, x, W[E_LN0], S, D, eps, 1.f);
+    __syncthreads();
+    for (int h = 0; h < H; ++h) {
+      tg_gemm<0>(hq, dkp, xn, D, W[E_Q] + (size_t)h * dkv * D, dkv, D, S);
+      tg_gemm<0>(hk, dkp, xn, D, W[E_K] + (size_t)h * dkv * D, dkv, D, S);
+      tg_gemm<0>(hv, dkp, xn, D, W[E_V] + (size_t)h * dkv * D, dkv, D, S);
+      __syncthreads();
+      const float* bh = bias + h * (2 * S - 1) + (S - 1);
+      for (int i0 = 0; i0 < S; i0 += TG_WAVES) {
+        const int i = i0 + wave;
+        float* pr = prow + wave * S;
+        if (i < S) {
+          float s[2], mx = -INFINITY;
+#pragma unroll
+          for (int t = 0; t < 2; ++t) {
+            const int j = lane + 64 * t;
+            s[t] = -INFINITY;
+            if (j < S && kmask[j]) {
+              float a = 0.f;
+              for (int c = 0; c < dkv; ++c) a = fmaf(hq[i * dkp + c], hk[j * dkp + c], a);
+              s[t] = a + bh[j - i];
+            }
+            mx = fmaxf(mx, s[t]);
+          }
+          mx = wave_max(mx);
+          float sum = 0.f;
+#pragma unroll
+          for (int t = 0; t < 2; ++t) {
+            s[t] = (s[t] == -INFINITY) ? 0.f : expf(s[t] - mx);
+            sum += s[t];
+          }
+          sum = wave_sum(sum);
+#pragma unroll
+          for (int t = 0; t < 2; ++t) {
+            const int j = lane + 64 * t;
+            if (j < S) pr[j] = s[t] / sum;
+          }
+        }
+        __syncthreads();
+        if (i < S) {
+          const int c = lane % dkv, g = lane / dkv, G = 64 / dkv;
+          float a = 0.f;
+          for (int j = g; j < S; j += G) a = fmaf(pr[j], hv[j * dkp + c], a);
+          a = tg_group_sum(a, dkv);
+          if (lane < dkv) ao[i * inner + h * dkv + c] = a;
+        }
+        __syncthreads();
+      }
+    }
+    tg_gemm<1>(x, D, ao, inner, W[E_O], D, inner, S);
+    __syncthreads();
+    tg_rmsnorm(xn, x, W[E_LN1], S, D, eps, 1.f);
+    __syncthreads();
+    // feed-forward over tiles of rows: the hidden rows take the attention buffers' place
+    const int R = min(S, L.hb_floats / dff);
+    for (int r0 = 0; r0 < S; r0 += R) {
+      const int rows = min(R, S - r0);
+      tg_gemm<2>(ao, dff, xn + r0 * D, D, W[E_WI], dff, D, rows);
+      __syncthreads();
+      tg_gemm<1>(x + r0 * D, D, ao, dff, W[E_WO], D, dff, rows);
+      __syncthreads();
+    }
+  }
+  TG_OPAQUE(D); TG_OPAQUE(dkv); TG_OPAQUE(H); TG_OPAQUE(dff); TG_OPAQUE(S);
+  TG_ENC_PTRS
+  const int n_dec = cint[1];
+  tg_rmsnorm(xn, x, wtab[GR_TIGER_MAX_LAYERS * 8 + 8], S, D, ceps, 1.f);
+  __syncthreads();
+  if (enc_out)
+    for (int e = tid; e < S * D; e += TG_THREADS) enc_out[u * S * D + e] = xn[e];
+  // cross-attention K and V of every decoder layer: [n_dec][2][S][inner] per user
+  float* cu = cross + (size_t)u * n_dec * 2 * S * inner;
+  for (int l = 0; l < n_dec; ++l) {
+    tg_gemm<0>(cu + (size_t)(2 * l) * S * inner, inner, xn, D, wtab[GR_TIGER_MAX_LAYERS * 8 + 2 * l], inner, D, S);
+    tg_gemm<0>(cu + (size_t)(2 * l + 1) * S * inner, inner, xn, D, wtab[GR_TIGER_MAX_LAYERS * 8 + 2 * l + 1], inner, D,
+               S);
+  }
+}
+
+// The search kernel's LDS layout is fixed at the envelope's largest shapes (32 beams, d_model and
+// heads * d_kv 64, d_ff 256, 128 keys, 16 waves), so every sub-array's address is an immediate:
+// 88 KB per workgroup, one workgroup per compute unit.
+constexpr int SR_H = TG_SRCH_STATE, SR_XN = SR_H + 2048, SR_Q = SR_XN + 2048, SR_AO = SR_Q + 2048,
+              SR_FF = SR_AO + 2048, SR_PROW = SR_FF + 8192, SR_SATTN = SR_PROW + (TG_SRCH_THREADS / 64) * TG_MAX_S,
+              SR_DBIAS = SR_SATTN + TG_MAX_BEAMS * 8 * TG_MAX_T, SR_TOTAL = SR_DBIAS + 8 * TG_MAX_T;
+
+__global__ __launch_bounds__(TG_SRCH_THREADS) void tiger_search_kernel(gr_tiger_params p, const int64_t* __restrict__ amask,
+                                                                  int S, int nb, int T, const float* __restrict__ cross,
+                                                                  float* __restrict__ selfkv, int64_t* __restrict__ seq_out,
+                                                                  float* __restrict__ score_out,
+                                                                  float* __restrict__ step_logits) {
+  extern __shared__ __align__(16) float lds[];
+  int D = p.d_model, dkv = p.d_kv, H = p.n_heads, dff = p.d_ff, V = p.vocab;
+  float* h = lds + SR_H;
+  float* xn = lds + SR_XN;
+  float* q = lds + SR_Q;
+  float* ao = lds + SR_AO;
+  float* ff = lds + SR_FF;         // feed-forward hidden rows, then the logits / candidate scores
+  float* prow = lds + SR_PROW;
+  float* sattn = lds + SR_SATTN;   // self-attention scores of (beam, head)
+  float* dbias = lds + SR_DBIAS;   // decoder relative bias of (distance, head)
+  // the small search state sits at fixed offsets (sized for 32 beams, 8 positions, 128 keys), so that its
+  // addresses are immediates, not scalar registers
+  float* run_score = lds;
+  float* new_run_score = lds + TG_MAX_BEAMS;
+  float* fin_score = lds + 2 * TG_MAX_BEAMS;
+  float* new_fin_score = lds + 3 * TG_MAX_BEAMS;
+  float* top_val = lds + 4 * TG_MAX_BEAMS;
+  int* ist = reinterpret_cast<int*>(lds + 6 * TG_MAX_BEAMS);
+  int* top_idx = ist;
+  int* run_par = ist + 2 * TG_MAX_BEAMS;
+  int* run_tok = ist + 3 * TG_MAX_BEAMS;
+  int* fin_src = ist + 4 * TG_MAX_BEAMS;
+  int* flags = ist + 5 * TG_MAX_BEAMS;          // [0] live beams, [1] finished count, [2] stop
+  int* kmask = flags + 4;
+  int* run_seq = kmask + TG_MAX_S;
+  int* anc = run_seq + TG_MAX_BEAMS * TG_MAX_T;
+  int* fin_seq = anc + TG_MAX_BEAMS * TG_MAX_T;
+  int* tmp_run_seq = fin_seq + TG_MAX_BEAMS * TG_MAX_T;
+  int* tmp_anc = tmp_run_seq + TG_MAX_BEAMS * TG_MAX_T;
+  int* tmp_fin_seq = tmp_anc + TG_MAX_BEAMS * TG_MAX_T;
+  static_assert(11 * TG_MAX_BEAMS + 4 + TG_MAX_S + 6 * TG_MAX_BEAMS * TG_MAX_T <= TG_SRCH_STATE, "search state");
+
+  __shared__ const float* wtab[GR_TIGER_MAX_LAYERS * 13 + 3];   // as in the encoder kernel
+  const float* const* gshared = wtab + GR_TIGER_MAX_LAYERS * 13;   // shared, lm_head, decoder final norm
+  // pointers and constants that are read where they are used instead of living in scalar registers:
+  // step logits, sequences, scores, cross K/V, self K/V; eos, fill, layers; eps, lm scale
+  __shared__ void* gout[5];
+  __shared__ int cint[3];
+  __shared__ float cflt[2];
+  const int64_t u = blockIdx.x;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  for (int e = tid; e < p.n_dec * 13; e += TG_THREADS) wtab[e] = p.dec[e / 13][e % 13];
+  if (tid == 0) {
+    gout[0] = step_logits;
+    gout[1] = seq_out;
+    gout[2] = score_out;
+    gout[3] = const_cast<float*>(cross);
+    gout[4] = selfkv;
+    cint[0] = p.eos_id;
+    cint[1] = p.fill_id;
+    cint[2] = p.n_dec;
+    cflt[0] = p.eps;
+    cflt[1] = p.lm_scale;
+    wtab[GR_TIGER_MAX_LAYERS * 13] = p.shared;
+    wtab[GR_TIGER_MAX_LAYERS * 13 + 1] = p.lm_head;
+    wtab[GR_TIGER_MAX_LAYERS * 13 + 2] = p.dec_final_ln;
+  }
+  for (int e = tid; e < H * TG_MAX_T; e += TG_THREADS) dbias[e] = p.dec_rel[p.dec_bucket[e / H] * H + e % H];
+
+
+  for (int j = tid; j < S; j += TG_THREADS) kmask[j] = amask ? (amask[u * S + j] != 0) : 1;
+  for (int e = tid; e < nb * T; e += TG_THREADS) {
+    run_seq[e] = (e % T == 0) ? p.pad_id : p.fill_id;
+    fin_seq[e] = run_seq[e];
+    anc[e] = 0;
+  }
+  for (int b = tid; b < nb; b += TG_THREADS) {
+    run_score[b] = b == 0 ? 0.f : TG_NEG;
+    fin_score[b] = TG_NEG;
+  }
+  if (tid == 0) {
+    flags[0] = 1;   // at step 0 only beam 0 is live: the others carry -1e9 and V >= 2 nb candidates beat them
+    flags[1] = 0;
+    flags[2] = 0;
+  }
+  if (step_logits)
+    for (int e = tid; e < (T - 1) * nb * V; e += TG_THREADS) step_logits[(size_t)u * (T - 1) * nb * V + e] = 0.f;
+  __syncthreads();
+
+  for (int t = 0; t + 1 < T; ++t) {
+    TG_OPAQUE(D); TG_OPAQUE(dkv); TG_OPAQUE(H); TG_OPAQUE(dff); TG_OPAQUE(V);
+    TG_OPAQUE(S); TG_OPAQUE(nb); TG_OPAQUE(T);
+    const int live = flags[0];
+    for (int e = tid; e < live * D; e += TG_THREADS) {
+      const int tok = tg_token(run_seq[(e / D) * T + t], V);
+      h[e] = gshared[0][(size_t)tok * D + e % D];
+    }
+    __syncthreads();
+    for (int l = 0; l < cint[2]; ++l) {
+      TG_OPAQUE(D); TG_OPAQUE(dkv); TG_OPAQUE(H); TG_OPAQUE(dff); TG_OPAQUE(S); TG_OPAQUE(nb);
+      const int inner = H * dkv;
+      const float* const* W = wtab + l * 13;
+      const int n_dec = cint[2];
+      const float eps = cflt[0];
+      const float* cu = static_cast<const float*>(gout[3]) + (size_t)u * n_dec * 2 * S * inner;
+      // self K/V: [n_dec][2][T-1][nb][inner] per user
+      float* su = static_cast<float*>(gout[4]) + (size_t)u * n_dec * 2 * (T - 1) * nb * inner;
+      const size_t kv_stride = (size_t)(T - 1) * nb * inner;
+      float* sk = su + (size_t)(2 * l) * kv_stride;
+      float* sv = su + (size_t)(2 * l + 1) * kv_stride;
+      // self-attention over the beam's own prefix
+      tg_rmsnorm(xn, h, W[D_LN0], live, D, eps, 1.f);
+      __syncthreads();
+      tg_gemm<0>(q, inner, xn, D, W[D_Q], inner, D, live);
+      tg_gemm<0>(sk + (size_t)t * nb * inner, inner, xn, D, W[D_K], inner, D, live);
+      tg_gemm<0>(sv + (size_t)t * nb * inner, inner, xn, D, W[D_V], inner, D, live);
+      __syncthreads();
+      for (int it = tid; it < live * H; it += TG_THREADS) {
+        const int b = it / H, hd = it % H;
+        const float* qv = q + b * inner + hd * dkv;
+        float* s = sattn + it * TG_MAX_T;      // this thread's scores, then probabilities
+        float mx = -INFINITY;
+#pragma unroll 1
+        for (int pos = 0; pos <= t; ++pos) {
+          const int slot = pos == t ? b : anc[b * T + pos];
+          const float* kr = sk + ((size_t)pos * nb + slot) * inner + hd * dkv;
+          float a = 0.f;
+          for (int c = 0; c < dkv; ++c) a = fmaf(qv[c], kr[c], a);
+          a += dbias[(t - pos) * H + hd];
+          s[pos] = a;
+          mx = fmaxf(mx, a);
+        }
+        float sum = 0.f;
+#pragma unroll 1
+        for (int pos = 0; pos <= t; ++pos) {
+          const float e = expf(s[pos] - mx);
+          s[pos] = e;
+          sum += e;
+        }
+#pragma unroll 1
+        for (int pos = 0; pos <= t; ++pos) s[pos] = s[pos] / sum;
+        for (int c = 0; c < dkv; ++c) {
+          float a = 0.f;
+#pragma unroll 1
+          for (int pos = 0; pos <= t; ++pos) {
+            const int slot = pos == t ? b : anc[b * T + pos];
+            a = fmaf(s[pos], sv[((size_t)pos * nb + slot) * inner + hd * dkv + c], a);
+          }
+          ao[b * inner + hd * dkv + c] = a;
+        }
+      }
+      __syncthreads();
+      tg_gemm<1>(h, D, ao, inner, W[D_O], D, inner, live);
+      __syncthreads();
+      // cross-attention over the user's encoder keys (no position bias, padding masked)
+      tg_rmsnorm(xn, h, W[D_LN1], live, D, eps, 1.f);
+      __syncthreads();
+      tg_gemm<0>(q, inner, xn, D, W[D_CQ], inner, D, live);
+      __syncthreads();
+      const float* ck = cu + (size_t)(2 * l) * S * inner;
+      const float* cv = cu + (size_t)(2 * l + 1) * S * inner;
+      for (int it0 = 0; it0 < live * H; it0 += TG_WAVES) {
+        const int it = it0 + wave;
+        const int b = it / H, hd = it % H;
+        float* pr = prow + wave * S;
+        if (it < live * H) {
+          const float* qv = q + b * inner + hd * dkv;
+          float s[2], mx = -INFINITY;
+#pragma unroll
+          for (int k2 = 0; k2 < 2; ++k2) {
+            const int j = lane + 64 * k2;
+            s[k2] = -INFINITY;
+            if (j < S && kmask[j]) {
+              const float4* kr = reinterpret_cast<const float4*>(ck + (size_t)j * inner + hd * dkv);
+              float a = 0.f;
+              for (int c = 0; c < dkv; c += 4) {
+                const float4 kk = kr[c >> 2];
+                a = fmaf(qv[c], kk.x, a);
+                a = fmaf(qv[c + 1], kk.y, a);
+                a = fmaf(qv[c + 2], kk.z, a);
+                a = fmaf(qv[c + 3], kk.w, a);
+              }
+              s[k2] = a;
+            }
+            mx = fmaxf(mx, s[k2]);
+          }
+          mx = wave_max(mx);
+          float sum = 0.f;
+#pragma unroll
+          for (int k2 = 0; k2 < 2; ++k2) {
+            s[k2] = (s[k2] == -INFINITY) ? 0.f : expf(s[k2] - mx);
+            sum += s[k2];
+          }
+          sum = wave_sum(sum);
+#pragma unroll
+          for (int k2 = 0; k2 < 2; ++k2) {
+            const int j = lane + 64 * k2;
+            if (j < S) pr[j] = s[k2] / sum;
+          }
+        }
+        __syncthreads();
+        if (it < live * H) {
+          const int c = lane % dkv, g = lane / dkv, G = 64 / dkv;
+          float a = 0.f;
+          for (int j = g; j < S; j += G) a = fmaf(pr[j], cv[(size_t)j * inner + hd * dkv + c], a);
+          a = tg_group_sum(a, dkv);
+          if (lane < dkv) ao[b * inner + hd * dkv + c] = a;
+        }
+        __syncthreads();
+      }
+      tg_gemm<1>(h, D, ao, inner, W[D_CO], D, inner, live);
+      __syncthreads();
+      // feed-forward
+      tg_rmsnorm(xn, h, W[D_LN2], live, D, eps, 1.f);
+      __syncthreads();
+      tg_gemm<2>(ff, dff, xn, D, W[D_WI], dff, D, live);
+      __syncthreads();
+      tg_gemm<1>(h, D, ff, dff, W[D_WO], D, dff, live);
+      __syncthreads();
+    }
+    TG_OPAQUE(D); TG_OPAQUE(V); TG_OPAQUE(nb); TG_OPAQUE(T);
+    const int keep = 2 * nb;
+    // lm_head on the scaled final norm, log-softmax, plus the beam's running score
+    tg_rmsnorm(xn, h, gshared[2], live, D, cflt[0], cflt[1]);
+    __syncthreads();
+    tg_gemm<0>(ff, V, xn, D, gshared[1], V, D, live);
+    __syncthreads();
+    if (float* sl0 = static_cast<float*>(gout[0])) {
+      float* sl = sl0 + ((size_t)u * (T - 1) + t) * nb * V;
+      for (int e = tid; e < live * V; e += TG_THREADS) sl[e] = ff[e];
+      __syncthreads();   // the log-softmax below rewrites ff in place, a row per wave
+    }
+    for (int b = wave; b < live; b += TG_WAVES) {
+      float v[2], mx = -INFINITY;
+#pragma unroll
+      for (int k2 = 0; k2 < 2; ++k2) {
+        const int j = lane + 64 * k2;
+        v[k2] = j < V ? ff[b * V + j] : -INFINITY;
+        mx = fmaxf(mx, v[k2]);
+      }
+      mx = wave_max(mx);
+      float sum = 0.f;
+#pragma unroll
+      for (int k2 = 0; k2 < 2; ++k2) sum += (lane + 64 * k2 < V) ? expf(v[k2] - mx) : 0.f;
+      const float lse = logf(wave_sum(sum));
+#pragma unroll
+      for (int k2 = 0; k2 < 2; ++k2) {
+        const int j = lane + 64 * k2;
+        if (j < V) ff[b * V + j] = ((v[k2] - mx) - lse) + run_score[b];
+      }
+    }
+    for (int e = tid; e < keep; e += TG_THREADS) {
+      top_val[e] = TG_NEG;
+      top_idx[e] = 0;
+    }
+    __syncthreads();
+    // the 2 nb best of the live * V candidates, best first, equal scores by the lower flat index: a
+    // candidate's rank is the number of candidates ahead of it
+    TG_OPAQUE(V); TG_OPAQUE(nb); TG_OPAQUE(T);
+    const int N = live * V;
+    for (int i = tid; i < N; i += TG_THREADS) {
+      const float v = ff[i];
+      int cnt = 0;
+      for (int j = 0; j < N && cnt < keep; ++j) {
+        const float o = ff[j];
+        cnt += (o > v) || (o == v && j < i);
+      }
+      if (cnt < keep) {
+        top_val[cnt] = v;
+        top_idx[cnt] = i;
+      }
+    }
+    __syncthreads();
+    if (tid == 0) {
+      const bool last = t + 2 >= T;          // the continuation reaches max_length
+      int nr = 0;
+      for (int i = 0; i < keep; ++i) {
+        const int tok = top_idx[i] % V, par = top_idx[i] / V;
+        if (!(last || tok == cint[0]) && nr < nb) {
+          run_par[nr] = par;
+          run_tok[nr] = tok;
+          new_run_score[nr] = top_val[i];
+          ++nr;
+        }
+      }
+      // finished: the old list and the hits among the first nb continuations, both best first; the
+      // length-normalised score divides by the tokens generated so far
+      const int fc = flags[1];
+      const float len = (float)(t + 1);
+      int a = 0, i = 0, n = 0;
+      while (n < nb) {
+        while (i < nb && !(last || top_idx[i] % V == cint[0])) ++i;
+        const bool has_old = a < fc, has_new = i < nb;
+        if (!has_old && !has_new) break;
+        const float sn = has_new ? top_val[i] / len : 0.f;
+        if (has_old && (!has_new || fin_score[a] >= sn)) {
+          fin_src[n] = a;
+          new_fin_score[n] = fin_score[a];
+          ++a;
+        } else {
+          fin_src[n] = nb + i;
+          new_fin_score[n] = sn;
+          ++i;
+        }
+        ++n;
+      }
+      flags[1] = n;
+      flags[0] = nr;
+      // early stop (early_stopping False, length_penalty 1): every slot finished and the best running
+      // beam, normalised at its current length, no better than the worst finished one
+      int stop = last || nr == 0;
+      if (!stop && n == nb && !(new_run_score[0] / len > new_fin_score[nb - 1])) stop = 1;
+      flags[2] = stop;
+    }
+    __syncthreads();
+    TG_OPAQUE(V); TG_OPAQUE(nb); TG_OPAQUE(T);
+    const int nr = flags[0], nf = flags[1];
+    for (int e = tid; e < nb * T; e += TG_THREADS) {
+      const int b = e / T, pos = e % T;
+      if (b < nr) {
+        const int par = run_par[b];
+        tmp_run_seq[e] = pos <= t ? run_seq[par * T + pos] : (pos == t + 1 ? run_tok[b] : cint[1]);
+        tmp_anc[e] = pos < t ? anc[par * T + pos] : (pos == t ? par : 0);
+      }
+      if (b < nf) {
+        const int src = fin_src[b];
+        if (src < nb) {
+          tmp_fin_seq[e] = fin_seq[src * T + pos];
+        } else {
+          const int ci = top_idx[src - nb], par = ci / V;
+          tmp_fin_seq[e] = pos <= t ? run_seq[par * T + pos] : (pos == t + 1 ? ci % V : cint[1]);
+        }
+      }
+    }
+    __syncthreads();
+    for (int e = tid; e < nb * T; e += TG_THREADS) {
+      const int b = e / T;
+      if (b < nr) {
+        run_seq[e] = tmp_run_seq[e];
+        anc[e] = tmp_anc[e];
+      }
+      if (b < nf) fin_seq[e] = tmp_fin_seq[e];
+    }
+    for (int b = tid; b < nb; b += TG_THREADS) {
+      if (b < nr) run_score[b] = new_run_score[b];
+      if (b < nf) fin_score[b] = new_fin_score[b];
+    }
+    __syncthreads();
+    if (flags[2]) break;
+  }
+  int64_t* so = static_cast<int64_t*>(gout[1]);
+  float* co = static_cast<float*>(gout[2]);
+  for (int e = tid; e < nb * T; e += TG_THREADS) so[(size_t)u * nb * T + e] = fin_seq[e];
+  for (int b = tid; b < nb; b += TG_THREADS) co[(size_t)u * nb + b] = fin_score[b];
+}
+
+__global__ void beam_hits_kernel(const int64_t* __restrict__ preds, int64_t B, int k, int pred_len, int64_t ld,
+                                 const int64_t* __restrict__ labels, int label_len, uint8_t* __restrict__ hits) {
+  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  int found = -1;
+  for (int j = 0; j < k && found < 0; ++j) {
+    const int64_t* pr = preds + (b * k + j) * ld;
+    bool eq = true;
+    for (int c = 0; c < label_len && eq; ++c) eq = (c < pred_len ? pr[c] : 0) == labels[b * label_len + c];
+    if (eq) found = j;
+  }
+  for (int j = 0; j < k; ++j) hits[b * k + j] = j == found;
+}
+
+const char* tiger_check(const gr_tiger_params* p, int64_t B, int S, int nb, int T) {
+  if (!p) return "null params";
+  if (p->d_model != 32 && p->d_model != 64) return "d_model must be 32 or 64";
+  if (p->d_kv != 8 && p->d_kv != 16 && p->d_kv != 32) return "d_kv must be 8, 16 or 32";
+  if (p->n_heads < 1 || (p->n_heads * p->d_kv != 32 && p->n_heads * p->d_kv != 64))
+    return "num_heads * d_kv must be 32 or 64";
+  if (p->d_ff < 32 || p->d_ff > 256 || p->d_ff % 32) return "d_ff must be a multiple of 32, at most 256";
+  if (p->n_enc < 1 || p->n_enc > GR_TIGER_MAX_LAYERS) return "num_layers must be 1..4";
+  if (p->n_dec < 1 || p->n_dec > GR_TIGER_MAX_LAYERS) return "num_decoder_layers must be 1..4";
+  if (p->n_buckets != 32) return "relative_attention_num_buckets must be 32";
+  if (nb < 1 || nb > TG_MAX_BEAMS) return "num_beams must be 1..32";
+  if (p->vocab > TG_MAX_V) return "vocab_size must be at most 128";
+  if (p->vocab < 2 * nb) return "vocab_size must be at least 2 * num_beams";
+  if (S < 1 || S > TG_MAX_S) return "the history must hold 1..128 tokens";
+  if (T < 2 || T > TG_MAX_T) return "max_length must be 2..8";
+  if (B < 0 || B > TG_MAX_USERS) return "the batch must hold at most 2^21 users";
+  return nullptr;
+}
+
+size_t tiger_cross_floats(const gr_tiger_params* p, int64_t B, int S) {
+  return (size_t)B * p->n_dec * 2 * S * p->n_heads * p->d_kv;
+}
+
+size_t tiger_self_floats(const gr_tiger_params* p, int64_t B, int nb, int T) {
+  return (size_t)B * p->n_dec * 2 * (T - 1) * nb * p->n_heads * p->d_kv;
+}
+
+}  // namespace
+}  // namespace gr
+
+extern "C" size_t gr_tiger_workspace_bytes(const gr_tiger_params* p, int64_t B, int32_t S, int32_t num_beams,
+                                           int32_t max_length) {
+  if (gr::tiger_check(p, B, S, num_beams, max_length)) return 0;
+  const size_t f = gr::align_up(gr::tiger_cross_floats(p, B, S), 4) + gr::tiger_self_floats(p, B, num_beams, max_length);
+  return gr::align_up(f * sizeof(float), 16) + 16;
+}
+
+extern "C" int gr_tiger_generate_f32(const gr_tiger_params* p, const int64_t* input_ids,
+                                     const int64_t* attention_mask, int64_t B, int32_t S, int32_t num_beams,
+                                     int32_t max_length, int64_t* sequences, float* scores, float* enc_out,
+                                     float* step_logits, void* workspace, size_t workspace_bytes, void* stream) {
+  using namespace gr;
+  clear_error();
+  if (const char* why = tiger_check(p, B, S, num_beams, max_length)) {
+    const bool arg = !p || B < 0;
+    return fail(arg ? GR_ERR_ARG : GR_ERR_UNSUPPORTED, std::string("gr_tiger_generate_f32: ") + why);
+  }
+  if (p->eos_id < 0 || p->eos_id >= p->vocab || p->pad_id < 0 || p->pad_id >= p->vocab || p->fill_id < 0 ||
+      p->fill_id >= p->vocab)
+    return fail(GR_ERR_ARG, "gr_tiger_generate_f32: pad, eos and fill ids must lie in [0, vocab)");
+  const size_t need = gr_tiger_workspace_bytes(p, B, S, num_beams, max_length);
+  if (!workspace || workspace_bytes < need || !aligned16(workspace))
+    return fail(GR_ERR_WORKSPACE, "gr_tiger_generate_f32: workspace missing, misaligned or smaller than "
+                                  "gr_tiger_workspace_bytes");
+  if (!input_ids || !sequences || !scores) return fail(GR_ERR_ARG, "gr_tiger_generate_f32: null pointer");
+  bool ok = p->shared && p->lm_head && p->enc_rel && p->dec_rel && p->enc_final_ln && p->dec_final_ln &&
+            p->enc_bucket && p->dec_bucket && aligned16(p->shared) && aligned16(p->lm_head);
+  for (int l = 0; ok && l < p->n_enc; ++l)
+    for (int i = 0; i < 8; ++i) ok = ok && p->enc[l][i] && aligned16(p->enc[l][i]);
+  for (int l = 0; ok && l < p->n_dec; ++l)
+    for (int i = 0; i < 13; ++i) ok = ok && p->dec[l][i] && aligned16(p->dec[l][i]);
+  if (!ok) return fail(GR_ERR_ARG, "gr_tiger_generate_f32: a weight pointer is null or not 16-byte aligned");
+  if (B == 0) return GR_OK;
+  const int inner = p->n_heads * p->d_kv;
+  const EncLayout EL = enc_layout(S, p->d_model, inner, p->d_kv, p->n_heads, p->d_ff, TG_ENC_THREADS / 64);
+  const size_t enc_lds = (size_t)EL.total * sizeof(float), srch_lds = (size_t)SR_TOTAL * sizeof(float);
+  constexpr size_t kLdsMax = 159 * 1024;   // dynamic part; the kernels' static LDS is under 1 KB
+  if (enc_lds > kLdsMax || srch_lds > kLdsMax)
+    return fail(GR_ERR_UNSUPPORTED, "gr_tiger_generate_f32: the per-user state does not fit in LDS");
+  // the limit is a property of the kernel on the current device: raised on each device's first call
+  static std::atomic<uint64_t> lds_raised{0};
+  int devid = 0;
+  if (hipGetDevice(&devid) != hipSuccess) return fail(GR_ERR_HIP, "gr_tiger_generate_f32: no current device");
+  const uint64_t bit = 1ull << (devid & 63);
+  if (!(lds_raised.load() & bit)) {
+    const bool lds_ok =
+        hipFuncSetAttribute(reinterpret_cast<const void*>(tiger_encoder_kernel),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax) == hipSuccess &&
+        hipFuncSetAttribute(reinterpret_cast<const void*>(tiger_search_kernel),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax) == hipSuccess;
+    if (!lds_ok) return fail(GR_ERR_HIP, "gr_tiger_generate_f32: cannot raise the dynamic LDS limit");
+    lds_raised.fetch_or(bit);
+  }
+  float* cross = static_cast<float*>(workspace);
+  float* selfkv = cross + align_up(tiger_cross_floats(p, B, S), 4);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  tiger_encoder_kernel<<<dim3((unsigned)B), dim3(TG_ENC_THREADS), enc_lds, st>>>(*p, input_ids, attention_mask, S, cross,
+                                                                            enc_out);
+  if (int rc = check_launch("tiger_encoder_kernel")) return rc;
+  tiger_search_kernel<<<dim3((unsigned)B), dim3(TG_SRCH_THREADS), srch_lds, st>>>(
+      *p, attention_mask, S, num_beams, max_length, cross, selfkv, sequences, scores, step_logits);
+  return check_launch("tiger_search_kernel");
+}
+
+extern "C" int gr_beam_hits_i64(const int64_t* preds, int64_t B, int32_t k, int32_t pred_len, int64_t ld_pred,
+                                const int64_t* labels, int32_t label_len, uint8_t* hits, void* stream) {
+  using namespace gr;
+  clear_error();
+  if (B < 0 || k < 1 || pred_len < 0 || label_len < 1 || ld_pred < pred_len)
+    return fail(GR_ERR_ARG, "gr_beam_hits_i64: needs B >= 0, k >= 1, pred_len >= 0, label_len >= 1, ld_pred >= pred_len");
+  if (B >= (1ll << 31)) return fail(GR_ERR_UNSUPPORTED, "gr_beam_hits_i64: the batch must hold fewer than 2^31 users");
+  if (!preds || !labels || !hits) return fail(GR_ERR_ARG, "gr_beam_hits_i64: null pointer");
+  if (B == 0) return GR_OK;
+  beam_hits_kernel<<<dim3((unsigned)((B + 127) / 128)), dim3(128), 0, static_cast<hipStream_t>(stream)>>>(
+      preds, B, k, pred_len, ld_pred, labels, label_len, hits);
+  return check_launch("beam_hits_kernel");
+}

@@ -1634,3 +1634,197 @@ def mlp_train(x, mlp):
     for m in mlp.linears():
         params += [m.weight, m.bias]
     return _MlpTrain.apply(x.contiguous(), p, snap, *params)
+
+
+TIGER_ENVELOPE = ("d_model in {32, 64}; num_heads * d_kv in {32, 64} with d_kv in {8, 16, 32}; d_ff <= 256 and a "
+                  "multiple of 32; 1..4 layers on each side; 2 * num_beams <= vocab_size <= 128; at most 128 history "
+                  "tokens; num_beams <= 32; max_length <= 8; at most 2**21 users per call; 32 relative-attention "
+                  "buckets over distance 128; tied embeddings; feed_forward_proj 'relu'; one EOS id")
+TIGER_ENC_KEYS = ("layer.0.layer_norm", "layer.0.SelfAttention.q", "layer.0.SelfAttention.k", "layer.0.SelfAttention.v",
+                  "layer.0.SelfAttention.o", "layer.1.layer_norm", "layer.1.DenseReluDense.wi",
+                  "layer.1.DenseReluDense.wo")
+TIGER_DEC_KEYS = ("layer.0.layer_norm", "layer.0.SelfAttention.q", "layer.0.SelfAttention.k", "layer.0.SelfAttention.v",
+                  "layer.0.SelfAttention.o", "layer.1.layer_norm", "layer.1.EncDecAttention.q",
+                  "layer.1.EncDecAttention.k", "layer.1.EncDecAttention.v", "layer.1.EncDecAttention.o",
+                  "layer.2.layer_norm", "layer.2.DenseReluDense.wi", "layer.2.DenseReluDense.wo")
+TIGER_REL = "layer.0.SelfAttention.relative_attention_bias"
+
+
+def t5_relative_bucket(relative_position, bidirectional, num_buckets=32, max_distance=128):
+    """T5's bucket of a relative position (key position - query position), in the library's own
+    arithmetic (float32 log, truncation), so that the tables the kernels index are the library's."""
+    import math
+    rp = relative_position
+    buckets = torch.zeros_like(rp)
+    if bidirectional:
+        num_buckets //= 2
+        buckets = buckets + (rp > 0).to(torch.long) * num_buckets
+        rp = rp.abs()
+    else:
+        rp = -torch.min(rp, torch.zeros_like(rp))
+    max_exact = num_buckets // 2
+    large = max_exact + (torch.log(rp.float() / max_exact) / math.log(max_distance / max_exact)
+                         * (num_buckets - max_exact)).to(torch.long)
+    large = torch.min(large, torch.full_like(large, num_buckets - 1))
+    return buckets + torch.where(rp < max_exact, rp, large)
+
+
+def tiger_check_config(cfg, num_beams=None, S=None, max_length=None):
+    """Raise NotImplementedError, naming the limit, for a configuration outside the kernels' envelope."""
+    def no(msg):
+        raise NotImplementedError(f"TIGER: {msg} (the gfx950 kernels cover: {TIGER_ENVELOPE}); there is no CPU "
+                                  "fallback")
+    if cfg.get("feed_forward_proj", "relu") != "relu":
+        no(f"feed_forward_proj={cfg['feed_forward_proj']!r} is not built, only 'relu'")
+    if int(cfg.get("relative_attention_num_buckets", 32)) != 32:
+        no(f"relative_attention_num_buckets={cfg['relative_attention_num_buckets']} is not built, only 32")
+    if int(cfg.get("relative_attention_max_distance", 128)) != 128:
+        no(f"relative_attention_max_distance={cfg['relative_attention_max_distance']} is not built, only 128")
+    if cfg.get("tie_word_embeddings", True) is False:
+        no("tie_word_embeddings=False is not built: lm_head is the shared embedding")
+    eos = cfg["eos_token_id"]
+    if isinstance(eos, (list, tuple)):
+        if len(eos) != 1:
+            no("only one EOS id is supported")
+        eos = eos[0]
+    d, dkv, H, dff, V = (int(cfg[k]) for k in ("d_model", "d_kv", "num_heads", "d_ff", "vocab_size"))
+    if d not in (32, 64):
+        no(f"d_model={d} must be 32 or 64")
+    if dkv not in (8, 16, 32):
+        no(f"d_kv={dkv} must be 8, 16 or 32")
+    if H * dkv not in (32, 64):
+        no(f"num_heads * d_kv = {H * dkv} must be 32 or 64")
+    if dff > 256 or dff < 32 or dff % 32:
+        no(f"d_ff={dff} must be a multiple of 32, at most 256")
+    for k in ("num_layers", "num_decoder_layers"):
+        if not 1 <= int(cfg[k]) <= 4:
+            no(f"{k}={cfg[k]} must be 1..4")
+    if V > 128:
+        no(f"vocab_size={V} must be at most 128")
+    if not (0 <= int(eos) < V and 0 <= int(cfg["pad_token_id"]) < V):
+        raise ValueError("TIGER: pad_token_id and eos_token_id must lie in [0, vocab_size)")
+    if num_beams is not None:
+        if not 1 <= num_beams <= 32:
+            no(f"num_beams={num_beams} must be 1..32")
+        if V < 2 * num_beams:
+            no(f"vocab_size={V} must be at least 2 * num_beams = {2 * num_beams}: below that the -1e9-masked dead "
+               "beams reach the selection as exact fp32 ties")
+    if S is not None and not 1 <= S <= 128:
+        no(f"a history of {S} tokens; at most 128 are supported")
+    if max_length is not None and not 2 <= max_length <= 8:
+        no(f"max_length={max_length} must be 2..8")
+    return int(eos)
+
+
+class TigerBinding:
+    """Device-pointer view of a T5 parameter set (``gr_tiger_params``).  ``tensors``: name -> tensor with the
+    reference's T5 names (``shared.weight``, ``encoder.block.0.layer.0.SelfAttention.q.weight``, ...).  The
+    pointers are the tensors' own storage, so in-place weight updates are seen by the next call."""
+
+    def __init__(self, cfg, tensors):
+        eos = tiger_check_config(cfg)
+        self.cfg = cfg
+        self.keep = []
+        dev = tensors["shared.weight"].device
+        self.device = dev
+        p = L.TigerParams()
+        p.vocab, p.d_model, p.d_kv, p.n_heads = (int(cfg[k]) for k in ("vocab_size", "d_model", "d_kv", "num_heads"))
+        p.d_ff, p.n_enc, p.n_dec, p.n_buckets = int(cfg["d_ff"]), int(cfg["num_layers"]), int(cfg["num_decoder_layers"]), 32
+        p.pad_id, p.eos_id = int(cfg["pad_token_id"]), eos
+        p.fill_id = p.pad_id or eos          # the library's `pad_token_id or eos_token_id[0]`
+        p.eps = float(cfg.get("layer_norm_epsilon", 1e-6))
+        p.lm_scale = float(p.d_model ** -0.5) if cfg.get("scale_decoder_outputs", True) else 1.0
+        f = self._f
+        p.shared, p.lm_head = f(tensors["shared.weight"]), f(tensors["lm_head.weight"])
+        p.enc_rel = f(tensors[f"encoder.block.0.{TIGER_REL}.weight"])
+        p.dec_rel = f(tensors[f"decoder.block.0.{TIGER_REL}.weight"])
+        p.enc_final_ln = f(tensors["encoder.final_layer_norm.weight"])
+        p.dec_final_ln = f(tensors["decoder.final_layer_norm.weight"])
+        for l in range(p.n_enc):
+            for i, k in enumerate(TIGER_ENC_KEYS):
+                p.enc[l][i] = f(tensors[f"encoder.block.{l}.{k}.weight"])
+        for l in range(p.n_dec):
+            for i, k in enumerate(TIGER_DEC_KEYS):
+                p.dec[l][i] = f(tensors[f"decoder.block.{l}.{k}.weight"])
+        r = torch.arange(-127, 128)
+        self.enc_bucket = t5_relative_bucket(r, True).to(torch.int32).to(dev)
+        self.dec_bucket = t5_relative_bucket(-torch.arange(8), False).to(torch.int32).to(dev)
+        p.enc_bucket, p.dec_bucket = self.enc_bucket.data_ptr(), self.dec_bucket.data_ptr()
+        self.params = p
+        self.ref = ctypes.byref(p)
+        self._ws = {}
+
+    def _f(self, t):
+        L.require_gpu(t)
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise TypeError("TIGER kernels take contiguous float32 parameters")
+        self.keep.append(t)
+        return t.data_ptr()
+
+    def workspace_bytes(self, B, S, num_beams, max_length):
+        key = (B, S, num_beams, max_length)
+        n = self._ws.get(key)
+        if n is None:
+            n = self._ws[key] = L.lib().gr_tiger_workspace_bytes(self.ref, B, S, num_beams, max_length)
+        return n
+
+
+def tiger_generate(binding, input_ids, attention_mask=None, num_beams=20, max_length=5, with_encoder=False,
+                   with_logits=False):
+    """``gr_tiger_generate_f32``: T5 encode and the whole beam search in one C call, nothing synchronises.
+    -> (sequences [B, num_beams, max_length] int64, scores [B, num_beams] fp32[, encoder output
+    [B, S, d_model]][, step logits [B, max_length - 1, num_beams, vocab]])."""
+    L.require_gpu(input_ids)
+    if input_ids.dim() != 2 or input_ids.dtype != torch.int64:
+        raise RuntimeError(f"tiger_generate takes [B, S] int64 token ids, got {tuple(input_ids.shape)} {input_ids.dtype}")
+    B, S = input_ids.shape
+    num_beams, max_length = int(num_beams), int(max_length)
+    tiger_check_config(binding.cfg, num_beams, S, max_length)
+    input_ids = input_ids.contiguous()
+    if attention_mask is not None:
+        L.require_gpu(attention_mask)
+        if tuple(attention_mask.shape) != (B, S):
+            raise RuntimeError(f"attention_mask must be [{B}, {S}], got {tuple(attention_mask.shape)}")
+        if attention_mask.dtype != torch.int64:
+            attention_mask = attention_mask.to(torch.int64)
+        attention_mask = attention_mask.contiguous()
+    dev = input_ids.device
+    V, D = binding.params.vocab, binding.params.d_model
+    seqs = torch.empty((B, num_beams, max_length), dtype=torch.int64, device=dev)
+    scores = torch.empty((B, num_beams), dtype=torch.float32, device=dev)
+    enc = torch.empty((B, S, D), dtype=torch.float32, device=dev) if with_encoder else None
+    logits = torch.empty((B, max_length - 1, num_beams, V), dtype=torch.float32, device=dev) if with_logits else None
+    nbytes = binding.workspace_bytes(B, S, num_beams, max_length)
+    wsp = L.workspace(nbytes, dev)
+    with L.on(dev):
+        L.check(L.lib().gr_tiger_generate_f32(binding.ref, L.ptr(input_ids), L.ptr(attention_mask), B, S, num_beams,
+                                              max_length, L.ptr(seqs), L.ptr(scores), L.ptr(enc), L.ptr(logits),
+                                              L.ptr(wsp), nbytes, L.stream_of(dev)), "gr_tiger_generate_f32")
+    out = (seqs, scores)
+    if with_encoder:
+        out += (enc,)
+    if with_logits:
+        out += (logits,)
+    return out
+
+
+def beam_hits(preds, labels, skip=0):
+    """``calculate_pos_index`` (RQVAE-T5/utils.py:6-32) on the device: preds [B, k, T] int64 (the first
+    ``skip`` tokens of each hypothesis dropped, the rest zero-padded or cut to the labels' width), labels
+    [B, W] int64 -> bool [B, k] marking the first beam whose tokens equal the label row."""
+    L.require_gpu(preds, labels)
+    if preds.dim() != 3 or labels.dim() != 2 or preds.shape[0] != labels.shape[0]:
+        raise RuntimeError(f"beam_hits takes preds [B, k, T] and labels [B, W], got {tuple(preds.shape)} and "
+                           f"{tuple(labels.shape)}")
+    if preds.dtype != torch.int64 or labels.dtype != torch.int64:
+        raise TypeError("beam_hits takes int64 tokens")
+    preds, labels = preds.contiguous(), labels.contiguous()
+    B, k, T = preds.shape
+    skip = int(skip)
+    if not 0 <= skip <= T:
+        raise ValueError(f"skip={skip} outside [0, {T}]")
+    hits = torch.empty((B, k), dtype=torch.uint8, device=preds.device)
+    with L.on(preds.device):
+        L.check(L.lib().gr_beam_hits_i64(preds.data_ptr() + 8 * skip, B, k, T - skip, T, L.ptr(labels),
+                                         labels.shape[1], L.ptr(hits), L.stream_of(preds.device)), "gr_beam_hits_i64")
+    return hits.view(torch.bool)

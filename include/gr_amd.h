@@ -601,6 +601,73 @@ int gr_kmeans_f32(const float* x, int64_t n, int32_t e, int32_t K, const float* 
                   int64_t* labels_out, double* inertia_out, int32_t* n_iter_out, void* workspace,
                   size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* TIGER generative retrieval (RQVAE-T5/model.py:62-81 TIGER.generate: a T5 encoder-decoder searched
+ * by transformers' GenerationMixin._beam_search with num_return_sequences = num_beams,
+ * length_penalty 1, early_stopping False, no sampling, decoder_start_token_id = pad).
+ *
+ * gr_tiger_params: dimensions and device pointers of the T5 weights (fp32, row-major [out, in] as
+ * nn.Linear stores them, 16-byte aligned).  enc[l] = {layer.0.layer_norm, q, k, v, o,
+ * layer.1.layer_norm, wi, wo}; dec[l] = {layer.0.layer_norm, q, k, v, o, layer.1.layer_norm,
+ * EncDecAttention q, k, v, o, layer.2.layer_norm, wi, wo}.  enc_rel / dec_rel: block 0's
+ * relative_attention_bias [n_buckets, n_heads].  enc_bucket[255]: the bucket of key - query distance
+ * r at index r + 127 (bidirectional); dec_bucket[8]: the bucket of a key d positions behind the query
+ * at index d (one-directional) -- T5Attention._relative_position_bucket's values, device int32.
+ * lm_scale multiplies the decoder output before lm_head (d_model^-0.5 with tied embeddings, else 1).
+ * fill_id is what unfilled positions of a hypothesis hold: the library's `pad_token_id or
+ * eos_token_id`, i.e. the EOS id when the pad id is 0.
+ *
+ * Envelope (GR_ERR_UNSUPPORTED outside, with the limit named): d_model in {32, 64};
+ * n_heads * d_kv in {32, 64} with d_kv in {8, 16, 32}; d_ff <= 256 and a multiple of 32; 1..4 layers
+ * on each side; 2 * num_beams <= vocab <= 128 (below that the -1e9-masked dead beams would reach the
+ * selection as exact fp32 ties); 1 <= S <= 128; 1 <= num_beams <= 32; 2 <= max_length <= 8; at most 2^21 users per call.
+ * Preconditions (not checked): ids in [0, vocab) (out-of-range ids are clamped); every history has at
+ * least one unmasked token.
+ *
+ * gr_tiger_generate_f32 enqueues two launches and never synchronises: an encoder kernel (one
+ * workgroup per user; it also projects every decoder layer's cross-attention K and V once per user)
+ * and a search kernel (one workgroup per user runs all max_length - 1 decode steps, the selection of
+ * the 2 * num_beams continuations among num_beams * vocab, and the running / finished bookkeeping).
+ * A user whose early-stop heuristic is satisfied runs no further step (the library runs them and
+ * ignores their result).  Equal scores: the lower flat index (beam * vocab + token) first; an old finished hypothesis before
+ * a new one.
+ *   input_ids[B, S] int64, attention_mask[B, S] int64 (0 = padding; NULL: none)
+ *   sequences[B, num_beams, max_length] int64: best first, never cropped; scores[B, num_beams]
+ *   enc_out[B, S, d_model] (optional): the encoder output (rows of padding are unspecified)
+ *   step_logits[B, max_length - 1, num_beams, vocab] (optional): lm_head logits of the running beams
+ *   at each step (zero where a beam is not live or the user's search has stopped)
+ * workspace: gr_tiger_workspace_bytes(...) bytes, 16-byte aligned (0 outside the envelope). */
+#define GR_TIGER_MAX_LAYERS 4
+typedef struct gr_tiger_params {
+  int32_t vocab, d_model, d_kv, n_heads, d_ff, n_enc, n_dec, n_buckets;
+  int32_t pad_id, eos_id, fill_id, reserved;
+  float eps, lm_scale;
+  const float* shared;
+  const float* lm_head;
+  const float* enc_rel;
+  const float* dec_rel;
+  const float* enc_final_ln;
+  const float* dec_final_ln;
+  const int32_t* enc_bucket;
+  const int32_t* dec_bucket;
+  const float* enc[GR_TIGER_MAX_LAYERS][8];
+  const float* dec[GR_TIGER_MAX_LAYERS][13];
+} gr_tiger_params;
+
+size_t gr_tiger_workspace_bytes(const gr_tiger_params* p, int64_t B, int32_t S, int32_t num_beams,
+                                int32_t max_length);
+int gr_tiger_generate_f32(const gr_tiger_params* p, const int64_t* input_ids, const int64_t* attention_mask,
+                          int64_t B, int32_t S, int32_t num_beams, int32_t max_length, int64_t* sequences,
+                          float* scores, float* enc_out, float* step_logits, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
+/* calculate_pos_index of RQVAE-T5/utils.py:6-32: hits[b, j] = 1 for the first beam j whose tokens
+ * equal labels[b, :], 0 elsewhere.  preds: beam j of user b starts at preds + (b * k + j) * ld_pred
+ * and holds pred_len tokens; positions past pred_len compare as 0 (evaluate_model's zero padding) and
+ * positions past label_len are not compared (its cut).  hits[B, k] uint8. */
+int gr_beam_hits_i64(const int64_t* preds, int64_t B, int32_t k, int32_t pred_len, int64_t ld_pred,
+                     const int64_t* labels, int32_t label_len, uint8_t* hits, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
