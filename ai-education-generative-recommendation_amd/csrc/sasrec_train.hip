@@ -16,24 +16,25 @@
 //
 // Dropout (p = params['dropout']) keeps an element when a counter-based hash of (seed, sequence,
 // site, element) is >= p and scales it by 1 / (1 - p), as torch's dropout does (its random stream
-// is not reproduced).  Sites per block k: 3k attention probabilities, 3k+1 FFN hidden, 3k+2 FFN
-// output.  The seed is read from a device word (seed0 ^ *seed_dev) so a captured step replays with
-// fresh masks; the forward and backward of one step read the same word.
-#include "gr_common.h"
+// is not reproduced).  The seed is read from a device word (seed0 ^ *seed_dev) so a captured step
+// replays with fresh masks; the forward and backward of one step read the same word.
+//
+// The g_vec layout, the dropout sites and element indices, the offsets into the saved-activation
+// buffers and the argument checks are sasrec_train_contract.h's, shared with sasrec_train_tiled.hip.
+#include "sasrec_train_contract.h"
 
 namespace gr {
 namespace st {
 
 constexpr int NT = 512;     // threads per workgroup (8 waves, 2 per SIMD)
-constexpr int MAXB = 8;     // transformer blocks
-constexpr int NMAX = 64, DMAX = 64, MMAX = 128;
+constexpr SasTrainLimits LIMITS{"gr_sasrec_train", 64, 64, 128, false};   // n, d, mlp_layer
 
 struct Blk {
   const float *ln_a_w, *ln_a_b, *w_in, *b_in, *w_o, *b_o, *ln_f_w, *ln_f_b, *w1, *b1, *w2, *b2;
 };
 
 struct Args {
-  Blk blk[MAXB];
+  Blk blk[SAS_TRAIN_MAXB];
   const float *item, *pos, *ln_w, *ln_b;
   int64_t item_rows;
   int nb, d, heads, mlp, n;
@@ -200,45 +201,6 @@ __device__ __forceinline__ void col_sums(float* dst, const float* M, int ld, int
   }
 }
 
-// ---- per-sequence offsets into the saved-activation buffers --------------------------------
-struct Offs {
-  int64_t rd, r3, rm, pp;   // row blocks of width d, 3d, mlp; probabilities per (block, sequence)
-};
-
-__device__ __forceinline__ Offs offs(const Args& a, int bk, int64_t b) {
-  const int64_t rows = a.B * a.n, r0 = b * a.n;
-  Offs o;
-  o.rd = (int64_t)bk * rows * a.d + r0 * a.d;
-  o.r3 = (int64_t)bk * rows * 3 * a.d + r0 * 3 * a.d;
-  o.rm = (int64_t)bk * rows * a.mlp + r0 * a.mlp;
-  o.pp = ((int64_t)bk * a.B + b) * a.heads * a.n * a.n;
-  return o;
-}
-
-// g_vec per sequence, in the order of SASRec's parameters: per block [ln_a w, ln_a b, in_proj w
-// (3d x d), in_proj b (3d), out_proj w (d x d), out_proj b, ln_f w, ln_f b, ffn1 w (mlp x d),
-// ffn1 b (mlp), ffn2 w (d x mlp), ffn2 b], then [last ln w, last ln b], then pos (n x d).
-struct VOff {
-  int law, lab, inw, inb, ow, ob, lfw, lfb, w1, b1, w2, b2, size;
-};
-__host__ __device__ __forceinline__ VOff voff(int d, int m) {
-  VOff v;
-  v.law = 0;
-  v.lab = d;
-  v.inw = 2 * d;
-  v.inb = v.inw + 3 * d * d;
-  v.ow = v.inb + 3 * d;
-  v.ob = v.ow + d * d;
-  v.lfw = v.ob + d;
-  v.lfb = v.lfw + d;
-  v.w1 = v.lfb + d;
-  v.b1 = v.w1 + m * d;
-  v.w2 = v.b1 + m;
-  v.b2 = v.w2 + d * m;
-  v.size = v.b2 + d;
-  return v;
-}
-
 __global__ __launch_bounds__(NT) void sas_train_fwd_kernel(const Args a, const int64_t* __restrict__ seqs,
                                                            float* __restrict__ out, int32_t* err) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -267,7 +229,7 @@ __global__ __launch_bounds__(NT) void sas_train_fwd_kernel(const Args a, const i
   __syncthreads();
   for (int bk = 0; bk < a.nb; ++bk) {
     const Blk& p = a.blk[bk];
-    const Offs o = offs(a, bk, b);
+    const SasOffs o = sas_offs(bk, b, a.B, a.n, a.d, a.mlp, a.heads);
     copy_out(g.xin + o.rd, X, pd, n, d);
     ln_rows(X, pd, Hb, pd, p.ln_a_w, p.ln_a_b, n, d, a.eps);                        // model.py:80
     stage_t(Wt, d3 + 1, p.w_in, d3, d);
@@ -294,7 +256,7 @@ __global__ __launch_bounds__(NT) void sas_train_fwd_kernel(const Args a, const i
         const float pr = e / wave_sum(e);
         if (lane < n) {
           g.prob[o.pp + ((int64_t)hh * n + i) * n + lane] = pr;
-          S[i * pn + lane] = pr * sas_keep(a, seed, b, 3 * bk, (uint32_t)((hh * n + i) * n + lane));
+          S[i * pn + lane] = pr * sas_keep(a, seed, b, sas_site_prob(bk), sas_elem_prob(hh, n, i, lane));
         }
       }
       __syncthreads();
@@ -316,7 +278,7 @@ __global__ __launch_bounds__(NT) void sas_train_fwd_kernel(const Args a, const i
     __syncthreads();
     for (int idx = tid; idx < n * m; idx += NT) {                                  // dropout(relu)
       const int i = idx / m, c = idx - i * m;
-      BIG[i * pw + c] = fmaxf(BIG[i * pw + c], 0.f) * sas_keep(a, seed, b, 3 * bk + 1, (uint32_t)idx);
+      BIG[i * pw + c] = fmaxf(BIG[i * pw + c], 0.f) * sas_keep(a, seed, b, sas_site_hidden(bk), sas_elem_row(i, c, m));
     }
     __syncthreads();
     copy_out(g.us + o.rm, BIG, pw, n, m);
@@ -324,7 +286,7 @@ __global__ __launch_bounds__(NT) void sas_train_fwd_kernel(const Args a, const i
     __syncthreads();
     for (int idx = tid; idx < n * d; idx += NT) {                                  // x + dropout(y) (model.py:94)
       const int i = idx / d, f = idx - i * d;
-      X[i * pd + f] += Hb[i * pd + f] * sas_keep(a, seed, b, 3 * bk + 2, (uint32_t)idx);
+      X[i * pd + f] += Hb[i * pd + f] * sas_keep(a, seed, b, sas_site_out(bk), sas_elem_row(i, f, d));
     }
     __syncthreads();
   }
@@ -347,9 +309,9 @@ __global__ __launch_bounds__(NT) void sas_train_bwd_kernel(const Args a, const i
   float* red = PS + n * pn;            // [NT] reduction scratch
   const gr_sasrec_train_bufs& g = a.buf;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const VOff vo = voff(d, m);
+  const VOff vo = voff(d, m, a.nb);
   float* gv = g.g_vec + b * a.vwidth;
-  float* glast = gv + a.nb * vo.size;
+  float* glast = gv + vo.last;
 
   // last LayerNorm (model.py:96)
   for (int idx = tid; idx < n * d; idx += NT) {
@@ -361,12 +323,12 @@ __global__ __launch_bounds__(NT) void sas_train_bwd_kernel(const Args a, const i
   ln_back(g.xl + b * n * d, T, pd, DX, pd, a.ln_w, n, d, a.eps, glast, glast + d, red);
   for (int bk = a.nb - 1; bk >= 0; --bk) {
     const Blk& p = a.blk[bk];
-    const Offs o = offs(a, bk, b);
+    const SasOffs o = sas_offs(bk, b, a.B, a.n, a.d, a.mlp, a.heads);
     float* gvb = gv + bk * vo.size;
     // FFN output: x2 = x1 + dropout(y), y = u W2^T + b2
     for (int idx = tid; idx < n * d; idx += NT) {
       const int i = idx / d, f = idx - i * d;
-      T[i * pd + f] = DX[i * pd + f] * sas_keep(a, seed, b, 3 * bk + 2, (uint32_t)idx);
+      T[i * pd + f] = DX[i * pd + f] * sas_keep(a, seed, b, sas_site_out(bk), sas_elem_row(i, f, d));
     }
     __syncthreads();
     col_sums(gvb + vo.b2, T, pd, n, d);                                              // db2
@@ -375,7 +337,7 @@ __global__ __launch_bounds__(NT) void sas_train_bwd_kernel(const Args a, const i
     __syncthreads();
     for (int idx = tid; idx < n * m; idx += NT) {                                   // through dropout and relu
       const int i = idx / m, c = idx - i * m;
-      G1[i * pw + c] = g.zs[o.rm + idx] > 0.f ? G1[i * pw + c] * sas_keep(a, seed, b, 3 * bk + 1, (uint32_t)idx) : 0.f;
+      G1[i * pw + c] = g.zs[o.rm + idx] > 0.f ? G1[i * pw + c] * sas_keep(a, seed, b, sas_site_hidden(bk), sas_elem_row(i, c, m)) : 0.f;
     }
     __syncthreads();
     col_sums(gvb + vo.b1, G1, pw, n, m);                                             // db1
@@ -393,7 +355,7 @@ __global__ __launch_bounds__(NT) void sas_train_bwd_kernel(const Args a, const i
       const float* P = g.prob + o.pp + (int64_t)hh * n * n;
       for (int idx = tid; idx < n * n; idx += NT) {                                 // P' = P * keep
         const int i = idx / n, j = idx - i * n;
-        PS[i * pn + j] = P[idx] * sas_keep(a, seed, b, 3 * bk, (uint32_t)(hh * n * n + idx));
+        PS[i * pn + j] = P[idx] * sas_keep(a, seed, b, sas_site_prob(bk), sas_elem_prob(hh, n, i, j));
       }
       __syncthreads();
       mm<false>(G1 + 2 * d + hh * hd, pw, PS, 1, pn, T + hh * hd, pd, 1, n, hd, n); // dV = P'^T dO
@@ -403,7 +365,7 @@ __global__ __launch_bounds__(NT) void sas_train_bwd_kernel(const Args a, const i
       for (int i = wv; i < n; i += NT / 64) {                                       // softmax backward
         const bool on = lane <= i && lane < n;
         const float pr = on ? P[i * n + lane] : 0.f;
-        const float dp = on ? PS[i * pn + lane] * sas_keep(a, seed, b, 3 * bk, (uint32_t)((hh * n + i) * n + lane)) : 0.f;
+        const float dp = on ? PS[i * pn + lane] * sas_keep(a, seed, b, sas_site_prob(bk), sas_elem_prob(hh, n, i, lane)) : 0.f;
         const float sdp = wave_sum(dp * pr);
         if (lane < n) PS[i * pn + lane] = on ? pr * (dp - sdp) : 0.f;
       }
@@ -420,7 +382,7 @@ __global__ __launch_bounds__(NT) void sas_train_bwd_kernel(const Args a, const i
   }
   // x0 = item_emb[s] + pos_emb[i]: rows of the item table by atomics (padding row 0 keeps a zero
   // gradient, nn.Embedding(padding_idx=0)); positions as this sequence's partial
-  float* gpos = glast + 2 * d;
+  float* gpos = gv + vo.pos;
   for (int idx = tid; idx < n * d; idx += NT) {
     const int i = idx / d, f = idx - i * d;
     const float v = DX[i * pd + f];
@@ -444,14 +406,8 @@ static size_t bwd_lds(int n, int d, int m) {
 
 static int build_args(const gr_sasrec_params* p, int64_t B, int32_t n, float p_drop, uint64_t seed,
                       const uint64_t* seed_dev, const gr_sasrec_train_bufs* bufs, Args& a) {
-  if (!p || !bufs) return fail(GR_ERR_ARG, "gr_sasrec_train: null params / buffers");
-  if (p->n_blocks < 1 || p->n_blocks > MAXB) return fail(GR_ERR_UNSUPPORTED, "gr_sasrec_train: 1..8 blocks");
-  if (p->d < 1 || p->d > DMAX || p->n_heads < 1 || p->d % p->n_heads)
-    return fail(GR_ERR_UNSUPPORTED, "gr_sasrec_train: d <= 64, divisible by num_heads");
-  if (p->mlp < 1 || p->mlp > MMAX) return fail(GR_ERR_UNSUPPORTED, "gr_sasrec_train: mlp_layer <= 128");
-  if (n < 1 || n > NMAX || n > p->max_len) return fail(GR_ERR_UNSUPPORTED, "gr_sasrec_train: 1 <= n <= min(64, max_len)");
-  if (B < 1 || B > 0x7fffffffLL) return fail(GR_ERR_ARG, "gr_sasrec_train: bad batch");
-  if (!(p_drop >= 0.f && p_drop < 1.f)) return fail(GR_ERR_ARG, "gr_sasrec_train: dropout must be in [0, 1)");
+  const int rc = sas_train_check(LIMITS, p, B, n, p_drop, bufs);
+  if (rc) return rc;
   a = Args{};
   for (int k = 0; k < p->n_blocks; ++k) {
     a.blk[k] = Blk{p->attn_ln_w[k], p->attn_ln_b[k], p->in_proj_w[k], p->in_proj_b[k], p->out_proj_w[k],
@@ -476,7 +432,7 @@ static int build_args(const gr_sasrec_params* p, int64_t B, int32_t n, float p_d
   a.seed_dev = seed_dev;
   a.buf = *bufs;
   a.B = B;
-  a.vwidth = p->n_blocks * voff(p->d, p->mlp).size + 2 * p->d + n * p->d;
+  a.vwidth = sas_vec_width(p->n_blocks, p->d, p->mlp, n);
   return GR_OK;
 }
 
@@ -485,7 +441,7 @@ static int build_args(const gr_sasrec_params* p, int64_t B, int32_t n, float p_d
 
 extern "C" int32_t gr_sasrec_train_vec_width(const gr_sasrec_params* p, int32_t n) {
   if (!p) return 0;
-  return p->n_blocks * gr::st::voff(p->d, p->mlp).size + 2 * p->d + n * p->d;
+  return gr::sas_vec_width(p->n_blocks, p->d, p->mlp, n);
 }
 
 extern "C" int gr_sasrec_train_fwd_f32(const gr_sasrec_params* p, const int64_t* seqs, int64_t B, int32_t n,
@@ -498,8 +454,7 @@ extern "C" int gr_sasrec_train_fwd_f32(const gr_sasrec_params* p, const int64_t*
   int rc = st::build_args(p, B, n, p_drop, seed, seed_dev, bufs, a);
   if (rc) return rc;
   const gr_sasrec_train_bufs& g = *bufs;
-  if (!seqs || !out || !g.xin || !g.hs || !g.qkv || !g.prob || !g.os || !g.x1 || !g.fs || !g.zs || !g.us || !g.xl)
-    return fail(GR_ERR_ARG, "gr_sasrec_train_fwd_f32: null pointer");
+  if (!seqs || !out || null_acts(g)) return fail(GR_ERR_ARG, "gr_sasrec_train_fwd_f32: null pointer");
   const size_t lds = st::fwd_lds(n, p->d, p->mlp);
   auto k = st::sas_train_fwd_kernel;
   if (lds > 64 * 1024 &&
@@ -521,9 +476,7 @@ extern "C" int gr_sasrec_train_bwd_f32(const gr_sasrec_params* p, const int64_t*
   int rc = st::build_args(p, B, n, p_drop, seed, seed_dev, bufs, a);
   if (rc) return rc;
   const gr_sasrec_train_bufs& g = *bufs;
-  if (!seqs || !d_out || !g.g_vec || !g.xin || !g.hs || !g.qkv || !g.prob || !g.os || !g.x1 || !g.fs ||
-      !g.zs || !g.us || !g.xl)
-    return fail(GR_ERR_ARG, "gr_sasrec_train_bwd_f32: null pointer");
+  if (!seqs || !d_out || !g.g_vec || null_acts(g)) return fail(GR_ERR_ARG, "gr_sasrec_train_bwd_f32: null pointer");
   const size_t lds = st::bwd_lds(n, p->d, p->mlp);
   auto k = st::sas_train_bwd_kernel;
   if (lds > 64 * 1024 &&

@@ -2,9 +2,8 @@
 // (sasrec_train.hip: n, d <= 64, mlp_layer <= 128): d <= 128, n <= 256, mlp_layer <= 256.
 //
 // The same computation (SASRec/model.py:49-96 in train mode and its backward), the same saved
-// activations (gr_sasrec_train_bufs) and the same dropout masks (gr_common.h SasDrop / sas_keep(),
-// shared with sasrec_train.hip: keyed by seed, sequence, site and element), but tiled over all
-// B * n rows instead of held in one workgroup's LDS:
+// activations, dropout masks and g_vec layout (sasrec_train_contract.h, shared with
+// sasrec_train.hip), but tiled over all B * n rows instead of held in one workgroup's LDS:
 //   - every product is one launch of gemm_kernel: 64 x 64 output tiles on v_mfma_f32_32x32x2_f32,
 //     operands staged through LDS from any (row stride, k stride) layout, a two-level batch index
 //     (sequence, head) for the attention products, causal tile / k-range skipping, and an epilogue
@@ -17,12 +16,13 @@
 //   - item-table rows are scattered with fp32 atomics (padding row 0 excluded).
 // Activation gradients (dX, dY, a [rows, d] temporary, dQ|dK|dV or dZ, LayerNorm row statistics,
 // P' = dropout(P) and dS) live in the caller's workspace.  All global offsets are 64-bit.
-#include "gr_common.h"
+#include "sasrec_train_contract.h"
 
 namespace gr {
 namespace stt {
 
-constexpr int MAXB = 8, NMAX = 256, DMAX = 128, MMAX = 256;
+constexpr int NMAX = 256, DMAX = 128;   // n, d; mlp_layer <= 256
+constexpr SasTrainLimits LIMITS{"gr_sasrec_train_tiled", NMAX, DMAX, 256, true};
 constexpr int GT = 256;                 // threads per workgroup: 4 waves, a 2 x 2 grid of 32 x 32 tiles
 constexpr int TM = 64, TN = 64, TK = 32, LP = 65;   // tile, k step, LDS pitch of a k row
 static_assert(TM == 64 && TN == 64 && GT % TK == 0 && (GT / TK) * (TK * 64 / GT) == 64 &&
@@ -143,8 +143,7 @@ __global__ __launch_bounds__(GT) void gemm_kernel(const Gemm g) {
       C[o] = g.R[o] + x;
     } else {
       const int64_t b = row / g.n;
-      const uint32_t idx = (uint32_t)((row - b * g.n) * g.N + col);
-      const float kf = sas_keep(g.dr, seed, b, g.site, idx);
+      const float kf = sas_keep(g.dr, seed, b, g.site, sas_elem_row(row - b * g.n, col, g.N));
       if (EPI == E_FFN1) {
         C[o] = x;
         g.C2[o] = fmaxf(x, 0.f) * kf;
@@ -205,7 +204,7 @@ __global__ __launch_bounds__(GT) void ln_fwd_kernel(const float* __restrict__ X,
 }
 
 // LayerNorm backward of one row: DX = (ACC ? DX : 0) + dLN/dx; the row's (mean, rstd) go to stats
-// for the dgamma / dbeta column sums; dy_out (optional) = new DX * sas_keep(site, i * d + f): the
+// for the dgamma / dbeta column sums; dy_out (optional) = new DX * sas_keep(site, row element): the
 // gradient of the FFN output of the block below.
 __global__ __launch_bounds__(GT) void ln_bwd_kernel(const float* __restrict__ X, const float* __restrict__ DY,
                                                     float* __restrict__ DX, int acc, const float* __restrict__ w,
@@ -256,13 +255,13 @@ __global__ __launch_bounds__(GT) void ln_bwd_kernel(const float* __restrict__ X,
       float v = rstd * (dxh[t] - s1 - xh[t] * s2);
       if (acc) v += DX[row * d + f];
       DX[row * d + f] = v;
-      if (dy_out) dy_out[row * d + f] = v * sas_keep(dr, seed, b, site, (uint32_t)(i * d + f));
+      if (dy_out) dy_out[row * d + f] = v * sas_keep(dr, seed, b, site, sas_elem_row(i, f, d));
     }
   }
 }
 
 // causal softmax of one query row of one (sequence, head): S holds the scaled scores of keys j <= i;
-// P (the saved probabilities, zero past i) overwrites them, PK = P * keep (site, (h n + i) n + j)
+// P (the saved probabilities, zero past i) overwrites them, PK = P * keep
 __global__ __launch_bounds__(GT) void softmax_fwd_kernel(float* __restrict__ P, float* __restrict__ PK, int64_t rows,
                                                          int n, int H, int site, const SasDrop dr) {
   const int lane = threadIdx.x & 63;
@@ -294,7 +293,7 @@ __global__ __launch_bounds__(GT) void softmax_fwd_kernel(float* __restrict__ P, 
     if (j < n) {
       const float pr = sv[t] / sum;
       P[row * n + j] = pr;
-      PK[row * n + j] = pr * sas_keep(dr, seed, b, site, (uint32_t)((hh * n + i) * n + j));
+      PK[row * n + j] = pr * sas_keep(dr, seed, b, site, sas_elem_prob(hh, n, i, j));
     }
   }
 }
@@ -317,7 +316,7 @@ __global__ __launch_bounds__(GT) void softmax_bwd_kernel(const float* __restrict
   for (int t = 0; t < 4; ++t) {
     const int j = lane + 64 * t;
     const bool on = j <= i;
-    kf[t] = on ? sas_keep(dr, seed, b, site, (uint32_t)((hh * n + i) * n + j)) : 0.f;
+    kf[t] = on ? sas_keep(dr, seed, b, site, sas_elem_prob(hh, n, i, j)) : 0.f;
     pr[t] = on ? P[row * n + j] : 0.f;
     dp[t] = on ? DS[row * n + j] * kf[t] : 0.f;
     sdp = fmaf(dp[t], pr[t], sdp);
@@ -383,28 +382,6 @@ __global__ __launch_bounds__(GT) void item_scatter_kernel(const int64_t* __restr
 }
 
 // ---- host side ------------------------------------------------------------------------------
-// g_vec per part, in the order of SASRec's parameters (sasrec_train.hip voff)
-struct VOff {
-  int law, lab, inw, inb, ow, ob, lfw, lfb, w1, b1, w2, b2, size;
-};
-static VOff voff(int d, int m) {
-  VOff v;
-  v.law = 0;
-  v.lab = d;
-  v.inw = 2 * d;
-  v.inb = v.inw + 3 * d * d;
-  v.ow = v.inb + 3 * d;
-  v.ob = v.ow + d * d;
-  v.lfw = v.ob + d;
-  v.lfb = v.lfw + d;
-  v.w1 = v.lfb + d;
-  v.b1 = v.w1 + m * d;
-  v.w2 = v.b1 + m;
-  v.b2 = v.w2 + d * m;
-  v.size = v.b2 + d;
-  return v;
-}
-
 static int parts_of(int64_t rows) {
   const int64_t s = (rows + PART_ROWS - 1) / PART_ROWS;
   return (int)(s < 1 ? 1 : s > MAXPARTS ? MAXPARTS : s);
@@ -432,25 +409,6 @@ static Ws ws_layout(int64_t B, int n, int d, int H, int m) {
   w.ds = take(pp);
   w.total = o;
   return w;
-}
-
-static int check_shape(const gr_sasrec_params* p, int64_t B, int32_t n, float p_drop,
-                       const gr_sasrec_train_bufs* bufs) {
-  if (!p || !bufs) return fail(GR_ERR_ARG, "gr_sasrec_train_tiled: null params / buffers");
-  if (p->n_blocks < 1 || p->n_blocks > MAXB) return fail(GR_ERR_UNSUPPORTED, "gr_sasrec_train_tiled: 1..8 blocks");
-  if (p->d < 1 || p->d > DMAX || p->n_heads < 1 || p->d % p->n_heads)
-    return fail(GR_ERR_UNSUPPORTED, "gr_sasrec_train_tiled: d <= 128, divisible by num_heads");
-  if (p->mlp < 1 || p->mlp > MMAX) return fail(GR_ERR_UNSUPPORTED, "gr_sasrec_train_tiled: mlp_layer <= 256");
-  if (n < 1 || n > NMAX || n > p->max_len)
-    return fail(GR_ERR_UNSUPPORTED, "gr_sasrec_train_tiled: 1 <= n <= min(256, max_len)");
-  // B * n * heads < 2^31: every launch's grid (softmax rows, attention tiles per (sequence, head)) fits
-  if (B < 1 || B > 0x7fffffffLL / n / p->n_heads) return fail(GR_ERR_ARG, "gr_sasrec_train_tiled: bad batch");
-  if (!(p_drop >= 0.f && p_drop < 1.f)) return fail(GR_ERR_ARG, "gr_sasrec_train_tiled: dropout must be in [0, 1)");
-  return GR_OK;
-}
-
-static bool null_acts(const gr_sasrec_train_bufs& g) {
-  return !g.xin || !g.hs || !g.qkv || !g.prob || !g.os || !g.x1 || !g.fs || !g.zs || !g.us || !g.xl;
 }
 
 template <int EPI>
@@ -504,7 +462,7 @@ extern "C" int gr_sasrec_train_tiled_fwd_f32(const gr_sasrec_params* p, const in
   using namespace gr;
   using namespace gr::stt;
   clear_error();
-  int rc = check_shape(p, B, n, p_drop, bufs);
+  const int rc = sas_train_check(LIMITS, p, B, n, p_drop, bufs);
   if (rc) return rc;
   const gr_sasrec_train_bufs& g = *bufs;
   if (!seqs || !out || !workspace || null_acts(g)) return fail(GR_ERR_ARG, "gr_sasrec_train_tiled_fwd_f32: null pointer");
@@ -523,16 +481,10 @@ extern "C" int gr_sasrec_train_tiled_fwd_f32(const gr_sasrec_params* p, const in
   hipLaunchKernelGGL(embed_kernel, dim3(eb), dim3(GT), 0, st, seqs, p->item_emb, p->pos_emb, p->item_rows, R, n, d,
                      g.xin, err_flag);
   for (int bk = 0; bk < nb; ++bk) {
-    float* X = g.xin + (int64_t)bk * R * d;
-    float* hs = g.hs + (int64_t)bk * R * d;
-    float* qkv = g.qkv + (int64_t)bk * R * d3;
-    float* prob = g.prob + (int64_t)bk * BH * nn;
-    float* os = g.os + (int64_t)bk * R * d;
-    float* x1 = g.x1 + (int64_t)bk * R * d;
-    float* fs = g.fs + (int64_t)bk * R * d;
-    float* zs = g.zs + (int64_t)bk * R * m;
-    float* us = g.us + (int64_t)bk * R * m;
-    float* xn = bk + 1 < nb ? g.xin + (int64_t)(bk + 1) * R * d : g.xl;
+    const SasOffs bo = sas_offs(bk, 0, B, n, d, m, H);
+    float *X = g.xin + bo.rd, *hs = g.hs + bo.rd, *qkv = g.qkv + bo.r3, *prob = g.prob + bo.pp, *os = g.os + bo.rd;
+    float *x1 = g.x1 + bo.rd, *fs = g.fs + bo.rd, *zs = g.zs + bo.rm, *us = g.us + bo.rm;
+    float* xn = bk + 1 < nb ? g.xin + sas_offs(bk + 1, 0, B, n, d, m, H).rd : g.xl;
     hipLaunchKernelGGL(ln_fwd_kernel, dim3(row_blocks(R)), dim3(GT), 0, st, X, hs, p->attn_ln_w[bk], p->attn_ln_b[bk],
                        R, d, p->eps);                                                  // model.py:80
     Gemm q = gemm(hs, d, 1, p->in_proj_w[bk], 1, d, qkv, d3, R, d3, d);                // q | k | v
@@ -547,8 +499,8 @@ extern "C" int gr_sasrec_train_tiled_fwd_f32(const gr_sasrec_params* p, const in
     s.post = q_scale;
     s.skip_upper = 1;
     run<E_PLAIN>(s, BH, st);
-    hipLaunchKernelGGL(softmax_fwd_kernel, dim3(row_blocks(BH * n)), dim3(GT), 0, st, prob, PK, BH * n, n, H, 3 * bk,
-                       dr);
+    hipLaunchKernelGGL(softmax_fwd_kernel, dim3(row_blocks(BH * n)), dim3(GT), 0, st, prob, PK, BH * n, n, H,
+                       sas_site_prob(bk), dr);
     Gemm o = gemm(PK, n, 1, qkv + 2 * d, d3, 1, os, d, n, hd, n);                      // O = P' v
     o.sAo = H * nn;
     o.sAi = nn;
@@ -568,14 +520,14 @@ extern "C" int gr_sasrec_train_tiled_fwd_f32(const gr_sasrec_params* p, const in
     Gemm f1 = gemm(fs, d, 1, p->ffn1_w[bk], 1, d, zs, m, R, m, d);                     // FFN1, dropout(relu)
     f1.bias = p->ffn1_b[bk];
     f1.C2 = us;
-    f1.site = 3 * bk + 1;
+    f1.site = sas_site_hidden(bk);
     f1.n = n;
     f1.dr = dr;
     run<E_FFN1>(f1, 1, st);
     Gemm f2 = gemm(us, m, 1, p->ffn2_w[bk], 1, m, xn, d, R, d, m);                     // x + dropout(FFN2) (model.py:94)
     f2.bias = p->ffn2_b[bk];
     f2.R = x1;
-    f2.site = 3 * bk + 2;
+    f2.site = sas_site_out(bk);
     f2.n = n;
     f2.dr = dr;
     run<E_FFN2>(f2, 1, st);
@@ -592,7 +544,7 @@ extern "C" int gr_sasrec_train_tiled_bwd_f32(const gr_sasrec_params* p, const in
   using namespace gr;
   using namespace gr::stt;
   clear_error();
-  int rc = check_shape(p, B, n, p_drop, bufs);
+  const int rc = sas_train_check(LIMITS, p, B, n, p_drop, bufs);
   if (rc) return rc;
   const gr_sasrec_train_bufs& g = *bufs;
   if (!seqs || !d_out || !workspace || !g.g_vec || null_acts(g))
@@ -609,13 +561,13 @@ extern "C" int gr_sasrec_train_tiled_bwd_f32(const gr_sasrec_params* p, const in
   float *PK = base + w.pk, *DS = base + w.ds;
   const SasDrop dr{p_drop, 1.f / (1.f - p_drop), seed, seed_dev};
   const float q_scale = sqrtf(1.f / (float)hd);
-  const VOff vo = voff(d, m);
+  const VOff vo = voff(d, m, nb);
   const int S = parts_of(R);
   const int64_t chunk = (R + S - 1) / S;          // rows per part
   const int64_t bchunk = (B + S - 1) / S;         // sequences per part (positional rows)
-  const int64_t vw = (int64_t)nb * vo.size + 2 * d + (int64_t)n * d;
+  const int64_t vw = sas_vec_width(nb, d, m, n);
   float* gv = g.g_vec;
-  float* glast = gv + (int64_t)nb * vo.size;
+  float* glast = gv + vo.last;
 
   auto colsum = [&](const float* src, int64_t ld, int width, float* dst) {
     hipLaunchKernelGGL(colsum_kernel, dim3((width + CS_C - 1) / CS_C, S), dim3(CS_C * CS_R), 0, st, src, ld, R, width, chunk, dst,
@@ -635,25 +587,19 @@ extern "C" int gr_sasrec_train_tiled_bwd_f32(const gr_sasrec_params* p, const in
 
   // last LayerNorm (model.py:96); Y = the gradient of the top block's FFN output
   hipLaunchKernelGGL(ln_bwd_kernel, dim3(row_blocks(R)), dim3(GT), 0, st, (const float*)g.xl, d_out, DX, 0,
-                     p->last_ln_w, stats, Y, 3 * (nb - 1) + 2, n, R, d, p->eps, dr);
+                     p->last_ln_w, stats, Y, sas_site_out(nb - 1), n, R, d, p->eps, dr);
   ln_sums(d_out, g.xl, glast, glast + d);
   for (int bk = nb - 1; bk >= 0; --bk) {
     float* gvb = gv + (int64_t)bk * vo.size;
-    const float* X = g.xin + (int64_t)bk * R * d;
-    const float* hs = g.hs + (int64_t)bk * R * d;
-    const float* qkv = g.qkv + (int64_t)bk * R * d3;
-    const float* prob = g.prob + (int64_t)bk * BH * nn;
-    const float* os = g.os + (int64_t)bk * R * d;
-    const float* x1 = g.x1 + (int64_t)bk * R * d;
-    const float* fs = g.fs + (int64_t)bk * R * d;
-    const float* zs = g.zs + (int64_t)bk * R * m;
-    const float* us = g.us + (int64_t)bk * R * m;
+    const SasOffs bo = sas_offs(bk, 0, B, n, d, m, H);
+    const float *X = g.xin + bo.rd, *hs = g.hs + bo.rd, *qkv = g.qkv + bo.r3, *prob = g.prob + bo.pp, *os = g.os + bo.rd;
+    const float *x1 = g.x1 + bo.rd, *fs = g.fs + bo.rd, *zs = g.zs + bo.rm, *us = g.us + bo.rm;
     // FFN: x2 = x1 + dropout(y), y = u W2^T + b2, u = dropout(relu(z)), z = f W1^T + b1
     colsum(Y, d, d, gvb + vo.b2);
     dweight(Y, d, d, us, m, m, gvb + vo.w2);                                           // dW2 = dY^T u
     Gemm du = gemm(Y, d, 1, p->ffn2_w[bk], m, 1, G1, m, R, m, d);                       // dZ = relu'(z) keep (dY W2)
     du.R = zs;
-    du.site = 3 * bk + 1;
+    du.site = sas_site_hidden(bk);
     du.n = n;
     du.dr = dr;
     run<E_DZ>(du, 1, st);
@@ -677,7 +623,7 @@ extern "C" int gr_sasrec_train_tiled_bwd_f32(const gr_sasrec_params* p, const in
     dp.skip_upper = 1;
     run<E_PLAIN>(dp, BH, st);
     hipLaunchKernelGGL(softmax_bwd_kernel, dim3(row_blocks(BH * n)), dim3(GT), 0, st, prob, DS, PK, BH * n, n, H,
-                       3 * bk, dr);
+                       sas_site_prob(bk), dr);
     Gemm dv = gemm(PK, 1, n, T, d, 1, G1 + 2 * d, d3, n, hd, n);                       // dV = P'^T dO
     dv.sAo = H * nn;
     dv.sAi = nn;
@@ -710,13 +656,13 @@ extern "C" int gr_sasrec_train_tiled_bwd_f32(const gr_sasrec_params* p, const in
     dweight(G1, d3, d3, hs, d, d, gvb + vo.inw);                                       // dW_in = dQKV^T h
     run<E_PLAIN>(gemm(G1, d3, 1, p->in_proj_w[bk], d, 1, T, d, R, d, d3), 1, st);      // dh = dQKV W_in
     hipLaunchKernelGGL(ln_bwd_kernel, dim3(row_blocks(R)), dim3(GT), 0, st, X, (const float*)T, DX, 1,
-                       p->attn_ln_w[bk], stats, bk > 0 ? Y : (float*)nullptr, 3 * (bk - 1) + 2, n, R, d, p->eps,
-                       dr);                                                            // LN_a
+                       p->attn_ln_w[bk], stats, bk > 0 ? Y : (float*)nullptr, sas_site_out(bk - 1), n, R, d,
+                       p->eps, dr);                                                           // LN_a
     ln_sums(T, X, gvb + vo.law, gvb + vo.lab);
   }
   // x0 = item_emb[s] + pos_emb[i]: positions as partial sums over each part's sequences
   hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)(((int64_t)n * d + CS_C - 1) / CS_C), S), dim3(CS_C * CS_R), 0, st,
-                     (const float*)DX, (int64_t)n * d, B, n * d, bchunk, glast + 2 * d, (float*)nullptr, vw,
+                     (const float*)DX, (int64_t)n * d, B, n * d, bchunk, gv + vo.pos, (float*)nullptr, vw,
                      (const float*)nullptr, (const float*)nullptr);
   if (g_item)
     hipLaunchKernelGGL(item_scatter_kernel, dim3((unsigned)((R * d + GT - 1) / GT)), dim3(GT), 0, st, seqs,

@@ -6,6 +6,7 @@ never synchronises.  Argument checking mirrors the ATen errors the reference wou
 import collections
 import ctypes
 import itertools
+import math
 import os
 
 import torch
@@ -1131,111 +1132,73 @@ def _train_params(model):
     return ps + [model.last_layernorm.weight, model.last_layernorm.bias]
 
 
-def _sas_train_fwd(ctx, tiled, seqs, binding, p_drop, seed_snap, params):
-    """Forward of ``_SasTrain`` (tiled False) / ``_SasTrainTiled``: allocate the saved-activation
-    buffers (and the tiled kernels' workspace), launch, keep what the backward needs."""
-    B, n = seqs.shape
-    p = binding.p
-    d, m, nb, H = p.d, p.mlp, p.n_blocks, p.n_heads
-    dev = seqs.device
-    R = B * n
-    e = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)   # noqa: E731
-    bufs = {"xin": e(nb, R, d), "hs": e(nb, R, d), "qkv": e(nb, R, 3 * d), "prob": e(nb, B, H, n, n),
-            "os": e(nb, R, d), "x1": e(nb, R, d), "fs": e(nb, R, d), "zs": e(nb, R, m), "us": e(nb, R, m),
-            "xl": e(R, d)}
-    out = e(B, n, d)
-    err = err_flag(dev)
-    cb = L.SasrecTrainBufs(**{k: v.data_ptr() for k, v in bufs.items()})
-    with L.on(dev):
-        if tiled:
-            nbytes = L.lib().gr_sasrec_train_tiled_workspace_bytes(ctypes.byref(p), B, n)
-            ws = L.workspace(nbytes, dev)
-            L.check(L.lib().gr_sasrec_train_tiled_fwd_f32(ctypes.byref(p), L.ptr(seqs), B, n, float(p_drop), 0,
-                                                          L.ptr(seed_snap), ctypes.byref(cb), L.ptr(out),
-                                                          L.ptr(err), L.ptr(ws), nbytes, L.stream_of(dev)),
-                    "gr_sasrec_train_tiled_fwd_f32")
-        else:
-            L.check(L.lib().gr_sasrec_train_fwd_f32(ctypes.byref(p), L.ptr(seqs), B, n, float(p_drop), 0,
-                                                    L.ptr(seed_snap), ctypes.byref(cb), L.ptr(out), L.ptr(err),
-                                                    L.stream_of(dev)), "gr_sasrec_train_fwd_f32")
-    _check_err(err)
-    ctx.binding, ctx.p_drop, ctx.bufs, ctx.seqs, ctx.seed = binding, p_drop, bufs, seqs, seed_snap
-    ctx.shapes = (B, n, d, m, nb, params[1].shape[0])
-    return out
-
-
-def _sas_train_bwd(ctx, tiled, dout):
-    """Backward of ``_SasTrain`` / ``_SasTrainTiled``: the kernels leave every parameter gradient but
-    the item table's as partial rows of g_vec (one per sequence; the tiled kernels: one per split-k
-    chunk of the rows), summed and sliced here; item-table rows are scattered in the kernel."""
-    B, n, d, m, nb, max_len = ctx.shapes
-    bufs, seqs = ctx.bufs, ctx.seqs
-    dev = seqs.device
-    p = ctx.binding.p
-    vw = L.lib().gr_sasrec_train_vec_width(ctypes.byref(p), n)
-    parts = L.lib().gr_sasrec_train_tiled_parts(ctypes.byref(p), B, n) if tiled else B
-    g_vec = torch.empty((parts, vw), dtype=torch.float32, device=dev)
-    g_item = torch.zeros((p.item_rows, d), dtype=torch.float32, device=dev)
-    cb = L.SasrecTrainBufs(g_vec=g_vec.data_ptr(), **{k: v.data_ptr() for k, v in bufs.items()})
-    dout = dout.contiguous().float()
-    with L.on(dev):
-        if tiled:
-            nbytes = L.lib().gr_sasrec_train_tiled_workspace_bytes(ctypes.byref(p), B, n)
-            ws = L.workspace(nbytes, dev)
-            L.check(L.lib().gr_sasrec_train_tiled_bwd_f32(ctypes.byref(p), L.ptr(seqs), B, n, float(ctx.p_drop), 0,
-                                                          L.ptr(ctx.seed), ctypes.byref(cb), L.ptr(dout),
-                                                          L.ptr(g_item), L.ptr(ws), nbytes, L.stream_of(dev)),
-                    "gr_sasrec_train_tiled_bwd_f32")
-        else:
-            L.check(L.lib().gr_sasrec_train_bwd_f32(ctypes.byref(p), L.ptr(seqs), B, n, float(ctx.p_drop), 0,
-                                                    L.ptr(ctx.seed), ctypes.byref(cb), L.ptr(dout), L.ptr(g_item),
-                                                    L.stream_of(dev)), "gr_sasrec_train_bwd_f32")
-    vec = g_vec.sum(0)   # every parameter's gradient but the item table's, in parameter order
-    shapes = [(d,), (d,), (3 * d, d), (3 * d,), (d, d), (d,), (d,), (d,), (m, d), (m,), (d, m), (d,)] * nb
-    shapes += [(d,), (d,)]
-    grads, off = [], 0
-    for shp in shapes:
-        k = 1
-        for x in shp:
-            k *= x
-        grads.append(vec[off:off + k].view(shp))
-        off += k
-    # rows n.. of pos_emb get zeros (a pad kernel rather than a copy into a zeros tensor, which
-    # keeps memset / memcpy nodes out of a captured step's graph)
-    dpos = torch.nn.functional.pad(vec[off:off + n * d].view(n, d), (0, 0, 0, max_len - n))
-    return (None, None, None, None, g_item, dpos, *grads)
-
-
 class _SasTrain(torch.autograd.Function):
-    """Train-mode SASRec forward (dropout on) and its backward on the kernels of sasrec_train.hip:
-    one launch each.  The backward leaves every parameter gradient but the item table's as a
-    per-sequence partial row of one [B, V] buffer (dW = dG^T A over the sequence's rows, bias and
-    LayerNorm column sums, positional rows), summed over B here; item-table rows are scattered in
-    the kernel."""
+    """Train-mode SASRec forward (dropout on) and its backward on one of the two kernel sets (same
+    saved activations, dropout masks and g_vec layout: csrc/sasrec_train_contract.h).  ``tiled``
+    False: sasrec_train.hip, one launch each, one workgroup and one partial row of g_vec per sequence
+    (n, d <= 64, mlp_layer <= 128).  True: sasrec_train_tiled.hip (n <= 256, d <= 128, mlp_layer <=
+    256), tiled launches over all B * n rows, ``gr_sasrec_train_tiled_parts`` partial rows (split-k
+    chunks of the rows) and a workspace, allocated like the saved buffers (inside a captured step:
+    from the graph's pool).  Every parameter gradient but the item table's is the sum of g_vec's
+    rows, sliced in ``_train_params`` order; item-table rows are scattered in the kernel."""
 
     @staticmethod
-    def forward(ctx, seqs, binding, p_drop, seed_snap, *params):
-        return _sas_train_fwd(ctx, False, seqs, binding, p_drop, seed_snap, params)
+    def _launch(which, ctx, cb, *tensors):
+        """gr_sasrec_train[_tiled]_{fwd,bwd}_f32 on ctx's step."""
+        seqs, p = ctx.seqs, ctx.binding.p
+        B, n = seqs.shape
+        dev = seqs.device
+        name = f"gr_sasrec_train_{'tiled_' if ctx.tiled else ''}{which}_f32"
+        args = [L.ptr(t) for t in tensors]
+        with L.on(dev):
+            if ctx.tiled:
+                nbytes = L.lib().gr_sasrec_train_tiled_workspace_bytes(ctypes.byref(p), B, n)
+                ws = L.workspace(nbytes, dev)
+                args += [L.ptr(ws), nbytes]
+            L.check(getattr(L.lib(), name)(ctypes.byref(p), L.ptr(seqs), B, n, float(ctx.p_drop), 0, L.ptr(ctx.seed),
+                                           ctypes.byref(cb), *args, L.stream_of(dev)), name)
+
+    @staticmethod
+    def forward(ctx, seqs, binding, tiled, p_drop, seed_snap, *params):
+        B, n = seqs.shape
+        p = binding.p
+        d, m, nb, H = p.d, p.mlp, p.n_blocks, p.n_heads
+        R = B * n
+        e = lambda *shape: torch.empty(shape, dtype=torch.float32, device=seqs.device)   # noqa: E731
+        bufs = {"xin": e(nb, R, d), "hs": e(nb, R, d), "qkv": e(nb, R, 3 * d), "prob": e(nb, B, H, n, n),
+                "os": e(nb, R, d), "x1": e(nb, R, d), "fs": e(nb, R, d), "zs": e(nb, R, m), "us": e(nb, R, m),
+                "xl": e(R, d)}
+        out = e(B, n, d)
+        err = err_flag(seqs.device)
+        ctx.binding, ctx.tiled, ctx.p_drop, ctx.bufs, ctx.seqs, ctx.seed = binding, tiled, p_drop, bufs, seqs, seed_snap
+        ctx.shapes = [q.shape for q in params]   # item table, positions, then g_vec's order
+        vw = L.lib().gr_sasrec_train_vec_width(ctypes.byref(p), n)
+        if sum(math.prod(shp) for shp in ctx.shapes[2:]) + n * d != vw:
+            raise RuntimeError(f"_SasTrain: the parameters do not fill a g_vec row of {vw} floats")
+        _SasTrain._launch("fwd", ctx, L.SasrecTrainBufs(**{k: v.data_ptr() for k, v in bufs.items()}), out, err)
+        _check_err(err)
+        return out
 
     @staticmethod
     def backward(ctx, dout):
-        return _sas_train_bwd(ctx, False, dout)
-
-
-class _SasTrainTiled(torch.autograd.Function):
-    """``_SasTrain`` on the tiled kernels of sasrec_train_tiled.hip (d <= 128, n <= 256, mlp_layer <=
-    256): the same saved activations and dropout masks; the products are tiled launches over all
-    B * n rows, and the backward leaves ``gr_sasrec_train_tiled_parts`` partial rows (split-k chunks
-    of the rows) instead of one per sequence.  Both calls take a workspace, allocated like the
-    saved buffers (inside a captured step: from the graph's pool)."""
-
-    @staticmethod
-    def forward(ctx, seqs, binding, p_drop, seed_snap, *params):
-        return _sas_train_fwd(ctx, True, seqs, binding, p_drop, seed_snap, params)
-
-    @staticmethod
-    def backward(ctx, dout):
-        return _sas_train_bwd(ctx, True, dout)
+        seqs, p = ctx.seqs, ctx.binding.p
+        B, n = seqs.shape
+        dev = seqs.device
+        vw = L.lib().gr_sasrec_train_vec_width(ctypes.byref(p), n)
+        parts = L.lib().gr_sasrec_train_tiled_parts(ctypes.byref(p), B, n) if ctx.tiled else B
+        g_vec = torch.empty((parts, vw), dtype=torch.float32, device=dev)
+        g_item = torch.zeros((p.item_rows, p.d), dtype=torch.float32, device=dev)
+        cb = L.SasrecTrainBufs(g_vec=g_vec.data_ptr(), **{k: v.data_ptr() for k, v in ctx.bufs.items()})
+        _SasTrain._launch("bwd", ctx, cb, dout.contiguous().float(), g_item)
+        vec = g_vec.sum(0)
+        grads, off = [], 0
+        for shp in ctx.shapes[2:]:
+            grads.append(vec[off:off + math.prod(shp)].view(shp))
+            off += math.prod(shp)
+        # rows n.. of pos_emb get zeros (a pad kernel rather than a copy into a zeros tensor, which
+        # keeps memset / memcpy nodes out of a captured step's graph)
+        dpos = torch.nn.functional.pad(vec[off:].view(n, p.d), (0, 0, 0, ctx.shapes[1][0] - n))
+        return (None, None, None, None, None, g_item, dpos, *grads)
 
 
 def sasrec_train_forward(model, log_seqs):
@@ -1257,11 +1220,77 @@ def sasrec_train_forward(model, log_seqs):
     seed = dropout_seed(seqs.device)
     snap = seed + 0              # this step's masks (forward and backward read the same word); a kernel, not a copy
     seed.add_(1)
-    fn = _SasTrainTiled if tiled else _SasTrain
-    return fn.apply(seqs, sasrec_binding(model), float(model.dropout), snap, *_train_params(model))
+    return _SasTrain.apply(seqs, sasrec_binding(model), tiled, float(model.dropout), snap, *_train_params(model))
 
 
-class SasTrainStepGraph:
+class _CapturedStep:
+    """A training step (``self._body()``: forward, loss, backward and, with ``self.opt``, the optimizer
+    step) captured once as a graph (hipGraph via ``torch.cuda.graph``) and replayed.  ``_capture``
+    owns the protocol: snapshot what the warm-up moves (the optimizer's parameters, its state tensors
+    and tensor learning rates, the module's buffers), run ``warmup`` steps on a side stream
+    (allocator, autograd and the optimizer's lazily created state), clear the gradients, capture the
+    detached outputs as ``self.out`` (the captured autograd graph and its AccumulateGrad nodes,
+    created on the capture stream, are released, so later eager backwards into the same leaves stay
+    on their own stream), restore the snapshot: the first replay is the first real step.  State the
+    warm-up created starts from zero.
+
+    A subclass that leaves ``graph`` None runs ``_body`` eagerly in ``replay``: that is the path with
+    the transformer / MLPs under torch autograd.  Back-to-back replays of that graph faulted (HSA
+    memory aperture violation) in rocPRIM's unique-by-key partition kernel of the item-embedding
+    backward (profiles/r02_train_graph_diag.txt); a graph of captured memsets and kernels replays
+    correctly back to back (profiles/r03_graph_memset.txt), so round 2's memset-node explanation
+    does not hold, and the fault stays inside that rocPRIM kernel.  Round 2 synchronised the device
+    after every replay; not capturing that path at all makes every path run without a host
+    synchronisation and without the faulting configuration."""
+
+    graph = opt = None
+    _check = False   # a row whose negative population may be short: the reference raises
+
+    def _clear_grads(self):
+        self.opt.zero_grad(set_to_none=True)
+
+    def _capture(self, dev, warmup, module=None):
+        opt = self.opt
+        params = [p for g in opt.param_groups for p in g["params"]] if opt else []
+        state = lambda: [v for p in params for v in opt.state.get(p, {}).values() if torch.is_tensor(v)]   # noqa: E731
+        keep = params + state() + [g["lr"] for g in (opt.param_groups if opt else []) if torch.is_tensor(g["lr"])]
+        keep += list(module.buffers()) if module is not None else []
+        saved = [t.detach().clone() for t in keep]
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            for _ in range(warmup):
+                self._clear_grads()
+                self._body()
+        torch.cuda.current_stream(dev).wait_stream(side)
+        self._clear_grads()
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            self.out = tuple(x.detach() for x in self._body())
+        with torch.no_grad():
+            known = {id(t) for t in keep}
+            for v in state():
+                if id(v) not in known:
+                    v.zero_()
+            for t, old in zip(keep, saved):
+                t.copy_(old)
+
+    def replay(self):
+        """Run one step; returns the step's outputs (captured: its static tensors), with no host
+        synchronisation between replays."""
+        if self.graph is None:
+            out = tuple(x.detach() for x in self._body())
+        else:
+            self.graph.replay()
+            if self.opt is not None:
+                weights_changed()   # the captured optimizer step moved the weights without a version bump
+            out = self.out
+        if self._check:
+            check_errors(self.inputs.device)
+        return out
+
+
+class SasTrainStepGraph(_CapturedStep):
     """The training-side scoring step of SASRec/train.py:131-167 -- negatives (train.py:142),
     scores + sampled BCE (134-158), ``loss = batch_loss / batch_valid_t`` (161-164) and its backward
     into ``feats.grad`` / ``table.grad`` -- captured once as a graph (hipGraph via
@@ -1283,20 +1312,10 @@ class SasTrainStepGraph:
         self.item_num, self.num_neg, self.eps = int(item_num), int(num_neg), float(eps)
         self._check = CHECK or 2 * (inputs.shape[1] + self.num_neg) > self.item_num
         self.seed = torch.tensor([int(seed)], dtype=torch.int64, device=feats.device)
-        side = torch.cuda.Stream(device=feats.device)
-        side.wait_stream(torch.cuda.current_stream(feats.device))
-        with torch.cuda.stream(side):
-            for _ in range(warmup):   # allocator / autograd warm-up outside the capture
-                feats.grad = table.grad = None
-                self._body()
-        torch.cuda.current_stream(feats.device).wait_stream(side)
-        feats.grad = table.grad = None
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            # detached: the captured autograd graph (and its AccumulateGrad nodes, created on the
-            # capture stream) is released, so later eager backwards into the same leaves stay on
-            # their own stream
-            self.out = tuple(x.detach() for x in self._body())
+        self._capture(feats.device, warmup)
+
+    def _clear_grads(self):
+        self.feats.grad = self.table.grad = None
 
     def _body(self):
         negs = neg_samples(self.inputs, self.item_num, self.num_neg, seed_tensor=self.seed)
@@ -1304,14 +1323,8 @@ class SasTrainStepGraph:
         (bl / valid.clamp(min=1.0)).backward()   # batch_loss is 0 when nothing is valid
         return bl, valid
 
-    def replay(self):
-        self.graph.replay()
-        if self._check:   # a row whose negative population may be short: the reference raises
-            check_errors(self.feats.device)
-        return self.out
 
-
-class SasTrainGraph:
+class SasTrainGraph(_CapturedStep):
     """The whole SASRec training step of SASRec/train.py:131-173 -- the transformer forward in
     train mode (dropout on, the drop-in's autograd path), GPU negatives (device-seeded), the fused
     sampled BCE, ``loss = batch_loss / batch_valid_t``, backward and ``optimizer.step()`` --
@@ -1321,9 +1334,10 @@ class SasTrainGraph:
     ``optimizer`` must be capturable (``torch.optim.Adam(..., capturable=True)``: its step counter
     lives on the device).  ``inputs`` [B, n] and ``targets`` [B, n] are the static batch tensors:
     copy each batch into them before ``replay()``, which returns the static ``(batch_loss,
-    batch_valid_t)`` device scalars.  Capture needs a few warm-up steps (allocator, autograd and the
-    optimizer's lazily created state); the parameters and the optimizer state are restored
-    afterwards, so the first replay is the first real training step.  Dropout draws from torch's
+    batch_valid_t)`` device scalars.  The warm-up steps are undone (``_CapturedStep``) and the negative
+    sampler's seed is reset, so the first replay is the first real training step.  Of what is
+    restored, the warm-up moves the parameters and Adam's state; tensor learning rates and module
+    buffers it does not move, so restoring them changes nothing here.  Dropout draws from torch's
     graph-safe generator (fresh masks each replay)."""
 
     def __init__(self, model, optimizer, inputs, targets, item_num, num_neg, eps, seed=0, warmup=3,
@@ -1337,59 +1351,9 @@ class SasTrainGraph:
         self._check = CHECK or 2 * (inputs.shape[1] + self.num_neg) > self.item_num
         dev = inputs.device
         self.seed = torch.tensor([int(seed)], dtype=torch.int64, device=dev)
-        self.graph = None
-        if not capture:
-            return
-        params = [p for g in optimizer.param_groups for p in g["params"]]
-        saved_p = [p.detach().clone() for p in params]
-        saved_s = {id(p): {k: (v.detach().clone() if torch.is_tensor(v) else v)
-                           for k, v in optimizer.state[p].items()} for p in params if p in optimizer.state}
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                self._body()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        optimizer.zero_grad(set_to_none=True)
-        with torch.cuda.graph(self.graph):
-            self.out = tuple(x.detach() for x in self._body())
-        with torch.no_grad():   # undo the warm-up steps: the first replay is the first step
-            for p, s in zip(params, saved_p):
-                p.copy_(s)
-            for p in params:
-                st = optimizer.state.get(p, {})
-                old = saved_s.get(id(p))
-                for k, v in st.items():
-                    if torch.is_tensor(v):
-                        if old is not None and torch.is_tensor(old.get(k)):
-                            v.copy_(old[k])
-                        else:
-                            v.zero_()
-            self.seed.fill_(int(seed))
-
-    def replay(self):
-        """Run one step; returns ``(batch_loss, batch_valid_t)`` (the captured step's static
-        tensors).
-
-        The fused-kernel step (``fused_train`` and a shape sasrec_train_supported takes) is one
-        captured graph, replayed back to back with no host synchronisation.  With the transformer
-        under torch autograd the step runs eagerly instead: back-to-back replays of that graph
-        faulted (HSA memory aperture violation) in rocPRIM's unique-by-key partition kernel of the
-        item-embedding backward (profiles/r02_train_graph_diag.txt); a graph of captured memsets
-        and kernels replays correctly back to back (profiles/r03_graph_memset.txt), so round 2's
-        memset-node explanation does not hold, and the fault stays inside that rocPRIM kernel.
-        Round 2 synchronised the device after every replay; not capturing that path at all makes
-        every path run without a host synchronisation and without the faulting configuration."""
-        if self.graph is None:
-            out = tuple(x.detach() for x in self._body())
-        else:
-            self.graph.replay()
-            weights_changed()
-            out = self.out
-        if self._check:   # a row whose negative population may be short: the reference raises
-            check_errors(self.inputs.device)
-        return out
+        if capture:
+            self._capture(dev, warmup, model)
+            self.seed.fill_(int(seed))   # the warm-up advanced the negative sampler
 
     def _body(self):
         self.opt.zero_grad(set_to_none=True)
@@ -1401,7 +1365,7 @@ class SasTrainGraph:
         return bl, valid
 
 
-class RqTrainGraph:
+class RqTrainGraph(_CapturedStep):
     """One RQ-VAE training step of RQ-VAE/train.py:108-119 -- ``out, rq_loss, indices =
     model(data)`` (every level's Sinkhorn / argmin assignment on the kernels, dropout on),
     ``compute_loss``, ``loss.backward()``, ``clip_grad_norm_(params, 1.0)`` and ``optimizer.step()``
@@ -1418,12 +1382,11 @@ class RqTrainGraph:
 
     A model with ``kmeans_init`` and codebooks not yet initialised is initialised here on
     ``inputs`` -- the reference's first training batch does the same (vq.py:66-67) -- before the
-    capture.  Warm-up steps (allocator, autograd, the optimizer's lazily created state) are undone
-    afterwards, so the first replay is the first real training step.  Dropout draws from torch's
-    graph-safe generator (fresh masks each replay).  On the kernel path (fused MLPs and quantizer)
-    replays run back to back (tests/test_rq_train_gpu.py); with the torch modules (``fused_train =
-    False``, BatchNorm) the step runs eagerly (SasTrainGraph.replay explains why).  ``capture``
-    overrides the choice."""
+    capture.  The warm-up steps are undone afterwards (``_CapturedStep``), so the first replay is the
+    first real training step.  Dropout draws from torch's graph-safe generator (fresh masks each
+    replay).  On the kernel path (fused MLPs and quantizer) replays run back to back
+    (tests/test_rq_train_gpu.py); with the torch modules (``fused_train = False``, BatchNorm) the step
+    runs eagerly (``_CapturedStep`` explains why).  ``capture`` overrides the choice."""
 
     def __init__(self, model, optimizer, inputs, max_norm=1.0, use_sk=True, warmup=3, capture=None):
         L.require_gpu(inputs)
@@ -1441,54 +1404,8 @@ class RqTrainGraph:
         if model.training and any(not q.initted for q in model.rq.vq_layers):
             with torch.no_grad():   # vq.py:66-67: k-means init on the first batch's residuals
                 model(inputs, use_sk=self.use_sk)
-        self.graph = None
-        if not capture:
-            return
-        params = [p for g in optimizer.param_groups for p in g["params"]]
-        saved_p = [p.detach().clone() for p in params]
-        saved_s = {id(p): {k: (v.detach().clone() if torch.is_tensor(v) else v)
-                           for k, v in optimizer.state[p].items()} for p in params if p in optimizer.state}
-        saved_lr = [g["lr"].detach().clone() for g in optimizer.param_groups]
-        # module buffers too: with bn=True every warm-up / capture forward is a train-mode BatchNorm
-        # step that moves running_mean / running_var / num_batches_tracked
-        bufs = list(model.buffers())
-        saved_b = [b.detach().clone() for b in bufs]
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                self._body()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        optimizer.zero_grad(set_to_none=True)
-        with torch.cuda.graph(self.graph):
-            self.out = tuple(x.detach() for x in self._body())
-        with torch.no_grad():   # undo the warm-up steps: the first replay is the first step
-            for p, s in zip(params, saved_p):
-                p.copy_(s)
-            for p in params:
-                st = optimizer.state.get(p, {})
-                old = saved_s.get(id(p))
-                for k, v in st.items():
-                    if torch.is_tensor(v):
-                        if old is not None and torch.is_tensor(old.get(k)):
-                            v.copy_(old[k])
-                        else:
-                            v.zero_()
-            for g, lr in zip(optimizer.param_groups, saved_lr):
-                g["lr"].copy_(lr)
-            for b, sb in zip(bufs, saved_b):
-                b.copy_(sb)
-
-    def replay(self):
-        """Run one step; returns ``(loss, loss_recon, indices)`` (the captured step's static tensors).
-        The kernel path is one captured graph replayed back to back; the torch-module fallback runs
-        eagerly (SasTrainGraph.replay explains why)."""
-        if self.graph is None:
-            return tuple(x.detach() for x in self._body())
-        self.graph.replay()
-        weights_changed()   # the captured AdamW step moved the weights without a version bump
-        return self.out
+        if capture:   # buffers too: with bn=True every train-mode BatchNorm forward moves its running statistics
+            self._capture(dev, warmup, model)
 
     def _body(self):
         self.opt.zero_grad(set_to_none=True)

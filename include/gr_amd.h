@@ -369,7 +369,7 @@ typedef struct gr_sasrec_train_bufs {
                     pos_emb rows [n, d]; the parameter gradients are its sum over B             */
 } gr_sasrec_train_bufs;
 
-/* Floats per sequence in gr_sasrec_train_bufs.g_vec: n_blocks * (4d^2 + 2 d mlp + 9d + mlp) + 2d + n*d. */
+/* Floats per sequence in gr_sasrec_train_bufs.g_vec (csrc/sasrec_train_contract.h sas_vec_width). */
 int32_t gr_sasrec_train_vec_width(const gr_sasrec_params* p, int32_t n);
 
 /* Train-mode forward: seqs[B, n] -> out[B, n, d] (model.py:49-96 with dropout p), saving the

@@ -84,7 +84,8 @@ def child(out):
         json.dump(res, f)
 
 
-def main():
+def main(child=child, script=__file__):
+    """``child`` / ``script``: another case set under the same rule (scripts/ab_train_libs.py)."""
     if sys.argv[1] == "--child":
         return child(sys.argv[2])
     libs = [os.path.abspath(p) for p in sys.argv[1:3]]
@@ -97,7 +98,7 @@ def main():
         for i, lib in enumerate(libs):
             out = os.path.join(tmp, f"{i}_{rep}.json")
             # a failed or hung child ends the whole run: nothing more is started on the GPU
-            subprocess.run(["timeout", "-k", "10", "240", sys.executable, __file__, "--child", out],
+            subprocess.run(["timeout", "-k", "10", "240", sys.executable, script, "--child", out],
                            env=dict(os.environ, GR_AMD_LIB=lib), check=True)
             runs[i].append(json.load(open(out)))
     bad = 0

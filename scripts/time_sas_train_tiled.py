@@ -2,7 +2,7 @@
 B 128, 100k items, 10 negatives, dropout 0.2, Adam as bench.bench_sas_train_step):
 
     module  ops.SasTrainGraph.replay with SASRec.fused_train = False: the transformer as torch modules
-            under autograd (run eagerly, SasTrainGraph.replay explains why) -- the only path this
+            under autograd (run eagerly, ops._CapturedStep explains why) -- the only path this
             shape had before the tiled kernels
     tiled   ops.SasTrainGraph.replay with the defaults: the tiled training kernels
             (csrc/sasrec_train_tiled.hip), the whole step one captured graph

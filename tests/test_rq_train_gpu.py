@@ -151,7 +151,7 @@ def test_graph_replays_back_to_back_equal_synchronised(dev):
 
 
 def test_module_fallback_runs_eagerly_and_matches(dev):
-    """fused_train = False (torch modules): the step is not captured (see SasTrainGraph.replay) and
+    """fused_train = False (torch modules): the step is not captured (see ops._CapturedStep) and
     back-to-back replays equal the same steps issued by hand."""
     from gr_amd import ops
     base = _model(dev, 0.0, False)

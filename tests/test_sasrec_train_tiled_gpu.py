@@ -1,4 +1,4 @@
-"""Tiled SASRec training kernels (csrc/sasrec_train_tiled.hip, ops._SasTrainTiled) against fp64.
+"""Tiled SASRec training kernels (csrc/sasrec_train_tiled.hip, ops._SasTrain) against fp64.
 
 The same comparison as test_sasrec_train_gpu.test_train_edge_shapes_vs_fp64, with its helpers: the
 train-mode forward (SASRec/model.py:49-96 as called by SASRec/train.py:131) and the gradient of
