@@ -19,6 +19,12 @@ GR_ACT_TANH = 3
 GR_ACT_LEAKYRELU = 4
 GR_MAX_LEVELS = 8
 GR_MAX_LINEAR = 8
+# bits of gr_sasrec_plan's mask
+GR_SAS_FUSED, GR_SAS_ROWTILE, GR_SAS_LAYERWISE = 0x1, 0x2, 0x4
+GR_SAS_FUSED_TWO_WAVES, GR_SAS_FUSED_MISALIGNED = 0x8, 0x10
+GR_SAS_B0_EMBED_PROJ, GR_SAS_B0_EMBED_LN_LINEAR, GR_SAS_B0_EMBED_LN = 0x20, 0x40, 0x80
+GR_SAS_ATTN_SCALAR, GR_SAS_ATTN_MFMA, GR_SAS_ATTN_PERSIST, GR_SAS_ATTN_K16 = 0x100, 0x200, 0x400, 0x800
+GR_SAS_ATTN_LAST_TILE, GR_SAS_TAIL, GR_SAS_TAIL_VALU, GR_SAS_PRUNED = 0x1000, 0x2000, 0x4000, 0x8000
 
 _c_int_p = ctypes.POINTER(ctypes.c_int32)
 _vp = ctypes.c_void_p
@@ -103,6 +109,7 @@ SIGNATURES = {
     "gr_sasrec_rank_workspace_bytes": (_sz, [ctypes.POINTER(SasrecParams), _i64, _i32]),
     "gr_sasrec_rank_f32": (ctypes.c_int, [ctypes.POINTER(SasrecParams), _vp, _i64, _i32, _vp, _i32, _vp, _vp,
                                           _sz, _vp, _sz, _vp, _vp]),
+    "gr_sasrec_plan": (_i32, [ctypes.POINTER(SasrecParams), _i64, _i32, _i32]),
     "gr_sasrec_train_vec_width": (_i32, [ctypes.POINTER(SasrecParams), _i32]),
     "gr_sasrec_train_fwd_f32": (ctypes.c_int, [ctypes.POINTER(SasrecParams), _vp, _i64, _i32, _f32,
                                                ctypes.c_uint64, _vp, ctypes.POINTER(SasrecTrainBufs), _vp,

@@ -586,28 +586,35 @@ void attn_k16_kernel(const float* __restrict__ qkv, float* __restrict__ out, int
 
 }  // namespace gr
 
-// Returns GR_ERR_UNSUPPORTED (message untouched) for head widths the kernel is not built for.
+bool gr_attn_mfma_hd(int hd) { return hd == 32 || hd == 64 || hd == 128; }
+
+// The attention kernel of a shape (GR_SAS_ATTN_*): head width 64 / 128 on the persistent grid while
+// its (sequence, head, query tile) count fits an int, width 32 and the rest on attn_mfma_kernel, one
+// workgroup per (sequence, head); GR_SAS_ATTN_SCALAR: not these kernels' (another head width, or
+// B * H past an int).
+// hd 128: 16-key steps at two waves per SIMD (C5: 0.322 -> 0.313 ms per last_hidden,
+// profiles/r06/ab_attn_k16.txt; k16 = option attn_k16); hd 64 measured no faster there and keeps the
+// 32 x 32 steps
+int gr_attn_form(int64_t B, int n, int H, int hd, bool k16) {
+  if (!gr_attn_mfma_hd(hd) || B * H > 0x7fffffffLL) return GR_SAS_ATTN_SCALAR;
+  if (hd == 32 || B * H * ((n + 31) / 32) > 0x7fffffffLL) return GR_SAS_ATTN_MFMA;
+  return hd == 128 && k16 && (int64_t)n * 3 * hd * H * 4 < (1LL << 31) ? GR_SAS_ATTN_K16 : GR_SAS_ATTN_PERSIST;
+}
+
+// form: gr_attn_form's answer for this shape (GR_ERR_UNSUPPORTED when it is not).
 // last_tile_only: only the query tile holding position n-1 (the rows a last-position-only forward
 // needs; every row is computed exactly as in the full launch).
-int gr_attn_mfma_launch(const float* qkv, float* out, int64_t B, int n, int H, int hd, float scale,
+int gr_attn_mfma_launch(int form, const float* qkv, float* out, int64_t B, int n, int H, int hd, float scale,
                         int last_tile_only, hipStream_t st) {
   using namespace gr;
-  if (hd != 32 && hd != 64 && hd != 128) return GR_ERR_UNSUPPORTED;
+  if (form == GR_SAS_ATTN_SCALAR || form != gr_attn_form(B, n, H, hd, form == GR_SAS_ATTN_K16))
+    return GR_ERR_UNSUPPORTED;
   if (!aligned16(qkv) || !aligned16(out)) return GR_ERR_UNSUPPORTED;
-  if (B * H > 0x7fffffffLL) return GR_ERR_UNSUPPORTED;
   const int qt_lo = last_tile_only ? (n - 1) / 32 : 0;
   const int64_t nbh = B * H;
-  if (hd != 32 && nbh * ((n + 31) / 32) <= 0x7fffffffLL) {   // the persistent grid
-    static int simds = 0;
-    if (!simds) {
-      int dev = 0, cus = 0;
-      (void)hipGetDevice(&dev);
-      (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-      simds = 4 * (cus > 0 ? cus : 256);
-    }
-    // hd 128: 16-key steps at two waves per SIMD (C5: 0.322 -> 0.313 ms per last_hidden,
-    // profiles/r06/ab_attn_k16.txt); hd 64 measured no faster there and keeps the 32 x 32 steps
-    if (hd == 128 && option("attn_k16") == 1 && (int64_t)n * 3 * hd * H * 4 < (1LL << 31)) {
+  if (form != GR_SAS_ATTN_MFMA) {   // the persistent grid
+    const int simds = 4 * cu_count();
+    if (form == GR_SAS_ATTN_K16) {
       const int wx2 = (2 * simds + 7) / 8;
       hipLaunchKernelGGL(attn_k16_kernel<128>, dim3(8 * wx2), dim3(64), 0, st, qkv, out, n, H, scale, (int)nbh, qt_lo, wx2);
       return check_launch("sasrec attention (16-key steps)");

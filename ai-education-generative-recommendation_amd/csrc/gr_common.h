@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cmath>
 #include <string>
 
 #include "gr_amd.h"
@@ -38,6 +39,9 @@ inline int check_launch(const char* what) {
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// The attention scale q * sqrt(1 / head width) (functional.py:6578), rounded once from double.
+inline float sas_scale(int hd) { return (float)std::sqrt(1.0 / (double)hd); }
 
 // Bijective XCD-aware remap of a 1-D workgroup id (cdna_hip_programming.md §5 T1): blocks that the
 // dispatcher deals to one XCD (orig % 8 equal) get consecutive logical ids, so neighbouring tiles
@@ -339,22 +343,37 @@ bool gr_rq_small_ok(int64_t n, int32_t n_linear, const int32_t* dims, int32_t L,
 int gr_rq_small_launch(const float* x, int64_t n, const int32_t* dims, const float* const* biases,
                        const float* packed, float* h1_scratch, float* h2_scratch, int32_t L, const int32_t* K,
                        const float* const* codebooks, int64_t* idx_out, float* z_out, hipStream_t st);
-int gr_sasrec_fused_launch(const gr_sasrec_params* p, const int64_t* seqs, int64_t B, int32_t n,
-                           float* out, int32_t last_only, int32_t* err, hipStream_t st, int64_t* init_out = nullptr, int64_t init_val = 0);
-int gr_attn_mfma_launch(const float* qkv, float* out, int64_t B, int n, int H, int hd, float scale,
+// SASRec inference (sasrec.hip plans and drives; each *_ok below is defined next to the launcher it
+// guards, and is both what sas_plan asks and that launcher's own first test).
+// gr_sasrec_fused_ok: 1 the fused kernel takes the shape, 0 another shape, -1 a fused shape with a
+// parameter pointer null or not 16-byte aligned.
+int gr_sasrec_fused_ok(const gr_sasrec_params* p, int32_t n);
+int gr_sasrec_fused_launch(const gr_sasrec_params* p, const int64_t* seqs, int64_t B, int32_t n, float* out,
+                           int32_t last_only, bool two_waves, int32_t* err, hipStream_t st,
+                           int64_t* init_out = nullptr, int64_t init_val = 0);
+// The MFMA attention kernels' head widths, and which of them a shape runs (GR_SAS_ATTN_MFMA /
+// _PERSIST / _K16; GR_SAS_ATTN_SCALAR: none of them, sasrec.hip's causal_attn_kernel).
+bool gr_attn_mfma_hd(int hd);
+int gr_attn_form(int64_t B, int n, int H, int hd, bool k16);
+int gr_attn_mfma_launch(int form, const float* qkv, float* out, int64_t B, int n, int H, int hd, float scale,
                         int last_tile_only, hipStream_t st);
 int gr_score_launch(const float* h, int64_t B, int32_t d, const float* table, int64_t rows,
                     float* logits, int64_t ld, hipStream_t st);
+bool gr_rowtile_shape_ok(const gr_sasrec_params* p);   // d and mlp of the row-tile kernels
+bool gr_post_attn_ok(const gr_sasrec_params* p, int blk, const float* ln_next_w, const float* ln_next_b,
+                     const float* wn, const float* bn, int nout, int64_t M);
 int gr_post_attn_launch(const gr_sasrec_params* p, int blk, const float* ln_next_w, const float* ln_next_b,
                         const float* wn, const float* bn, int nout, const float* O, float* X, float* H,
                         int64_t M, hipStream_t st);
+bool gr_embed_ln_ok(const gr_sasrec_params* p, int64_t M, const float* wn, const float* bn, int nout);
 int gr_embed_ln_launch(const gr_sasrec_params* p, const int64_t* seqs, int64_t M, int32_t n, const float* wn,
                        const float* bn, int nout, float* X, float* H, int32_t* err, hipStream_t st);
+bool gr_embed_proj_ok(const gr_sasrec_params* p, int64_t M, const float* wn, const float* bn, int nout);
 int gr_embed_proj_launch(const gr_sasrec_params* p, const int64_t* seqs, int64_t M, int32_t n, const float* wn,
                          const float* bn, int nout, float* X, float* QKV, int32_t* err, hipStream_t st);
-bool gr_sasrec_tail_ok(const gr_sasrec_params* p, int32_t n);
+bool gr_sasrec_tail_ok(const gr_sasrec_params* p, int blk, int64_t B, int32_t n);
 int gr_sasrec_tail_h_launch(const gr_sasrec_params* p, int blk, const float* X, const float* Hs,
-                            int64_t B, int32_t n, float* out, hipStream_t st);
+                            int64_t B, int32_t n, float* out, bool valu, hipStream_t st);
 int gr_rq_rows_launch(const float* x, int64_t n, int64_t call_m, const int64_t* group_ptr, int64_t n_groups,
                       int32_t n_linear, const int32_t* dims, const float* const* weights, const float* const* biases,
                       const float* const* bn_mean, const float* const* bn_var, const float* const* bn_w,

@@ -357,13 +357,7 @@ int gr_linear_launch(const float* x, int64_t m, int32_t k, const float* w, int32
   // K = 128, n % 128 == 0, long m: w slices resident in registers (linear_wres_kernel; option lin_wres)
   if (k == WR_K && n % WR_BN == 0 && !residual && (act == GR_ACT_NONE || act == GR_ACT_RELU) &&
       m >= (int64_t)WR_BM * 256 && ldy * WR_BM < (1LL << 31) && option("lin_wres") != 0) {
-    static int cus = 0;
-    if (!cus) {
-      int dev = 0;
-      if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-        cus = 256;
-    }
+    const int cus = cu_count();
     const int groups = n / WR_BN;
     const int per = cus / groups > 0 ? cus / groups : 1;   // one workgroup per CU
     auto kern = act == GR_ACT_RELU ? linear_wres_kernel<GR_ACT_RELU> : linear_wres_kernel<GR_ACT_NONE>;

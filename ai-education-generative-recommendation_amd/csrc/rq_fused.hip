@@ -799,13 +799,7 @@ int gr_rq_encoder_fused_launch(const float* x, int64_t n, int32_t n_linear, cons
     const int rc = gr_rq_encoder_pack_launch(n_linear, dims, weights, pack, st);
     if (rc) return rc;
   }
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-      cus = 256;
-  }
+  const int cus = cu_count();
   const int csplit = kb < dims[0] ? kb / FXC : dims[0] / FXC;
   const bool can_split = scratch && 2 * csplit * FXC == dims[0];
   // A short call (at most a quarter tile per CU, e.g. the reference's batch of 64 items): every tile

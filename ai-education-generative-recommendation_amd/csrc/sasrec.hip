@@ -211,37 +211,97 @@ __global__ __launch_bounds__(256) void rank_kernel(const float* __restrict__ log
   if (threadIdx.x == 0) ranks[b] = part[0] + part[1] + part[2] + part[3] + 1;
 }
 
+// ---------------------------------------------------------------------------------- plan
+// Everything a forward decides before it launches, from the shape, the batch, the options and the
+// alignment of the parameters, as GR_SAS_* bits (gr_sasrec_plan returns their union).  The driver
+// below only executes it: no launch is ever tried to find out whether it runs.
+struct SasPlan {
+  int pipe;     // GR_SAS_FUSED, GR_SAS_ROWTILE or GR_SAS_LAYERWISE
+  int block0;   // row-tile: GR_SAS_B0_EMBED_PROJ, _EMBED_LN_LINEAR or _EMBED_LN
+  int attn;     // GR_SAS_ATTN_* of the blocks that run attention; 0: no block does
+  int flags;    // GR_SAS_FUSED_TWO_WAVES, _FUSED_MISALIGNED, _ATTN_LAST_TILE, _TAIL, _TAIL_VALU, _PRUNED
+  bool has(int f) const { return flags & f; }
+};
+
+// What block i's post_attn kernel (row-tile) appends to the block: the LayerNorm its consumer reads
+// (the next block's LN_a, or the last one) and that block's Q|K|V in-projection -- none (wn = null)
+// after the final block and before an H-form tail, which works on LN_a(X): no K|V of its B n rows.
+struct SasNext {
+  const float *ln_w, *ln_b, *wn, *bn;
+  int nout;
+};
+static SasNext next_of(const gr_sasrec_params* p, int i, bool tail) {
+  const int nb = p->n_blocks;
+  if (i == nb - 1) return {p->last_ln_w, p->last_ln_b, nullptr, nullptr, 0};
+  if (tail && i == nb - 2) return {p->attn_ln_w[i + 1], p->attn_ln_b[i + 1], nullptr, nullptr, 0};
+  return {p->attn_ln_w[i + 1], p->attn_ln_b[i + 1], p->in_proj_w[i + 1], p->in_proj_b[i + 1], 3 * p->d};
+}
+
+// p has passed check_params (the workspace queries: at least n_heads >= 1).
+static SasPlan sas_plan(const gr_sasrec_params* p, int64_t B, int32_t n, int last_only) {
+  const int d = p->d, H = p->n_heads, hd = d / H, nb = p->n_blocks, cus = cu_count();
+  const int64_t rows = B * n, fused = option("sas_fused");
+  if (const int ok = fused >= 1 ? gr_sasrec_fused_ok(p, n) : 0) {
+    // Which form (sas_fused 2 = auto, 3 = always two waves).  The one-wave kernel runs in rounds of
+    // 4 x CUs sequences (one wave per SIMD, ~58 us per round at C3's shape); the two-wave kernel takes
+    // 0.63 of that round for up to 2 x CUs sequences (one wave per SIMD) and ~0.5 round per further
+    // 2 x CUs (two waves per SIMD overlap little: the MFMA and VALU work per SIMD is the bound), so
+    // it wins when k = ceil(B / 2 CUs) is odd (profiles/r05/ab_fused_waves.txt).
+    const int64_t k2 = (B + 2 * cus - 1) / (2 * cus), k1 = (B + 4 * cus - 1) / (4 * cus);
+    const double t2 = k2 == 1 ? 0.63 : 0.5 * (double)k2 + 0.03;
+    const bool two = n > 32 && (fused == 3 || (fused == 2 && t2 < (double)k1));
+    return {GR_SAS_FUSED, 0, 0, (two ? GR_SAS_FUSED_TWO_WAVES : 0) | (ok < 0 ? GR_SAS_FUSED_MISALIGNED : 0)};
+  }
+  const int form = gr_attn_form(B, n, H, hd, option("attn_k16") == 1);
+  // the final block of a last-position forward: the one-query tail wherever its kernel runs (its
+  // VALU reductions when B <= CUs: one sequence per CU is latency-bound)
+  const bool tail = last_only && gr_sasrec_tail_ok(p, nb - 1, B, n);
+  const int tail_bits = !tail ? 0 : B <= cus ? GR_SAS_TAIL | GR_SAS_TAIL_VALU : GR_SAS_TAIL;
+  const int attn = nb - tail > 0 ? form : 0;   // the tail replaces the final block's attention
+  // d = 128 (C5): the row-tile kernels, when each launch run_rowtile will make is one its launcher
+  // takes; a last-position forward ends in the tail there.  Block 0: embed + LN_a0 + in-projection
+  // in one kernel with 32-column slices of W_in resident in registers (embed_proj_kernel, option
+  // emb_proj), else embed + LN_a0 -> H and a plain GEMM (folding the GEMM into embed_ln_kernel
+  // measured slower: 218 us vs 37 + 133 at C5); later blocks fold it into post_attn (198 us vs
+  // 115 + 97 for the final block's K|V).
+  if (option("sas_rowtile") == 1 && nb >= 1 && gr_rowtile_shape_ok(p) && gr_attn_mfma_hd(hd) &&
+      (!last_only || tail) && attn != GR_SAS_ATTN_SCALAR) {
+    const bool ln = gr_embed_ln_ok(p, rows, nullptr, nullptr, 0);
+    const int b0 = !attn ? (ln ? GR_SAS_B0_EMBED_LN : 0)
+                   : option("emb_proj") == 1 && gr_embed_proj_ok(p, rows, p->in_proj_w[0], p->in_proj_b[0], 3 * d)
+                       ? GR_SAS_B0_EMBED_PROJ
+                       : (ln ? GR_SAS_B0_EMBED_LN_LINEAR : 0);
+    bool ok = b0 != 0;
+    for (int i = 0; ok && i < nb - tail; ++i) {
+      const SasNext nx = next_of(p, i, tail);
+      ok = gr_post_attn_ok(p, i, nx.ln_w, nx.ln_b, nx.wn, nx.bn, nx.nout, rows);
+    }
+    if (ok) return {GR_SAS_ROWTILE, b0, attn, tail_bits};
+  }
+  // layer-wise without the tail: only position n-1 of the final block is needed past its attention
+  // (and of that only the last query tile, which the scalar kernel cannot select), when that saves work
+  const bool pruned = last_only && !tail && nb >= 1 && n >= 2 && (int64_t)n * p->mlp >= 2LL * d + p->mlp;
+  const int pruned_bits = !pruned ? 0 : attn != GR_SAS_ATTN_SCALAR ? GR_SAS_PRUNED | GR_SAS_ATTN_LAST_TILE : GR_SAS_PRUNED;
+  return {GR_SAS_LAYERWISE, 0, attn, tail_bits | pruned_bits};
+}
+
 // ---------------------------------------------------------------------------------- driver
 struct SasWs {
   float *x, *h, *qkv, *o, *f;
 };
 
-// The fused kernel (sasrec_fused.hip) covers n <= 64, d <= 64; it needs only the [B, d] last
-// hidden states.  Must agree with the shape test of gr_sasrec_fused_launch.
-static bool fused_ok(const gr_sasrec_params* p, int32_t n) {
-  return option("sas_fused") >= 1 && n <= 64 && p->d <= 64 && p->d % 8 == 0 &&
-         (p->d / p->n_heads) % 8 == 0 && p->mlp <= 128 && p->n_blocks <= 8;
-}
-
-static size_t ws_layout(const gr_sasrec_params* p, int64_t B, int32_t n, char* base, SasWs* w) {
-  if (fused_ok(p, n)) {
-    if (w) {
-      *w = SasWs{};
-      w->h = reinterpret_cast<float*>(base);
-    }
+// The fused kernel (sasrec_fused.hip) needs only the [B, d] last hidden states.
+static size_t ws_layout(const SasPlan& s, const gr_sasrec_params* p, int64_t B, int32_t n, char* base, SasWs* w) {
+  auto at = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
+  if (s.pipe == GR_SAS_FUSED) {
+    if (w) *w = SasWs{nullptr, at(0), nullptr, nullptr, nullptr};
     return align_up((size_t)B * p->d * 4, 256) + 256;
   }
   const size_t rows = (size_t)B * n;
   const size_t sx = align_up(rows * p->d * 4, 256);
   const size_t sq = align_up(rows * 3 * p->d * 4, 256);
   const size_t sf = align_up(rows * (size_t)p->mlp * 4, 256);
-  if (w) {
-    w->x = reinterpret_cast<float*>(base);
-    w->h = reinterpret_cast<float*>(base + sx);
-    w->o = reinterpret_cast<float*>(base + 2 * sx);
-    w->qkv = reinterpret_cast<float*>(base + 3 * sx);
-    w->f = reinterpret_cast<float*>(base + 3 * sx + sq);
-  }
+  if (w) *w = SasWs{at(0), at(sx), at(3 * sx), at(2 * sx), at(3 * sx + sq)};   // in memory: x, h, o, qkv, f
   return 3 * sx + sq + sf + 256;
 }
 
@@ -263,6 +323,13 @@ static int check_params(const gr_sasrec_params* p, int64_t B, int32_t n) {
   return GR_OK;
 }
 
+// The plan has asked every launcher's predicate: GR_ERR_UNSUPPORTED from one of them now is a bug
+// of this file, reported as such and never answered with another path.
+static int planned(int rc, const char* launcher) {
+  if (rc != GR_ERR_UNSUPPORTED) return rc;
+  return fail(rc, std::string("sasrec: ") + launcher + " refused a launch its predicate had accepted");
+}
+
 static int run_layernorm(const float* in, int64_t rows, int d, int64_t stride, int64_t off,
                          const float* w, const float* b, float eps, float* out, hipStream_t st) {
   hipLaunchKernelGGL(layernorm_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, in, rows,
@@ -270,210 +337,161 @@ static int run_layernorm(const float* in, int64_t rows, int d, int64_t stride, i
   return check_launch("sasrec layernorm");
 }
 
-// Rows the final layernorm reads after run_forward: `rows` (B*n for a full forward, B when the
-// final block ran on the last positions only) at x + (r * stride + off) * d.
-struct SasOut {
-  const float* x;
-  int64_t stride, off;
-  bool done;   // the final hidden states were written by the last-position tail (LN included)
-};
-
 static int run_gather_last(const float* src, int64_t B, int n, int d, float* dst, hipStream_t st) {
   const int64_t tot = B * (d / 4);
-  hipLaunchKernelGGL(gather_last_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, src, B,
-                     n, d, dst);
+  hipLaunchKernelGGL(gather_last_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, src, B, n, d, dst);
   return check_launch("sasrec gather");
 }
 
-// last_only: the caller needs position n-1 only (model.py:104), so the FINAL block's attention
-// runs for the query tile holding it and its out-proj / FFN / residuals on the B last rows —
-// each of those rows computed by the same kernels with the same per-row instruction sequence as
-// the full forward (bitwise equal).  Earlier blocks still produce every position (they are the
-// final block's keys and values).
-// d = 128 (C5): row-tile fusions (sasrec_rowtile.hip) between the attention launches —
-//   embed + LN_a0 | per block: in-proj, attention, post_attn (out-proj + residual + LN_f + FFN +
-//   residual + the next LayerNorm) | final block for position n-1: K/V projection + tail.
-// full_out (full forward only): the [B*n, d] output; the last block's post_attn writes
-// LN_last(X) straight into it.
-static int run_forward_rowtile(const gr_sasrec_params* p, const int64_t* seqs, int64_t B, int32_t n,
-                               const SasWs& w, int32_t* err, int last_only, SasOut* fin, float* tail_out,
-                               float* full_out, hipStream_t st) {
-  const int d = p->d, H = p->n_heads, hd = d / H;
+static size_t scalar_attn_lds(int hd, int n) {
+  return (size_t)(ATT_QT + ATT_KC) * (hd + 1) * 4 + (size_t)ATT_QT * n * 4;
+}
+
+// w.qkv -> w.o by the planned kernel; last_tile: the query tile of position n-1 only.
+static int run_attention(const SasPlan& s, const SasWs& w, int64_t B, int n, int H, int hd, bool last_tile,
+                         hipStream_t st) {
+  if (s.attn != GR_SAS_ATTN_SCALAR)
+    return planned(gr_attn_mfma_launch(s.attn, w.qkv, w.o, B, n, H, hd, sas_scale(hd), last_tile, st),
+                   "gr_attn_mfma_launch");
+  hipLaunchKernelGGL(causal_attn_kernel, dim3((unsigned)(B * H), (unsigned)((n + ATT_QT - 1) / ATT_QT)), dim3(256),
+                     scalar_attn_lds(hd, n), st, w.qkv, w.o, n, H, hd, sas_scale(hd));
+  return check_launch("sasrec attention");
+}
+
+// d = 128 (C5): row-tile fusions (sasrec_rowtile.hip) between the attention launches --
+//   embed + LN_a0 + in-proj | per block: attention, post_attn (out-proj + residual + LN_f + FFN +
+//   residual + the next LayerNorm + the next in-proj) | last position: the tail on LN_a(X) in w.qkv.
+// h: the [B, d] (tail) or [B*n, d] output; the last block's post_attn writes LN_last(X) into it.
+static int run_rowtile(const gr_sasrec_params* p, const SasPlan& s, const int64_t* seqs, int64_t B, int32_t n,
+                       const SasWs& w, int32_t* err, float* h, hipStream_t st) {
+  const int d = p->d, H = p->n_heads, nb = p->n_blocks;
   const int64_t rows = B * n;
-  const int nb = p->n_blocks;
-  const bool tail = last_only && tail_out && gr_sasrec_tail_ok(p, n);
-  // block i's in-projection, fused into the kernel that produces its LayerNorm input: Q|K|V, or
-  // none for the final block of a last-position forward (wn = null: that kernel writes the
-  // LayerNorm output, [rows x d]): its one-query tail works on LN_a(X) itself (sas_tail_h2_kernel),
-  // so no K|V projection of its B n rows is computed
-  auto proj = [&](int i, const float** wn, const float** bn, int* nout) {
-    if (tail && i == nb - 1) {
-      *wn = *bn = nullptr;
-      *nout = 0;
-      return;
-    }
-    *wn = p->in_proj_w[i];
-    *bn = p->in_proj_b[i];
-    *nout = 3 * d;
-  };
-  const float *wn, *bn;
-  int nout;
-  // block 0: embed + LN_a0 -> H, then the in-projection as a plain GEMM (folding it into the
-  // embed kernel measured slower: 218 us vs 37 + 133 at C5, its weight fragments come from L2
-  // with one 16-B piece per row per lane); later blocks fold it into post_attn (198 us vs
-  // 115 + 97 for the final block's K|V)
-  // with 32-column slices of W_in resident in registers over a persistent tile range
-  // (embed_proj_kernel, option emb_proj) the two fold into one kernel
-  proj(0, &wn, &bn, &nout);
-  int rc = !wn ? gr_embed_ln_launch(p, seqs, rows, n, nullptr, nullptr, 0, w.x, w.qkv, err, st)   // H-form tail
-           : option("emb_proj") == 1 ? gr_embed_proj_launch(p, seqs, rows, n, wn, bn, nout, w.x, w.qkv, err, st)
-                                     : GR_ERR_UNSUPPORTED;
-  if (rc == GR_ERR_UNSUPPORTED) {
-    rc = gr_embed_ln_launch(p, seqs, rows, n, nullptr, nullptr, 0, w.x, w.h, err, st);
-    if (rc) return rc;
-    rc = gr_linear_launch(w.h, rows, d, wn, nout, bn, nullptr, 0, GR_ACT_NONE, w.qkv, nout, st);
+  const bool tail = s.has(GR_SAS_TAIL);
+  int rc;
+  if (s.block0 == GR_SAS_B0_EMBED_PROJ) {
+    rc = planned(gr_embed_proj_launch(p, seqs, rows, n, p->in_proj_w[0], p->in_proj_b[0], 3 * d, w.x, w.qkv, err, st),
+                 "gr_embed_proj_launch");
+  } else {   // LN_a0(X): block 0's in-projection reads it from w.h, a one-block tail from w.qkv
+    float* ln = s.block0 == GR_SAS_B0_EMBED_LN ? w.qkv : w.h;
+    rc = planned(gr_embed_ln_launch(p, seqs, rows, n, nullptr, nullptr, 0, w.x, ln, err, st), "gr_embed_ln_launch");
+    if (!rc && ln == w.h)
+      rc = gr_linear_launch(w.h, rows, d, p->in_proj_w[0], 3 * d, p->in_proj_b[0], nullptr, 0, GR_ACT_NONE, w.qkv, 3 * d, st);
   }
+  for (int i = 0; !rc && i < nb; ++i) {
+    const bool last = i == nb - 1;
+    if (last && tail)
+      return planned(gr_sasrec_tail_h_launch(p, i, w.x, w.qkv, B, n, h, s.has(GR_SAS_TAIL_VALU), st),
+                     "gr_sasrec_tail_h_launch");
+    rc = run_attention(s, w, B, n, H, d / H, false, st);
+    if (rc) return rc;
+    const SasNext nx = next_of(p, i, tail);
+    rc = planned(gr_post_attn_launch(p, i, nx.ln_w, nx.ln_b, nx.wn, nx.bn, nx.nout, w.o, w.x, last ? h : w.qkv, rows, st),
+                 "gr_post_attn_launch");
+  }
+  return rc;
+}
+
+// Block i past its attention, on m rows: x += o.W_o^T + b_o; h = LN_f(x); f = relu(h.W_1^T + b_1);
+// x += f.W_2^T + b_2 (model.py:84-94).
+static int run_block_rest(const gr_sasrec_params* p, int i, const float* o, float* x, float* h, float* f, int64_t m,
+                          hipStream_t st) {
+  const int d = p->d, mlp = p->mlp;
+  int rc = gr_linear_launch(o, m, d, p->out_proj_w[i], d, p->out_proj_b[i], x, d, GR_ACT_NONE, x, d, st);
+  if (!rc) rc = run_layernorm(x, m, d, 1, 0, p->ffn_ln_w[i], p->ffn_ln_b[i], p->eps, h, st);
+  if (!rc) rc = gr_linear_launch(h, m, d, p->ffn1_w[i], mlp, p->ffn1_b[i], nullptr, 0, GR_ACT_RELU, f, mlp, st);
+  if (!rc) rc = gr_linear_launch(f, m, mlp, p->ffn2_w[i], d, p->ffn2_b[i], x, d, GR_ACT_NONE, x, d, st);
+  return rc;
+}
+
+// One kernel per op.  last_only: the caller needs position n-1 only (model.py:104), so the FINAL
+// block is the one-query tail (sasrec_tail.hip) on LN_a(X), which writes the final hidden states,
+// last LayerNorm included; or, pruned, its attention runs for the query tile holding n-1 and the
+// rest of the block on the B last rows -- the same kernels and per-row instruction sequence as the
+// full forward (bitwise equal).  Earlier blocks still produce every position (its keys and values).
+static int run_layerwise(const gr_sasrec_params* p, const SasPlan& s, const int64_t* seqs, int64_t B, int32_t n,
+                         const SasWs& w, int32_t* err, int last_only, float* h, hipStream_t st) {
+  const int d = p->d, H = p->n_heads, nb = p->n_blocks;
+  const int64_t rows = B * n, tot = rows * (d / 4);
+  hipLaunchKernelGGL(embed_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, seqs, rows, n, d,
+                     p->item_emb, p->item_rows, p->pos_emb, w.x, err);
+  int rc = check_launch("sasrec embed");
   if (rc) return rc;
-  const float scale = (float)std::sqrt(1.0 / (double)hd);
+  if (s.attn == GR_SAS_ATTN_SCALAR && scalar_attn_lds(d / H, n) > 64 * 1024 &&
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&causal_attn_kernel),
+                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)scalar_attn_lds(d / H, n)) != hipSuccess)
+    return fail(GR_ERR_HIP, "sasrec attention: cannot raise the LDS limit");
   for (int i = 0; i < nb; ++i) {
     const bool last = i == nb - 1;
-    if (last && tail) {   // w.qkv holds LN_a(X) [rows x d]
-      rc = gr_sasrec_tail_h_launch(p, i, w.x, w.qkv, B, n, tail_out, st);
-      if (rc) return rc;
-      fin->done = true;
-      return GR_OK;
-    }
-    rc = gr_attn_mfma_launch(w.qkv, w.o, B, n, H, hd, scale, 0, st);
+    rc = run_layernorm(w.x, rows, d, 1, 0, p->attn_ln_w[i], p->attn_ln_b[i], p->eps, w.h, st);
     if (rc) return rc;
-    if (!last) {
-      proj(i + 1, &wn, &bn, &nout);
-      rc = gr_post_attn_launch(p, i, p->attn_ln_w[i + 1], p->attn_ln_b[i + 1], wn, bn, nout, w.o, w.x, w.qkv,
-                               rows, st);
-    } else {
-      rc = gr_post_attn_launch(p, i, p->last_ln_w, p->last_ln_b, nullptr, nullptr, 0, w.o, w.x,
-                               full_out ? full_out : w.h, rows, st);
-    }
+    if (last && s.has(GR_SAS_TAIL))
+      return planned(gr_sasrec_tail_h_launch(p, i, w.x, w.h, B, n, h, s.has(GR_SAS_TAIL_VALU), st),
+                     "gr_sasrec_tail_h_launch");
+    rc = gr_linear_launch(w.h, rows, d, p->in_proj_w[i], 3 * d, p->in_proj_b[i], nullptr, 0, GR_ACT_NONE, w.qkv, 3 * d, st);
+    if (!rc) rc = run_attention(s, w, B, n, H, d / H, last && s.has(GR_SAS_ATTN_LAST_TILE), st);
     if (rc) return rc;
-  }
-  if (full_out) {
-    fin->done = true;           // LN_last(X) of every row is in full_out
-    return GR_OK;
-  }
-  // last position of LN_last(X) (a tail-unsupported shape): gather it
-  rc = run_gather_last(w.h, B, n, d, tail_out, st);
-  if (rc) return rc;
-  fin->done = true;
-  return GR_OK;
-}
-
-static bool rowtile_ok(const gr_sasrec_params* p, int32_t n) {
-  const int hd = p->d / p->n_heads;
-  return option("sas_rowtile") == 1 && p->d == 128 && p->n_blocks >= 1 &&
-         (p->mlp == 32 || p->mlp == 64 || p->mlp == 128) && (hd == 32 || hd == 64 || hd == 128) && n >= 1;
-}
-
-static int run_forward(const gr_sasrec_params* p, const int64_t* seqs, int64_t B, int32_t n,
-                       const SasWs& w, int32_t* err, int last_only, SasOut* fin, float* tail_out,
-                       hipStream_t st, float* full_out = nullptr) {
-  const int d = p->d, H = p->n_heads, hd = d / H;
-  const int64_t rows = B * n;
-  *fin = SasOut{w.x, n, n - 1, false};
-  if (rowtile_ok(p, n) && (last_only ? tail_out != nullptr : full_out != nullptr)) {
-    const int rc = run_forward_rowtile(p, seqs, B, n, w, err, last_only, fin, tail_out, full_out, st);
-    if (rc != GR_ERR_UNSUPPORTED) return rc;
-    clear_error();
-    *fin = SasOut{w.x, n, n - 1, false};
-  }
-  {
-    const int64_t tot = rows * (d / 4);
-    hipLaunchKernelGGL(embed_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, seqs,
-                       rows, n, d, p->item_emb, p->item_rows, p->pos_emb, w.x, err);
-    int rc = check_launch("sasrec embed");
-    if (rc) return rc;
-  }
-  const float scale = (float)std::sqrt(1.0 / (double)hd);
-  const size_t att_lds = (size_t)(ATT_QT + ATT_KC) * (hd + 1) * 4 + (size_t)ATT_QT * n * 4;
-  if (att_lds > 64 * 1024) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&causal_attn_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)att_lds) != hipSuccess)
-      return fail(GR_ERR_HIP, "sasrec attention: cannot raise the LDS limit");
-  }
-  *fin = SasOut{w.x, n, n - 1, false};
-  // the pruned final block keeps [B, d] x / h and [B, mlp] f in the (then free) FFN buffer
-  const bool prune = last_only && n >= 2 && (int64_t)n * p->mlp >= 2LL * d + p->mlp;
-  for (int i = 0; i < p->n_blocks; ++i) {
-    const bool last_blk = prune && i == p->n_blocks - 1;
-    int rc = run_layernorm(w.x, rows, d, 1, 0, p->attn_ln_w[i], p->attn_ln_b[i], p->eps, w.h, st);
-    if (rc) return rc;
-    if (last_only && tail_out && i == p->n_blocks - 1) {
-      // final block for position n-1 only: the one-query tail (sasrec_tail.hip) on LN_a(X) writes
-      // the final hidden states, last LayerNorm included
-      rc = gr_sasrec_tail_h_launch(p, i, w.x, w.h, B, n, tail_out, st);
-      if (rc == GR_OK) {
-        fin->done = true;
-        return GR_OK;
-      }
-      if (rc != GR_ERR_UNSUPPORTED) return rc;
-      clear_error();   // shape outside the tail kernel: the full final block below
-    }
-    rc = gr_linear_launch(w.h, rows, d, p->in_proj_w[i], 3 * d, p->in_proj_b[i], nullptr, 0,
-                          GR_ACT_NONE, w.qkv, 3 * d, st);
-    if (rc) return rc;
-    rc = gr_attn_mfma_launch(w.qkv, w.o, B, n, H, hd, scale, last_blk ? 1 : 0, st);   // attn.hip
-    if (rc == GR_ERR_UNSUPPORTED) {                                   // other head widths
-      clear_error();
-      hipLaunchKernelGGL(causal_attn_kernel, dim3((unsigned)(B * H), (unsigned)((n + ATT_QT - 1) / ATT_QT)),
-                         dim3(256), att_lds, st, w.qkv, w.o, n, H, hd, scale);
-      rc = check_launch("sasrec attention");
-    }
-    if (rc) return rc;
-    if (last_blk) {
+    if (last && s.has(GR_SAS_PRUNED)) {
       float* xl = w.f;                 // [B, d] residual stream of the last positions
       float* hl = w.f + B * d;         // [B, d] layernorm output
       float* fl = w.f + 2 * B * d;     // [B, mlp] FFN hidden
       float* ol = w.h;                 // [B, d] attention output rows
       rc = run_gather_last(w.o, B, n, d, ol, st);
       if (!rc) rc = run_gather_last(w.x, B, n, d, xl, st);
-      if (!rc) rc = gr_linear_launch(ol, B, d, p->out_proj_w[i], d, p->out_proj_b[i], xl, d, GR_ACT_NONE, xl, d, st);
-      if (!rc) rc = run_layernorm(xl, B, d, 1, 0, p->ffn_ln_w[i], p->ffn_ln_b[i], p->eps, hl, st);
-      if (!rc) rc = gr_linear_launch(hl, B, d, p->ffn1_w[i], p->mlp, p->ffn1_b[i], nullptr, 0, GR_ACT_RELU, fl, p->mlp, st);
-      if (!rc) rc = gr_linear_launch(fl, B, p->mlp, p->ffn2_w[i], d, p->ffn2_b[i], xl, d, GR_ACT_NONE, xl, d, st);
-      if (rc) return rc;
-      *fin = SasOut{xl, 1, 0, false};
-      break;
+      if (!rc) rc = run_block_rest(p, i, ol, xl, hl, fl, B, st);
+      if (!rc) rc = run_layernorm(xl, B, d, 1, 0, p->last_ln_w, p->last_ln_b, p->eps, h, st);
+      return rc;
     }
-    rc = gr_linear_launch(w.o, rows, d, p->out_proj_w[i], d, p->out_proj_b[i], w.x, d, GR_ACT_NONE,
-                          w.x, d, st);
-    if (rc) return rc;
-    rc = run_layernorm(w.x, rows, d, 1, 0, p->ffn_ln_w[i], p->ffn_ln_b[i], p->eps, w.h, st);
-    if (rc) return rc;
-    rc = gr_linear_launch(w.h, rows, d, p->ffn1_w[i], p->mlp, p->ffn1_b[i], nullptr, 0, GR_ACT_RELU,
-                          w.f, p->mlp, st);
-    if (rc) return rc;
-    rc = gr_linear_launch(w.f, rows, p->mlp, p->ffn2_w[i], d, p->ffn2_b[i], w.x, d, GR_ACT_NONE,
-                          w.x, d, st);
+    rc = run_block_rest(p, i, w.o, w.x, w.h, w.f, rows, st);
     if (rc) return rc;
   }
-  return GR_OK;
+  // the last LayerNorm: on position n-1 of every sequence, or on every row
+  return run_layernorm(w.x, last_only ? B : rows, d, last_only ? n : 1, last_only ? n - 1 : 0, p->last_ln_w,
+                       p->last_ln_b, p->eps, h, st);
+}
+
+// Runs a plan.  *hidden: the final hidden states, last LayerNorm applied ([B, d] of a last-position
+// forward, else [B*n, d]), in `out` or, without one, in the workspace: w.h after the fused kernel, else
+// w.o (free by then).  init_ranks: gr_sasrec_rank_f32's ranks, which the fused kernel starts at 1.
+static int sas_run(const gr_sasrec_params* p, const SasPlan& s, const int64_t* seqs, int64_t B, int32_t n,
+                   const SasWs& w, int last_only, float* out, int32_t* err, hipStream_t st, float** hidden,
+                   int64_t* init_ranks = nullptr) {
+  float* h = *hidden = out ? out : s.pipe == GR_SAS_FUSED ? w.h : w.o;
+  if (s.pipe != GR_SAS_FUSED)
+    return s.pipe == GR_SAS_ROWTILE ? run_rowtile(p, s, seqs, B, n, w, err, h, st)
+                                    : run_layerwise(p, s, seqs, B, n, w, err, last_only, h, st);
+  if (s.has(GR_SAS_FUSED_MISALIGNED) || !aligned16(h))
+    return fail(GR_ERR_UNSUPPORTED, "sasrec: the fused forward (n <= 64, d <= 64) needs every block parameter, the "
+                                    "last layernorm and the output non-null and 16-byte aligned");
+  return planned(gr_sasrec_fused_launch(p, seqs, B, n, h, last_only, s.has(GR_SAS_FUSED_TWO_WAVES), err, st, init_ranks, 1),
+                 "gr_sasrec_fused_launch");
 }
 
 }  // namespace gr
 
-extern "C" size_t gr_sasrec_workspace_bytes(const gr_sasrec_params* p, int64_t B, int32_t n) {
-  if (!p || B < 0 || n < 1) return 0;
-  return gr::ws_layout(p, B, n, nullptr, nullptr);
+extern "C" int32_t gr_sasrec_plan(const gr_sasrec_params* p, int64_t B, int32_t n, int32_t last_only) {
+  gr::clear_error();
+  if (const int rc = gr::check_params(p, B, n)) return rc;
+  const gr::SasPlan s = gr::sas_plan(p, B, n, last_only);
+  return s.pipe | s.block0 | s.attn | s.flags;
 }
 
-static int sas_prepare(const gr_sasrec_params* p, int64_t B, int32_t n, void* ws, size_t wsb,
-                       gr::SasWs* w) {
+extern "C" size_t gr_sasrec_workspace_bytes(const gr_sasrec_params* p, int64_t B, int32_t n) {
+  if (!p || B < 0 || n < 1 || p->n_heads < 1) return 0;
+  return gr::ws_layout(gr::sas_plan(p, B, n, 0), p, B, n, nullptr, nullptr);
+}
+
+// Argument checks, the plan, and the workspace laid out for it.
+static int sas_prepare(const gr_sasrec_params* p, int64_t B, int32_t n, int last_only, void* ws, size_t wsb,
+                       gr::SasWs* w, gr::SasPlan* s) {
   using namespace gr;
   int rc = check_params(p, B, n);
   if (rc) return rc;
-  const size_t need = ws_layout(p, B, n, nullptr, nullptr);
+  *s = sas_plan(p, B, n, last_only);
+  const size_t need = ws_layout(*s, p, B, n, nullptr, nullptr);
   if (!ws || wsb < need)
     return fail(GR_ERR_WORKSPACE, "sasrec: workspace too small (need " + std::to_string(need) + " bytes)");
   char* base = reinterpret_cast<char*>(align_up(reinterpret_cast<uintptr_t>(ws), 256));
-  ws_layout(p, B, n, base, w);
+  ws_layout(*s, p, B, n, base, w);
   return GR_OK;
 }
 
@@ -482,24 +500,14 @@ extern "C" int gr_sasrec_forward_f32(const gr_sasrec_params* p, const int64_t* s
                                      size_t workspace_bytes, int32_t* err_flag, void* stream) {
   using namespace gr;
   clear_error();
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   SasWs w;
-  int rc = sas_prepare(p, B, n, workspace, workspace_bytes, &w);
+  SasPlan s;
+  const int rc = sas_prepare(p, B, n, last_only, workspace, workspace_bytes, &w, &s);
   if (rc) return rc;
   if (B == 0) return GR_OK;
   if (!seqs || !out) return fail(GR_ERR_ARG, "gr_sasrec_forward_f32: null seqs / out");
-  if (fused_ok(p, n)) {
-    rc = gr_sasrec_fused_launch(p, seqs, B, n, out, last_only, err_flag, st);
-    if (rc != GR_ERR_UNSUPPORTED) return rc;
-    return fail(GR_ERR_UNSUPPORTED, "sasrec: fused path refused a shape fused_ok accepted");
-  }
-  SasOut fin;
-  rc = run_forward(p, seqs, B, n, w, err_flag, last_only, &fin, last_only ? out : nullptr, st,
-                   last_only ? nullptr : out);
-  if (rc) return rc;
-  if (fin.done) return GR_OK;
-  if (last_only) return run_layernorm(fin.x, B, p->d, fin.stride, fin.off, p->last_ln_w, p->last_ln_b, p->eps, out, st);
-  return run_layernorm(w.x, B * n, p->d, 1, 0, p->last_ln_w, p->last_ln_b, p->eps, out, st);
+  float* h;
+  return sas_run(p, s, seqs, B, n, w, last_only, out, err_flag, reinterpret_cast<hipStream_t>(stream), &h);
 }
 
 static int score_hidden(const gr_sasrec_params* p, const float* h, int64_t B, float* logits, int64_t ld,
@@ -521,26 +529,15 @@ extern "C" int gr_sasrec_predict_ld_f32(const gr_sasrec_params* p, const int64_t
     return fail(GR_ERR_ARG, "gr_sasrec_predict_ld_f32: ld < item_rows");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   SasWs w;
-  int rc = sas_prepare(p, B, n, workspace, workspace_bytes, &w);
+  SasPlan s;
+  int rc = sas_prepare(p, B, n, 1, workspace, workspace_bytes, &w, &s);
   if (rc) return rc;
   if (B == 0) return GR_OK;
   if (!seqs || !logits) return fail(GR_ERR_ARG, "gr_sasrec_predict: null seqs / logits");
-  if (fused_ok(p, n)) {
-    rc = gr_sasrec_fused_launch(p, seqs, B, n, w.h, 1, err_flag, st);
-    if (rc == GR_ERR_UNSUPPORTED)
-      return fail(GR_ERR_UNSUPPORTED, "sasrec: fused path refused a shape fused_ok accepted");
-  } else {
-    SasOut fin;
-    float* hout = w.o;   // [B, d] final hidden states (the attention-output buffer is free by then)
-    rc = run_forward(p, seqs, B, n, w, err_flag, 1, &fin, hout, st);
-    if (rc) return rc;
-    if (!fin.done)
-      rc = run_layernorm(fin.x, B, p->d, fin.stride, fin.off, p->last_ln_w, p->last_ln_b, p->eps, hout, st);
-    if (rc) return rc;
-    return score_hidden(p, hout, B, logits, ld, st);
-  }
+  float* h;
+  rc = sas_run(p, s, seqs, B, n, w, 1, nullptr, err_flag, st, &h);
   if (rc) return rc;
-  return score_hidden(p, w.h, B, logits, ld, st);
+  return score_hidden(p, h, B, logits, ld, st);
 }
 
 extern "C" int gr_sasrec_predict_f32(const gr_sasrec_params* p, const int64_t* seqs, int64_t B,
@@ -565,13 +562,13 @@ extern "C" int gr_rank_f32(const float* logits, int64_t B, int64_t cols, int64_t
 }
 
 // evaluate.py:26-32 for one batch in ONE call: the last hidden states of the
-// forward (which also writes every rank's starting 1), then one count launch that forms each
-// target logit with the scoring chain (gr_score_pairs_f32's tile) and counts the strictly greater
-// logits (gr_score_count_gt_ws_f32's kernel) -- two launches (three when the count spreads over the
-// workspace copies), the [B, item_rows] logits never written.
+// forward (the fused kernel also writes every rank's starting 1, so the count needs no fill), then
+// one count launch that forms each target logit with the scoring chain (gr_score_pairs_f32's tile)
+// and counts the strictly greater logits (gr_score_count_gt_ws_f32's kernel) -- two launches (three
+// when the count spreads over the workspace copies), the [B, item_rows] logits never written.
 extern "C" size_t gr_sasrec_rank_workspace_bytes(const gr_sasrec_params* p, int64_t B, int32_t n) {
-  if (!p || B < 0 || n < 1) return 0;
-  return gr::ws_layout(p, B, n, nullptr, nullptr) + gr::align_up((size_t)B * 4, 256) + 256;
+  const size_t fwd = gr_sasrec_workspace_bytes(p, B, n);
+  return fwd ? fwd + gr::align_up((size_t)B * 4, 256) + 256 : 0;
 }
 
 extern "C" int gr_sasrec_rank_f32(const gr_sasrec_params* p, const int64_t* seqs, int64_t B, int32_t n,
@@ -586,30 +583,17 @@ extern "C" int gr_sasrec_rank_f32(const gr_sasrec_params* p, const int64_t* seqs
   if (!workspace || workspace_bytes < need)
     return fail(GR_ERR_WORKSPACE, "gr_sasrec_rank_f32: workspace too small (need " + std::to_string(need) + " bytes)");
   SasWs w;
-  int rc = sas_prepare(p, B, n, workspace, workspace_bytes, &w);
+  SasPlan s;
+  int rc = sas_prepare(p, B, n, 1, workspace, workspace_bytes, &w, &s);
   if (rc) return rc;
   if (B == 0) return GR_OK;
   if (!seqs || !targets || !ranks_out) return fail(GR_ERR_ARG, "gr_sasrec_rank_f32: null seqs / targets / ranks");
   if (p->d != 16 && p->d != 32 && p->d != 64 && p->d != 128)
     return fail(GR_ERR_UNSUPPORTED, "gr_sasrec_rank_f32: d must be 16, 32, 64 or 128 (the fused rank's widths)");
   float* h;
-  bool preinit = false;
-  if (fused_ok(p, n)) {
-    // the forward also writes ranks_out[b] = 1 (the count's start), so the count needs no fill
-    h = w.h;
-    rc = gr_sasrec_fused_launch(p, seqs, B, n, h, 1, err_flag, st, ranks_out, 1);
-    if (rc == GR_ERR_UNSUPPORTED)
-      return fail(GR_ERR_UNSUPPORTED, "sasrec: fused path refused a shape fused_ok accepted");
-    preinit = true;
-  } else {
-    SasOut fin;
-    h = w.o;   // [B, d] final hidden states (the attention-output buffer is free by then)
-    rc = run_forward(p, seqs, B, n, w, err_flag, 1, &fin, h, st);
-    if (!rc && !fin.done)
-      rc = run_layernorm(fin.x, B, p->d, fin.stride, fin.off, p->last_ln_w, p->last_ln_b, p->eps, h, st);
-  }
+  rc = sas_run(p, s, seqs, B, n, w, 1, nullptr, err_flag, st, &h, ranks_out);
   if (rc) return rc;
   // the target logits and the strict count in one launch (score_count_kernel<D, true>)
   return gr_score_rank_launch(h, B, p->d, p->item_emb, p->item_rows, targets, mask_col0, ranks_out, count_ws,
-                              count_ws_bytes, err_flag, preinit, st);
+                              count_ws_bytes, err_flag, s.pipe == GR_SAS_FUSED, st);
 }

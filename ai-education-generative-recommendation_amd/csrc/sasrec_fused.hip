@@ -1049,17 +1049,32 @@ __global__ __launch_bounds__(256, 2) void sasrec_fused2_kernel(const SasFusedArg
 
 }  // namespace gr
 
-// Fused path for n <= 64, d <= 64 (d % 8 == 0, head width % 8 == 0), mlp <= 128, blocks <= 8.
-// Returns GR_ERR_UNSUPPORTED (error message untouched) for any other shape: the caller then runs
-// the layer-wise pipeline.
-int gr_sasrec_fused_launch(const gr_sasrec_params* p, const int64_t* seqs, int64_t B, int32_t n,
-                           float* out, int32_t last_only, int32_t* err, hipStream_t st, int64_t* init_out,
+// The fused kernel's envelope: n <= 64, d <= 64 (d % 8 == 0, head width % 8 == 0), mlp <= 128 (a
+// multiple of 4), blocks <= 8; every block parameter and the last LayerNorm non-null and 16-byte
+// aligned.  1: it runs; 0: another shape (the layer-wise pipeline's); -1: a fused shape whose
+// parameters miss the alignment -- the workspace was sized for this kernel, so the forward fails.
+int gr_sasrec_fused_ok(const gr_sasrec_params* p, int32_t n) {
+  using namespace gr;
+  const int d = p->d, H = p->n_heads;
+  if (n > 64 || d > 64 || d % 8 || (d / H) % 8 || p->mlp > 128 || p->mlp % 4 || p->n_blocks > SF_MAX_BLOCKS)
+    return 0;
+  for (int i = 0; i < p->n_blocks; ++i) {
+    const float* ptrs[12] = {p->attn_ln_w[i], p->attn_ln_b[i], p->in_proj_w[i], p->in_proj_b[i],
+                             p->out_proj_w[i], p->out_proj_b[i], p->ffn_ln_w[i], p->ffn_ln_b[i],
+                             p->ffn1_w[i],    p->ffn1_b[i],    p->ffn2_w[i],   p->ffn2_b[i]};
+    for (const float* q : ptrs)
+      if (!q || !aligned16(q)) return -1;
+  }
+  return aligned16(p->last_ln_w) && aligned16(p->last_ln_b) ? 1 : -1;
+}
+
+// two_waves: one wave per 32-token tile (n > 32 only) instead of one per sequence; sas_plan chooses.
+int gr_sasrec_fused_launch(const gr_sasrec_params* p, const int64_t* seqs, int64_t B, int32_t n, float* out,
+                           int32_t last_only, bool two_waves, int32_t* err, hipStream_t st, int64_t* init_out,
                            int64_t init_val) {
   using namespace gr;
   const int d = p->d, H = p->n_heads;
-  if (n > 64 || d > 64 || d % 8 || (d / H) % 8 || p->mlp > 128 || p->mlp % 4 ||
-      p->n_blocks > SF_MAX_BLOCKS)
-    return GR_ERR_UNSUPPORTED;
+  if (gr_sasrec_fused_ok(p, n) != 1 || !aligned16(out) || (two_waves && n <= 32)) return GR_ERR_UNSUPPORTED;
   SasFusedArgs a;
   for (int i = 0; i < p->n_blocks; ++i) {
     SasBlockPtrs& b = a.blk[i];
@@ -1069,37 +1084,17 @@ int gr_sasrec_fused_launch(const gr_sasrec_params* p, const int64_t* seqs, int64
     b.ln_f_w = p->ffn_ln_w[i];  b.ln_f_b = p->ffn_ln_b[i];
     b.w1 = p->ffn1_w[i];        b.b1 = p->ffn1_b[i];
     b.w2 = p->ffn2_w[i];        b.b2 = p->ffn2_b[i];
-    const float* ptrs[12] = {b.ln_a_w, b.ln_a_b, b.w_in, b.b_in, b.w_o, b.b_o,
-                             b.ln_f_w, b.ln_f_b, b.w1, b.b1, b.w2, b.b2};
-    for (const float* q : ptrs)
-      if (!q || !aligned16(q)) return GR_ERR_UNSUPPORTED;
   }
-  if (!aligned16(p->last_ln_w) || !aligned16(p->last_ln_b) || !aligned16(out)) return GR_ERR_UNSUPPORTED;
   a.item = p->item_emb; a.pos = p->pos_emb; a.ln_w = p->last_ln_w; a.ln_b = p->last_ln_b;
   a.item_rows = p->item_rows; a.nb = p->n_blocks; a.d = d; a.heads = H; a.mlp = p->mlp; a.n = n;
   a.eps = p->eps;
-  a.scale = (float)std::sqrt(1.0 / (double)(d / H));
+  a.scale = sas_scale(d / H);
   a.init_out = init_out;
   a.init_val = init_val;
   const int TT = n > 32 ? 2 : 1, DT = d > 32 ? 2 : 1, MT = (p->mlp + 31) / 32;
   const dim3 g((unsigned)((B + 3) / 4)), blk(256);
   const bool exact = d == 32 * DT && p->mlp == 32 * MT;
-  // Which form (sas_fused 2 = auto, 3 = always two waves).  The one-wave kernel runs in rounds of
-  // 4 x CUs sequences (one wave per SIMD, ~58 us per round at C3's shape); the two-wave kernel takes
-  // 0.63 of that round for up to 2 x CUs sequences (one wave per SIMD) and ~0.5 round per further
-  // 2 x CUs (two waves per SIMD overlap little: the MFMA and VALU work per SIMD is the bound), so
-  // it wins when k = ceil(B / 2 CUs) is odd (profiles/r05/ab_fused_waves.txt).
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-      cus = 256;
-  }
-  const int64_t opt = option("sas_fused");
-  const int64_t k2 = (B + 2 * cus - 1) / (2 * cus), k1 = (B + 4 * cus - 1) / (4 * cus);
-  const double t2 = k2 == 1 ? 0.63 : 0.5 * (double)k2 + 0.03;
-  if (TT == 2 && (opt == 3 || (opt == 2 && t2 < (double)k1))) {
+  if (two_waves) {
     const dim3 g2((unsigned)((B + 1) / 2));
 #define GR_SF2_LAUNCH(dt, mt)                                                                      \
     if (DT == dt && MT == mt) {                                                                    \

@@ -595,17 +595,35 @@ __global__ __launch_bounds__(64 * NW, 1) void embed_proj_kernel(const int64_t* _
 
 }  // namespace gr
 
-// Shapes: d == 128, mlp in {32, 64, 128}; anything else returns GR_ERR_UNSUPPORTED (the caller
-// keeps the kernel-per-op sequence).  ln_next_* = the next block's attention LayerNorm, or the
-// last LayerNorm after the final block.  wn / bn (nout = 3d columns): the next block's
-// in-projection, computed from the LayerNorm image and written to H as [M x nout]; null: H gets
-// the LayerNorm output itself [M x d].
+// The row-tile kernels' shapes: d == 128, mlp in {32, 64, 128}.
+bool gr_rowtile_shape_ok(const gr_sasrec_params* p) {
+  return p->d == gr::RT_D && (p->mlp == 32 || p->mlp == 64 || p->mlp == 128);
+}
+
+// ln_next_* = the next block's attention LayerNorm, or the last LayerNorm after the final block.
+// wn / bn (nout = 3d columns): the next block's in-projection, computed from the LayerNorm image and
+// written to H as [M x nout]; null: H gets the LayerNorm output itself [M x d].
+// gr_post_attn_ok: the shape, the 16-byte alignment of every parameter the kernel reads as float4
+// and the tile count (O, X, H are workspace buffers, tested at the launch).
+bool gr_post_attn_ok(const gr_sasrec_params* p, int blk, const float* ln_next_w, const float* ln_next_b,
+                     const float* wn, const float* bn, int nout, int64_t M) {
+  using namespace gr;
+  if (!gr_rowtile_shape_ok(p)) return false;
+  const float* ptrs[] = {p->out_proj_w[blk], p->ffn1_w[blk], p->ffn2_w[blk], p->ffn_ln_w[blk], p->ffn_ln_b[blk],
+                         ln_next_w, ln_next_b};
+  for (const float* q : ptrs)
+    if (!aligned16(q)) return false;
+  if (wn && (!aligned16(wn) || !bn || nout % 32 || nout < 32)) return false;
+  return (M + RT_BM - 1) / RT_BM <= 0x7fffffffLL;
+}
+
 int gr_post_attn_launch(const gr_sasrec_params* p, int blk, const float* ln_next_w, const float* ln_next_b,
                         const float* wn, const float* bn, int nout, const float* O, float* X, float* H,
                         int64_t M, hipStream_t st) {
   using namespace gr;
   const int mlp = p->mlp;
-  if (p->d != RT_D || (mlp != 32 && mlp != 64 && mlp != 128)) return GR_ERR_UNSUPPORTED;
+  if (!gr_post_attn_ok(p, blk, ln_next_w, ln_next_b, wn, bn, nout, M)) return GR_ERR_UNSUPPORTED;
+  if (!aligned16(O) || !aligned16(X) || !aligned16(H)) return GR_ERR_UNSUPPORTED;
   RowTileArgs a;
   a.wo = p->out_proj_w[blk]; a.bo = p->out_proj_b[blk];
   a.ln_f_w = p->ffn_ln_w[blk]; a.ln_f_b = p->ffn_ln_b[blk];
@@ -615,12 +633,7 @@ int gr_post_attn_launch(const gr_sasrec_params* p, int blk, const float* ln_next
   a.wn = wn; a.bn = bn; a.nout = nout;
   a.kv2 = wn && (nout / 32) % 8 == 0;
   a.mlp = mlp; a.eps = p->eps;
-  const float* ptrs[] = {a.wo, a.w1, a.w2, a.ln_f_w, a.ln_f_b, a.ln_n_w, a.ln_n_b, O, X, H};
-  for (const float* q : ptrs)
-    if (!aligned16(q)) return GR_ERR_UNSUPPORTED;
-  if (wn && (!aligned16(wn) || !bn || nout % 32 || nout < 32)) return GR_ERR_UNSUPPORTED;
   const int64_t tiles = (M + RT_BM - 1) / RT_BM;
-  if (tiles > 0x7fffffffLL) return GR_ERR_UNSUPPORTED;
   // 8 waves per 64-row tile (4 per SIMD); the 4-wave form measured 200 vs 182 us per C5 forward
   switch (mlp) {
     case 32: hipLaunchKernelGGL(post_attn8_kernel<1>, dim3((unsigned)tiles), dim3(512), 0, st, a, O, X, H, M); break;
@@ -630,37 +643,41 @@ int gr_post_attn_launch(const gr_sasrec_params* p, int blk, const float* ln_next
   return check_launch("sasrec post-attention row tile (8 waves)");
 }
 
+bool gr_embed_ln_ok(const gr_sasrec_params* p, int64_t M, const float* wn, const float* bn, int nout) {
+  using namespace gr;
+  if (p->d != RT_D || p->n_blocks < 1) return false;
+  if (!aligned16(p->attn_ln_w[0]) || !aligned16(p->attn_ln_b[0])) return false;
+  if (wn && (!aligned16(wn) || !bn || nout % 32 || nout < 32)) return false;
+  return (M + RT_BM - 1) / RT_BM <= 0x7fffffffLL;
+}
+
 int gr_embed_ln_launch(const gr_sasrec_params* p, const int64_t* seqs, int64_t M, int32_t n, const float* wn,
                        const float* bn, int nout, float* X, float* H, int32_t* err, hipStream_t st) {
   using namespace gr;
-  if (p->d != RT_D || p->n_blocks < 1) return GR_ERR_UNSUPPORTED;
-  if (!aligned16(p->attn_ln_w[0]) || !aligned16(p->attn_ln_b[0])) return GR_ERR_UNSUPPORTED;
-  if (wn && (!aligned16(wn) || !bn || nout % 32 || nout < 32)) return GR_ERR_UNSUPPORTED;
+  if (!gr_embed_ln_ok(p, M, wn, bn, nout)) return GR_ERR_UNSUPPORTED;
   const int64_t tiles = (M + RT_BM - 1) / RT_BM;
-  if (tiles > 0x7fffffffLL) return GR_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(embed_ln_kernel, dim3((unsigned)tiles), dim3(256), 0, st, seqs, M, n, p->item_emb, p->item_rows,
                      p->pos_emb, p->attn_ln_w[0], p->attn_ln_b[0], p->eps, wn, bn, nout, X, H, err);
   return check_launch("sasrec embed + layernorm");
 }
 
 // Block 0 fused: X, then QKV = LN_a0(X) . W^T + b ([M x 3d]) by embed_proj_kernel
-// (d == 128 only; GR_ERR_UNSUPPORTED otherwise -- the caller keeps embed_ln + gr_linear).  One
+// (d == 128 only; where gr_embed_proj_ok is false the plan keeps embed_ln + gr_linear).  One
 // workgroup per CU over contiguous ranges of 32-row tiles (64-row tiles measured C5 forward 414 vs
 // 403 us: 3200 tiles over 256 CUs balance better than 1600).  RC (row tiles of 32 per step) stays a
 // template parameter of the kernel; the launcher uses 1.
+bool gr_embed_proj_ok(const gr_sasrec_params* p, int64_t M, const float* wn, const float* bn, int nout) {
+  using namespace gr;
+  if (p->d != RT_D || p->n_blocks < 1 || nout != 3 * RT_D) return false;
+  if (!aligned16(p->attn_ln_w[0]) || !aligned16(p->attn_ln_b[0]) || !aligned16(wn) || !bn) return false;
+  return M * nout < (1LL << 40);
+}
+
 int gr_embed_proj_launch(const gr_sasrec_params* p, const int64_t* seqs, int64_t M, int32_t n, const float* wn,
                          const float* bn, int nout, float* X, float* QKV, int32_t* err, hipStream_t st) {
   using namespace gr;
-  if (p->d != RT_D || p->n_blocks < 1 || nout != 3 * RT_D) return GR_ERR_UNSUPPORTED;
-  if (!aligned16(p->attn_ln_w[0]) || !aligned16(p->attn_ln_b[0]) || !aligned16(wn) || !bn)
-    return GR_ERR_UNSUPPORTED;
-  if (M * nout >= (1LL << 40)) return GR_ERR_UNSUPPORTED;
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
-  }
+  if (!gr_embed_proj_ok(p, M, wn, bn, nout)) return GR_ERR_UNSUPPORTED;
+  const int cus = cu_count();
   const int64_t tiles = (M + 31) / 32;
   const unsigned g = (unsigned)(tiles < cus ? tiles : cus);
 #define GR_EMB_PROJ(NW, RC)                                                                              \

@@ -361,25 +361,35 @@ __global__ __launch_bounds__(ST_NT, 2) void sas_tail_h2_kernel(const SasTailArgs
 
 }  // namespace gr
 
-// Returns GR_ERR_UNSUPPORTED for shapes outside the kernel's limits (the caller keeps the
-// layer-wise final block): lane groups of k/4 lanes (k = d for the scores / Wq / Wo / W1 reads,
-// k = mlp for W2), at most 8 heads and 1024 keys.
-bool gr_sasrec_tail_ok(const gr_sasrec_params* p, int32_t n) {
+// The kernel's limits: lane groups of k/4 lanes (k = d for the scores / Wq / Wo / W1 reads, k = mlp
+// for W2), at most 8 heads and 1024 keys, B below 2^31; and block blk's in-projection (its Wk and Wv
+// parts start whole float4s further), out-projection and FFN weights 16-byte aligned.  Where it is
+// false the final block of a last-position forward stays layer-wise.
+bool gr_sasrec_tail_ok(const gr_sasrec_params* p, int blk, int64_t B, int32_t n) {
   using namespace gr;
   const int d = p->d, H = p->n_heads;
   auto pow2 = [](int v) { return v >= 1 && (v & (v - 1)) == 0; };
-  return !(d > ST_MAX_D || d % 4 || !pow2(d / 4) || H > ST_MAX_H || d % H || (d / H) % 4 || !pow2(d / H / 4) ||
-           n > ST_MAX_N || p->mlp > ST_MAX_MLP || p->mlp % 4 || !pow2(p->mlp / 4) || p->mlp / 4 > 64);
+  if (d > ST_MAX_D || d % 4 || !pow2(d / 4) || H > ST_MAX_H || d % H || (d / H) % 4 || !pow2(d / H / 4) ||
+      n > ST_MAX_N || p->mlp > ST_MAX_MLP || p->mlp % 4 || !pow2(p->mlp / 4) || p->mlp / 4 > 64)
+    return false;
+  if (blk < 0 || blk >= p->n_blocks || B > 0x7fffffffLL) return false;
+  const float* w_in = p->in_proj_w[blk];
+  const float* ptrs[] = {w_in, p->out_proj_w[blk], p->ffn1_w[blk], p->ffn2_w[blk], w_in + (int64_t)d * d,
+                         w_in + 2LL * d * d};
+  for (const float* q : ptrs)
+    if (!aligned16(q)) return false;
+  return true;
 }
 
 // X: [B, n, d] residual stream entering the final block; Hs [B, n, d] = LN_a(X) of the final block
 // (the LayerNorm output the K|V projection would have read); out: [B, d] = the final hidden state
-// of position n-1.
+// of position n-1.  valu: the VALU butterflies in the reductions (one sequence per CU: latency-bound,
+// they pay), else ds_bpermute.
 int gr_sasrec_tail_h_launch(const gr_sasrec_params* p, int blk, const float* X, const float* Hs,
-                            int64_t B, int32_t n, float* out, hipStream_t st) {
+                            int64_t B, int32_t n, float* out, bool valu, hipStream_t st) {
   using namespace gr;
   const int d = p->d, H = p->n_heads;
-  if (!gr_sasrec_tail_ok(p, n) || B > 0x7fffffffLL) return GR_ERR_UNSUPPORTED;
+  if (!gr_sasrec_tail_ok(p, blk, B, n) || !aligned16(X) || !aligned16(Hs)) return GR_ERR_UNSUPPORTED;
   SasTailArgs a;
   a.ln_a_w = p->attn_ln_w[blk]; a.ln_a_b = p->attn_ln_b[blk];
   a.wq = p->in_proj_w[blk];     a.bq = p->in_proj_b[blk];
@@ -391,20 +401,10 @@ int gr_sasrec_tail_h_launch(const gr_sasrec_params* p, int blk, const float* X, 
   const float* wk = p->in_proj_w[blk] + (int64_t)d * d;
   const float* wv = p->in_proj_w[blk] + 2LL * d * d;
   const float* bv = p->in_proj_b[blk] + 2 * d;
-  const float* ptrs[] = {a.wq, a.wo, a.w1, a.w2, wk, wv, X, Hs};
-  for (const float* q : ptrs)
-    if (!aligned16(q)) return GR_ERR_UNSUPPORTED;
   a.d = d; a.n = n; a.heads = H; a.mlp = p->mlp; a.eps = p->eps;
-  a.scale = (float)std::sqrt(1.0 / (double)(d / H));
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
-  }
-  const bool vx = B <= cus;   // one sequence per CU: latency-bound, the VALU butterflies pay
+  a.scale = sas_scale(d / H);
 #define GR_TAIL(HM)                                                                                           \
-  if (vx)                                                                                                     \
+  if (valu)                                                                                                   \
     hipLaunchKernelGGL((sas_tail_h2_kernel<HM, true>), dim3((unsigned)B), dim3(ST_NT), 0, st, a, X, Hs, wk, wv, bv, out); \
   else                                                                                                        \
     hipLaunchKernelGGL((sas_tail_h2_kernel<HM, false>), dim3((unsigned)B), dim3(ST_NT), 0, st, a, X, Hs, wk, wv, bv, out)

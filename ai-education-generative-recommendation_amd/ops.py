@@ -851,6 +851,10 @@ class SasrecBinding:
                 self._ws[key] = nb
         return nb
 
+    def plan(self, B, n, last_only):
+        """``gr_sasrec_plan``: the GR_SAS_* mask of the kernels a forward of this shape runs now."""
+        return L.lib().gr_sasrec_plan(self.p_ref, B, n, 1 if last_only else 0)
+
 
 def sasrec_binding(model):
     """Cached :class:`SasrecBinding` of ``model``: reused while every parameter's storage pointer

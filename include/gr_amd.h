@@ -49,8 +49,8 @@ const char* gr_last_error(void);
 /* Process-wide path switches (no reference counterpart).  Each selects between two kernel paths
  * that give BITWISE identical results, so the tests can run both; no option changes numerics, and
  * the defaults are what every caller wants.  (Round 5 removed the A/B knobs of slower variants and
- * the two numerics-changing ones: the final SASRec block of a last-position forward always runs
- * the H form below.)
+ * the two numerics-changing ones: which form the final SASRec block of a last-position forward
+ * runs follows from the shape alone, see below.)
  *   "rq_fused"      1 (default): gr_rq_encode_f32 runs the fused persistent kernel when the encoder
  *                   shape is in -> 256 -> 128 -> 32; 0: the layer-wise path (exact gr_linear +
  *                   quantize).
@@ -84,7 +84,11 @@ const char* gr_last_error(void);
  *                   workgroup when n <= 256, n K e <= 2^20 (e padded) and the rows and
  *                   the workspace fit in LDS; 0: always one launch per phase over row tiles.  Both forms
  *                   run the same phase code in the same order: bitwise the same results.
- * A last-position forward (predict, last_hidden) runs its final block as the one-query tail on
+ * The final block of a last-position forward (predict, last_hidden; gr_sasrec_plan reports the
+ * choice): the H form when the tail kernel takes the shape (d / 4, head width / 4 and mlp / 4 powers
+ * of two, at most 8 heads, d and mlp <= 256, 16-byte aligned weights); otherwise the pruned final
+ * block (attention on the last query tile, the rest on the B last rows) when n >= 2 and
+ * n * mlp >= 2 d + mlp; otherwise the full block.  The H form is the one-query tail on
  * LN_a(X): q . K_j = (W_k^T q) . H_j (+ a term constant over j that cancels in the softmax) and
  * p . V = W_v (p . H) + b_v, so K|V of the B n rows are never projected (sas_tail_h2_kernel; the
  * fused d <= 64 kernel likewise).  The reassociated sums round differently from the reference
@@ -340,6 +344,31 @@ int gr_sasrec_rank_f32(const gr_sasrec_params* p, const int64_t* seqs, int64_t B
                        const int64_t* targets, int32_t mask_col0, int64_t* ranks_out, void* workspace,
                        size_t workspace_bytes, void* count_ws, size_t count_ws_bytes, int32_t* err_flag,
                        void* stream);
+
+/* The kernels the three entry points above run for this model, batch and length under the options
+ * in force (host only, nothing is launched): a non-negative mask of the GR_SAS_* bits below, or the
+ * negative code of the parameter checks those entry points make.  One pipeline bit is always set. */
+#define GR_SAS_FUSED 0x1            /* the register-resident forward kernel (option sas_fused)    */
+#define GR_SAS_ROWTILE 0x2          /* d = 128 row-tile kernels (option sas_rowtile)              */
+#define GR_SAS_LAYERWISE 0x4        /* one kernel per op                                          */
+#define GR_SAS_FUSED_TWO_WAVES 0x8  /* fused: two waves per sequence (else one)                   */
+#define GR_SAS_FUSED_MISALIGNED 0x10 /* fused shape, a parameter not 16-byte aligned: the forward
+                                        returns GR_ERR_UNSUPPORTED before any launch              */
+#define GR_SAS_B0_EMBED_PROJ 0x20   /* row-tile block 0: embed + LN_a0 + in-projection, one kernel */
+#define GR_SAS_B0_EMBED_LN_LINEAR 0x40 /* row-tile block 0: embed + LN_a0, then gr_linear          */
+#define GR_SAS_B0_EMBED_LN 0x80     /* row-tile block 0: embed + LN_a0 alone (the H-form tail of a
+                                       one-block model reads it)                                  */
+#define GR_SAS_ATTN_SCALAR 0x100    /* causal_attn_kernel (head widths other than 32 / 64 / 128)  */
+#define GR_SAS_ATTN_MFMA 0x200      /* attn_mfma_kernel                                           */
+#define GR_SAS_ATTN_PERSIST 0x400   /* attn_persist_kernel                                        */
+#define GR_SAS_ATTN_K16 0x800       /* attn_k16_kernel (option attn_k16); no ATTN bit: no attention
+                                       launch at all                                              */
+#define GR_SAS_ATTN_LAST_TILE 0x1000 /* the final block's attention runs on the last query tile only */
+#define GR_SAS_TAIL 0x2000          /* last-position forward: the final block is the H-form tail  */
+#define GR_SAS_TAIL_VALU 0x4000     /* the tail's VALU reduction form (B <= compute units)        */
+#define GR_SAS_PRUNED 0x8000        /* last-position forward: the final block after its attention
+                                       runs on the B last rows only                               */
+int32_t gr_sasrec_plan(const gr_sasrec_params* p, int64_t B, int32_t n, int32_t last_only);
 
 /* SASRec training, the transformer part of one step (SASRec/train.py:131 `model.forward` in train
  * mode and the backward that `loss.backward()`, train.py:161-172, runs through model.py:49-96).

@@ -29,10 +29,21 @@ def sas_path(request):
     """Run a test through the register-resident fused forward (n <= 64, d <= 64: two waves per
     sequence when n > 32, or one), and through the layer-wise pipeline: all must meet the same bar
     (shapes outside the fused kernel's range run layer-wise either way)."""
+    import ctypes
     from gr_amd import _lib
     _lib.set_option("sas_fused", request.param)
-    yield request.param
-    _lib.set_option("sas_fused", 2)
+    try:
+        # the option selects what the ids say, at config 3's shape (a host-only query: no address is read)
+        ptrs = {f: 0x10000 for f, _ in _lib.SasrecParams._fields_[7:]}
+        blk = (ctypes.c_void_p * 2)(0x10000, 0x10000)
+        ptrs.update({f: ctypes.cast(blk, ctypes.c_void_p) for f, _ in _lib.SasrecParams._fields_[9:21]})
+        c3 = _lib.SasrecParams(d=64, n_blocks=2, n_heads=1, mlp=64, max_len=50, eps=1e-8, item_rows=100, **ptrs)
+        want = {3: _lib.GR_SAS_FUSED | _lib.GR_SAS_FUSED_TWO_WAVES, 1: _lib.GR_SAS_FUSED, 0: _lib.GR_SAS_LAYERWISE}
+        mask = _lib.lib().gr_sasrec_plan(ctypes.byref(c3), 300, 50, 1)
+        assert mask & (want[3] | want[0]) == want[request.param], hex(mask)
+        yield request.param
+    finally:
+        _lib.set_option("sas_fused", 2)
 
 
 def build(name, dev):
@@ -251,6 +262,12 @@ def test_embed_proj_equals_two_kernels(B, blocks, dev):
     try:
         for opt in (0, 1):
             _lib.set_option("emb_proj", opt)
+            b0 = _lib.GR_SAS_B0_EMBED_PROJ if opt else _lib.GR_SAS_B0_EMBED_LN_LINEAR
+            for last_only in (0, 1):   # a one-block last-position forward has no in-projection: embed_ln alone
+                want = _lib.GR_SAS_B0_EMBED_LN if last_only and blocks == 1 else b0
+                b0s = _lib.GR_SAS_B0_EMBED_PROJ | _lib.GR_SAS_B0_EMBED_LN_LINEAR | _lib.GR_SAS_B0_EMBED_LN
+                plan = m._binding(seqs).plan(B, n, last_only)
+                assert plan & _lib.GR_SAS_ROWTILE and plan & b0s == want, hex(plan)
             res[opt] = (m.forward(seqs), m.predict(seqs))
             bad = seqs.clone()
             bad[B // 2, 5] = items + 3
@@ -282,6 +299,10 @@ def test_tail_h_form_vs_full_block_and_oracle(d, heads, n, blocks, B, dev):
     p = synth.sasrec_params(d, n, blocks, heads, 2 * d if d < 128 else 64, dev)
     m = synth.sasrec_model(items, p, dev, seed=d + heads + n)
     seqs = synth.sequences(B, n, items, 5 + n, dev)
+    from gr_amd import _lib
+    plan = m._binding(seqs).plan(B, n, 1)
+    assert plan & _lib.GR_SAS_TAIL and plan & (_lib.GR_SAS_ROWTILE if d == 128 else _lib.GR_SAS_LAYERWISE), hex(plan)
+    assert not m._binding(seqs).plan(B, n, 0) & (_lib.GR_SAS_TAIL | _lib.GR_SAS_PRUNED)   # `full` below
     h_h = m.last_hidden(seqs).cpu()
     full = m.forward(seqs)[:, -1, :].cpu()
     got = m.predict(seqs).cpu()
@@ -368,6 +389,9 @@ def test_fused_tail_h_vs_full_block_and_oracle(d, heads, n, blocks, B, dev):
     seqs = synth.sequences(B, n, items, 7 + n, dev)
     _lib.set_option("sas_fused", 3)
     try:
+        for last_only in (0, 1):
+            plan = m._binding(seqs).plan(B, n, last_only)   # the whole mask: not misaligned either
+            assert plan == _lib.GR_SAS_FUSED | (_lib.GR_SAS_FUSED_TWO_WAVES if n > 32 else 0), hex(plan)
         h_h = m.last_hidden(seqs).cpu()
         full = m.forward(seqs)[:, -1, :].cpu()
         got = m.predict(seqs).cpu()
@@ -601,6 +625,10 @@ def test_d128_layerwise_paths_vs_oracle(heads, mlp, n, blocks, B, rowtile, dev):
         seqs = synth.sequences(B, n, items, 11 + n, dev)
         sd = {k: v.detach().cpu() for k, v in m.state_dict().items()}
         ref_f = sasrec_oracle.forward(seqs.cpu(), sd, blocks, heads, 1e-8)
+        for last_only in (0, 1):
+            plan = m._binding(seqs).plan(B, n, last_only)
+            assert plan & (_lib.GR_SAS_ROWTILE if rowtile else _lib.GR_SAS_LAYERWISE), hex(plan)
+            assert bool(plan & _lib.GR_SAS_TAIL) == bool(last_only), hex(plan)
         got_f = m.forward(seqs).cpu()
         assert (got_f - ref_f).abs().max().item() < 5e-5
         assert (m.last_hidden(seqs).cpu() - ref_f[:, -1, :]).abs().max().item() < 5e-5

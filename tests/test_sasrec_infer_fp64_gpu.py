@@ -25,7 +25,7 @@ output finite.  Cases are (d, heads, mlp, n, blocks, B); the branches of csrc/sa
   is d = 128 per-op with causal_attn_kernel);
 * per-op with the H-form tail: HFORM ((128, 2, 256, 40, 1, 4): d = 128 with mlp_layer outside
   {32, 64, 128}, so not the row-tile path, tail accepted);
-* the tail refused (d/4, head width/4 or mlp/4 no power of two), so run_forward's pruned final block
+* the tail refused (d/4, head width/4 or mlp/4 no power of two), so run_layerwise's pruned final block
   (``last_tile_only = 1``, the gathers, out-proj / LN / FFN on B rows inside the FFN buffer): PRUNED;
   (48, 2, 100, 70, 2, 9) and (20, 5, 12, 70, 2, 5) take causal_attn_kernel (head widths 24 and 4),
   (128, 2, 100, 77, 2, 7) attn_persist_kernel<64>, (128, 1, 100, 70, 2, 5) attn_k16_kernel and
@@ -152,14 +152,6 @@ CASES = ([("fused", s, "plain") for s in FUSED] + [("fused_default", s, "plain")
 DEFAULTS = {"sas_fused": 2, "sas_rowtile": 1, "attn_k16": 1}
 
 
-def tail_ok(d, heads, mlp):
-    """gr_sasrec_tail_ok (sasrec_tail.hip) for the shapes here: d/4, head width/4 and mlp/4 powers of two."""
-    pow2 = lambda v: v >= 1 and v & (v - 1) == 0   # noqa: E731
-    hd = d // heads
-    return d % 4 == 0 and pow2(d // 4) and heads <= 8 and hd % 4 == 0 and pow2(hd // 4) and mlp % 4 == 0 \
-        and pow2(mlp // 4) and mlp <= 256 and d <= 256
-
-
 def paths(group, shape):
     """(name, options) of every kernel path a case runs through."""
     d, heads = shape[0], shape[1]
@@ -173,6 +165,46 @@ def paths(group, shape):
     if group == "pruned" and d // heads == 128:
         return [("per_op_k16", {"attn_k16": 1}), ("per_op_k32", {"attn_k16": 0})]
     return [("per_op", {})]
+
+
+def assert_plan(binding, group, name, shape):
+    """The label of a run is the plan under its options (``gr_sasrec_plan``), for the full forward and
+    the last-position one: pipeline, attention kernel, and the final block's tail / pruned form."""
+    from gr_amd import _lib as L
+    d, heads, mlp, n, blocks, B = shape
+    hd = d // heads
+    for last_only in (0, 1):
+        m = binding.plan(B, n, last_only)
+        assert m >= 0, (name, m)
+        pipe = m & (L.GR_SAS_FUSED | L.GR_SAS_ROWTILE | L.GR_SAS_LAYERWISE)
+        attn = m & (L.GR_SAS_ATTN_SCALAR | L.GR_SAS_ATTN_MFMA | L.GR_SAS_ATTN_PERSIST | L.GR_SAS_ATTN_K16)
+        tail, pruned = bool(m & L.GR_SAS_TAIL), bool(m & L.GR_SAS_PRUNED)
+        what = (name, last_only, hex(m))
+        assert not m & L.GR_SAS_FUSED_MISALIGNED, what
+        if name in ("fused1", "fused3", "default"):
+            assert pipe == L.GR_SAS_FUSED, what
+            if name != "default":   # two waves need two 32-token tiles
+                assert bool(m & L.GR_SAS_FUSED_TWO_WAVES) == (name == "fused3" and n > 32), what
+            continue
+        # (128, 8, 64, 33, 2, CUs + 40), head width 16, is per-op under sas_rowtile 1 as well
+        rowtile = name.startswith("rowtile") and hd in (32, 64, 128)
+        assert pipe == (L.GR_SAS_ROWTILE if rowtile else L.GR_SAS_LAYERWISE), what
+        # the final block of a last-position forward: the tail everywhere but in the pruned group, where
+        # it is the pruned block (n = 1 has nothing to prune: the full block); the layer-wise run of a
+        # fused shape takes whichever of the two its widths give
+        if group == "fused":
+            assert tail + pruned == (last_only == 1 and blocks >= 1 and (tail or n >= 2)), what
+        else:
+            assert tail == (last_only == 1 and group != "pruned"), what
+            assert pruned == (last_only == 1 and group == "pruned" and n >= 2), what
+        if blocks - tail == 0:
+            assert attn == 0, what
+        elif hd == 128:
+            k16 = name.endswith("_k16") or not name.endswith("_k32")   # unnamed: the default, 16-key steps
+            assert attn == (L.GR_SAS_ATTN_K16 if k16 else L.GR_SAS_ATTN_PERSIST), what
+        else:
+            assert attn == {64: L.GR_SAS_ATTN_PERSIST, 32: L.GR_SAS_ATTN_MFMA}.get(hd, L.GR_SAS_ATTN_SCALAR), what
+        assert bool(m & L.GR_SAS_ATTN_LAST_TILE) == (pruned and attn != L.GR_SAS_ATTN_SCALAR), what
 
 
 def build_sequences(B, n, seed):
@@ -282,8 +314,6 @@ def test_infer_paths_vs_fp64(case, dev, parity_log):
     if shape[5] == CUS:   # above the CU count: the tail's ds_bpermute reduction form
         shape = shape[:5] + (torch.cuda.get_device_properties(dev).multi_processor_count + 40,)
     d, heads, mlp, n, blocks, B = shape
-    if not group.startswith("fused"):   # the layer-wise run of a fused shape takes whichever its widths give
-        assert tail_ok(d, heads, mlp) == (group != "pruned")
     ref = reference(shape, variant)
     tol = tolerances(variant)
     model = SASRec(ITEMS, dict(ref["params"], device=str(dev)))
@@ -297,6 +327,7 @@ def test_infer_paths_vs_fp64(case, dev, parity_log):
     bad, outs = [], {}
     for name, opts in paths(group, shape):
         with options(opts):
+            assert_plan(model._binding(seqs[:B]), group, name, shape)
             fwd = model.forward(seqs[:B]).cpu()
             last = model.last_hidden(seqs[:B]).cpu()
             lg_b = model.predict(seqs[:B]).cpu()
