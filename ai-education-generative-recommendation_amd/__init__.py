@@ -16,5 +16,6 @@ from .rqvae import RQVAE  # noqa: F401
 from .sasrec import SASRec  # noqa: F401
 from . import tiger  # noqa: F401
 from .tiger import TIGER  # noqa: F401
+from . import tiger_prefix  # noqa: F401  (its TIGER is the prefix variant: gr_amd.tiger_prefix.TIGER)
 
-__all__ = ["RQVAE", "SASRec", "TIGER", "tiger", "ops", "lib", "LIB_PATH"]
+__all__ = ["RQVAE", "SASRec", "TIGER", "tiger", "tiger_prefix", "ops", "lib", "LIB_PATH"]

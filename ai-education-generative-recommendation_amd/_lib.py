@@ -63,6 +63,12 @@ class TigerParams(ctypes.Structure):
                [("enc", (_vp * 8) * GR_TIGER_MAX_LAYERS), ("dec", (_vp * 13) * GR_TIGER_MAX_LAYERS)]
 
 
+class TigerPrefixParams(ctypes.Structure):
+    """Mirror of ``gr_tiger_prefix_params`` (include/gr_amd.h)."""
+    _fields_ = [(f, _i32) for f in ("bert_dim", "n_vec", "n_heads", "reserved")] + \
+               [("eps", _f32), ("reserved_f", _f32), ("adapter", (_vp * 14) * 3)]
+
+
 # (name, restype, argtypes) for every entry point of include/gr_amd.h
 SIGNATURES = {
     "gr_version": (ctypes.c_char_p, []),
@@ -155,6 +161,11 @@ SIGNATURES = {
     "gr_tiger_workspace_bytes": (_sz, [ctypes.POINTER(TigerParams), _i64, _i32, _i32, _i32]),
     "gr_tiger_generate_f32": (ctypes.c_int, [ctypes.POINTER(TigerParams), _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp,
                                              _vp, _vp, _vp, _sz, _vp]),
+    "gr_tiger_prefix_workspace_bytes": (_sz, [ctypes.POINTER(TigerParams), ctypes.POINTER(TigerPrefixParams), _i64,
+                                              _i32, _i32, _i32]),
+    "gr_tiger_generate_prefix_f32": (ctypes.c_int, [ctypes.POINTER(TigerParams), ctypes.POINTER(TigerPrefixParams),
+                                                    _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp,
+                                                    _vp, _vp, _vp, _sz, _vp]),
     "gr_beam_hits_i64": (ctypes.c_int, [_vp, _i64, _i32, _i32, _i64, _vp, _i32, _vp, _vp]),
 }
 

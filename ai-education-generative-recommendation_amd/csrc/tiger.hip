@@ -13,6 +13,15 @@
 //                         the slot of each of its ancestors, so the library's cache reorder between
 //                         steps is a copy of <= 8 small integers per beam.
 // Every product is an fp32 fma chain over k in order; nothing is approximated.
+//
+// The prefix variant (gr_tiger_generate_prefix_f32) puts one launch ahead of the two:
+//   tiger_adapter_kernel  grid (users, 3): the ProfessionalAdapter of one level for one user -- bert_proj of
+//                         the n_vec vectors, then AD_ROWS history rows at a time the q projection, the
+//                         attention over the n_vec keys, out_proj, LayerNorm, the GELU feed-forward and the
+//                         second LayerNorm, and a compensated running sum of the rows in row order for
+//                         the mean.  It writes the prefix token and (level 0) the [S + 3] key mask.
+// tiger_encoder_kernel<true> is the encoder with rows 0..2 taken from those tokens (<false>: the plain
+// entry's, whose code is what it was); the search kernel is launched unchanged on S + 3 keys.
 #include <atomic>
 
 #include "gr_common.h"
@@ -135,9 +144,13 @@ __host__ __device__ inline EncLayout enc_layout(int S, int D, int inner, int dkv
   return L;
 }
 
+// PFX: rows 0..2 of x are the user's prefix tokens (prefix[B, 3, D]) and rows 3.. the embeddings of its
+// S - 3 history tokens; amask then is the [B, S] mask the adapter kernel wrote (its first three columns 1).
+template <bool PFX>
 __global__ __launch_bounds__(TG_ENC_THREADS) void tiger_encoder_kernel(gr_tiger_params p, const int64_t* __restrict__ ids,
                                                                    const int64_t* __restrict__ amask, int S,
-                                                                   float* __restrict__ cross, float* __restrict__ enc_out) {
+                                                                   float* __restrict__ cross, float* __restrict__ enc_out,
+                                                                   const float* __restrict__ prefix) {
   extern __shared__ __align__(16) float lds[];
   int D = p.d_model, dkv = p.d_kv, H = p.n_heads, dff = p.d_ff;
 
@@ -161,8 +174,17 @@ __global__ __launch_bounds__(TG_ENC_THREADS) void tiger_encoder_kernel(gr_tiger_
   {
   TG_ENC_PTRS
   for (int e = tid; e < S * D; e += TG_THREADS) {
-    const int tok = tg_token(ids[u * S + e / D], p.vocab);
-    x[e] = p.shared[(size_t)tok * D + e % D];
+    if (PFX) {
+      if (e < 3 * D) {
+        x[e] = prefix[u * 3 * D + e];
+      } else {
+        const int tok = tg_token(ids[u * (S - 3) + e / D - 3], p.vocab);
+        x[e] = p.shared[(size_t)tok * D + e % D];
+      }
+    } else {
+      const int tok = tg_token(ids[u * S + e / D], p.vocab);
+      x[e] = p.shared[(size_t)tok * D + e % D];
+    }
   }
   for (int j = tid; j < S; j += TG_THREADS) kmask[j] = amask ? (amask[u * S + j] != 0) : 1;
   for (int e = tid; e < H * (2 * S - 1); e += TG_THREADS) {
@@ -614,6 +636,171 @@ __global__ __launch_bounds__(TG_SRCH_THREADS) void tiger_search_kernel(gr_tiger_
   for (int b = tid; b < nb; b += TG_THREADS) co[(size_t)u * nb + b] = fin_score[b];
 }
 
+// ProfessionalAdapter (RQVAE-T5-prefix/model.py:8-48) in eval mode: one workgroup per (user, level).
+// Every row of the history is independent until the final mean, so the S rows go through the block
+// AD_ROWS at a time and the workgroup's LDS is 36 KB whatever S is (four workgroups per compute unit).
+constexpr int AD_THREADS = 256, AD_ROWS = 16, AD_MAX_D = 64, AD_MAX_VEC = 16, AD_MAX_BERT = 1024;
+enum { A_BERT_W, A_BERT_B, A_IN_W, A_IN_B, A_OUT_W, A_OUT_B, A_FF1_W, A_FF1_B, A_FF2_W, A_FF2_B, A_N1_W, A_N1_B,
+       A_N2_W, A_N2_B };
+
+// out[r * ldo + n] = act(bias[n] + sum_k in[r * ldi + k] * W[n * K + k]); tg_gemm's items.  GELU: exact erf.
+template <bool GELU>
+__device__ __forceinline__ void ad_linear(float* out, int ldo, const float* in, int ldi, const float* __restrict__ W,
+                                          const float* __restrict__ bias, int N, int K, int rows) {
+  constexpr int RB = 4;
+  const int nrb = (rows + RB - 1) / RB;
+  for (int it = threadIdx.x; it < N * nrb; it += TG_THREADS) {
+    const int n = it % N, r0 = (it / N) * RB;
+    float acc[RB] = {0.f, 0.f, 0.f, 0.f};
+    const float4* w4 = reinterpret_cast<const float4*>(W + (size_t)n * K);
+    const float* xr[RB];
+#pragma unroll
+    for (int i = 0; i < RB; ++i) xr[i] = in + (size_t)min(r0 + i, rows - 1) * ldi;
+    for (int k = 0; k < K; k += 4) {
+      const float4 w = w4[k >> 2];
+#pragma unroll
+      for (int i = 0; i < RB; ++i) {
+        float a = acc[i];
+        a = fmaf(xr[i][k], w.x, a);
+        a = fmaf(xr[i][k + 1], w.y, a);
+        a = fmaf(xr[i][k + 2], w.z, a);
+        a = fmaf(xr[i][k + 3], w.w, a);
+        acc[i] = a;
+      }
+    }
+    const float b = bias[n];
+#pragma unroll
+    for (int i = 0; i < RB; ++i) {
+      if (r0 + i < rows) {
+        float v = acc[i] + b;
+        if (GELU) v = 0.5f * v * (1.f + erff(v * 0.70710678118654752f));
+        out[(size_t)(r0 + i) * ldo + n] = v;
+      }
+    }
+  }
+}
+
+// nn.LayerNorm of a + b over rows [rows, D] (D <= 64): biased variance; a wave per row.  out may be a.
+__device__ __forceinline__ void ad_layernorm(float* out, const float* a, const float* b, const float* __restrict__ w,
+                                             const float* __restrict__ bias, int rows, int D, float eps) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  for (int r = wave; r < rows; r += TG_WAVES) {
+    const float v = lane < D ? a[r * D + lane] + b[r * D + lane] : 0.f;
+    const float mean = wave_sum(v) / (float)D;
+    const float c = lane < D ? v - mean : 0.f;
+    const float var = wave_sum(c * c) / (float)D;
+    if (lane < D) out[r * D + lane] = c * rsqrtf(var + eps) * w[lane] + bias[lane];
+  }
+}
+
+__global__ __launch_bounds__(AD_THREADS) void tiger_adapter_kernel(
+    gr_tiger_prefix_params pp, const float* __restrict__ shared, int vocab, int D, const int64_t* __restrict__ ids,
+    const int64_t* __restrict__ amask, const float* __restrict__ prof1, const float* __restrict__ prof2,
+    const float* __restrict__ prof3, int S, int64_t* __restrict__ ext_mask, float* __restrict__ prefix_ws,
+    float* __restrict__ prefix_out) {
+  __shared__ __align__(16) float et[AD_ROWS * AD_MAX_D];        // embeddings, then the block's rows
+  __shared__ __align__(16) float qt[AD_ROWS * AD_MAX_D];        // queries, then each sub-layer's output
+  __shared__ __align__(16) float hid[AD_ROWS * 4 * AD_MAX_D];   // attention context, then the hidden rows
+  __shared__ __align__(16) float kv[AD_MAX_VEC * AD_MAX_D];     // bert_proj(prof)
+  __shared__ __align__(16) float kvp[AD_MAX_VEC * 2 * AD_MAX_D];   // its key | value projections
+  __shared__ const float* wtab[14];
+  const int64_t u = blockIdx.x;
+  const int level = blockIdx.y, tid = threadIdx.x;
+  const int nv = pp.n_vec, K = pp.bert_dim, nh = pp.n_heads, hd = D / nh;
+  const float eps = pp.eps;
+  if (tid < 14) wtab[tid] = pp.adapter[level][tid];
+  if (level == 0)
+    for (int j = tid; j < S + 3; j += AD_THREADS)
+      ext_mask[u * (S + 3) + j] = (j < 3 || !amask) ? 1 : (amask[u * S + j - 3] != 0);
+  __syncthreads();
+  // kv = bert_proj(prof): one output per item, four interleaved fma chains over k summed pairwise
+  const float* prof = (level == 0 ? prof1 : level == 1 ? prof2 : prof3) + (size_t)u * nv * K;
+  for (int it = tid; it < nv * D; it += AD_THREADS) {
+    const int n = it % D, r = it / D;
+    const float4* w4 = reinterpret_cast<const float4*>(wtab[A_BERT_W] + (size_t)n * K);
+    const float4* x4 = reinterpret_cast<const float4*>(prof + (size_t)r * K);
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+    for (int k = 0; k < (K >> 2); ++k) {
+      const float4 w = w4[k], x = x4[k];
+      a0 = fmaf(x.x, w.x, a0);
+      a1 = fmaf(x.y, w.y, a1);
+      a2 = fmaf(x.z, w.z, a2);
+      a3 = fmaf(x.w, w.w, a3);
+    }
+    kv[r * D + n] = ((a0 + a1) + (a2 + a3)) + wtab[A_BERT_B][n];
+  }
+  __syncthreads();
+  // keys and values: rows D .. 3 D of in_proj
+  ad_linear<false>(kvp, 2 * D, kv, D, wtab[A_IN_W] + (size_t)D * D, wtab[A_IN_B] + D, 2 * D, D, nv);
+  const float scale = sqrtf(1.f / (float)hd);
+  // thread c < D: the running sum of channel c over the rows, in row order, compensated (Kahan): a history
+  // of one item is all identical padding rows but four, and their plain running sum rounds the same way every time
+  float msum = 0.f, mcomp = 0.f;
+  for (int r0 = 0; r0 < S; r0 += AD_ROWS) {
+    const int rows = min(AD_ROWS, S - r0);
+    __syncthreads();
+    for (int e = tid; e < rows * D; e += AD_THREADS) {
+      const int tok = tg_token(ids[u * S + r0 + e / D], vocab);
+      et[e] = shared[(size_t)tok * D + e % D];
+    }
+    __syncthreads();
+    ad_linear<false>(qt, D, et, D, wtab[A_IN_W], wtab[A_IN_B], D, D, rows);
+    __syncthreads();
+    // softmax(q k^T * scale) v per (row, head) over the nv keys
+    for (int it = tid; it < rows * nh; it += AD_THREADS) {
+      const int r = it / nh, h = it % nh;
+      const float* q = qt + r * D + h * hd;
+      float s[AD_MAX_VEC], mx = -INFINITY;
+#pragma unroll
+      for (int j = 0; j < AD_MAX_VEC; ++j) {
+        s[j] = -INFINITY;
+        if (j < nv) {
+          const float* kr = kvp + j * 2 * D + h * hd;
+          float a = 0.f;
+          for (int c = 0; c < hd; ++c) a = fmaf(q[c] * scale, kr[c], a);
+          s[j] = a;
+        }
+        mx = fmaxf(mx, s[j]);
+      }
+      float sum = 0.f;
+#pragma unroll
+      for (int j = 0; j < AD_MAX_VEC; ++j) {
+        s[j] = j < nv ? expf(s[j] - mx) : 0.f;
+        sum += s[j];
+      }
+      for (int c = 0; c < hd; ++c) {
+        float a = 0.f;
+#pragma unroll
+        for (int j = 0; j < AD_MAX_VEC; ++j)
+          if (j < nv) a = fmaf(s[j] / sum, kvp[j * 2 * D + D + h * hd + c], a);
+        hid[r * D + h * hd + c] = a;
+      }
+    }
+    __syncthreads();
+    ad_linear<false>(qt, D, hid, D, wtab[A_OUT_W], wtab[A_OUT_B], D, D, rows);
+    __syncthreads();
+    ad_layernorm(et, et, qt, wtab[A_N1_W], wtab[A_N1_B], rows, D, eps);
+    __syncthreads();
+    ad_linear<true>(hid, 4 * D, et, D, wtab[A_FF1_W], wtab[A_FF1_B], 4 * D, D, rows);
+    __syncthreads();
+    ad_linear<false>(qt, D, hid, 4 * D, wtab[A_FF2_W], wtab[A_FF2_B], D, 4 * D, rows);
+    __syncthreads();
+    ad_layernorm(et, et, qt, wtab[A_N2_W], wtab[A_N2_B], rows, D, eps);
+    __syncthreads();
+    if (tid < D)
+      for (int r = 0; r < rows; ++r) {
+        const float y = et[r * D + tid] - mcomp, t = msum + y;
+        mcomp = (t - msum) - y;
+        msum = t;
+      }
+  }
+  if (tid < D) {
+    const float v = msum / (float)S;
+    prefix_ws[(u * 3 + level) * D + tid] = v;
+    if (prefix_out) prefix_out[(u * 3 + level) * D + tid] = v;
+  }
+}
+
 __global__ void beam_hits_kernel(const int64_t* __restrict__ preds, int64_t B, int k, int pred_len, int64_t ld,
                                  const int64_t* __restrict__ labels, int label_len, uint8_t* __restrict__ hits) {
   const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -658,68 +845,157 @@ size_t tiger_self_floats(const gr_tiger_params* p, int64_t B, int nb, int T) {
 }  // namespace
 }  // namespace gr
 
-extern "C" size_t gr_tiger_workspace_bytes(const gr_tiger_params* p, int64_t B, int32_t S, int32_t num_beams,
-                                           int32_t max_length) {
-  if (gr::tiger_check(p, B, S, num_beams, max_length)) return 0;
-  const size_t f = gr::align_up(gr::tiger_cross_floats(p, B, S), 4) + gr::tiger_self_floats(p, B, num_beams, max_length);
-  return gr::align_up(f * sizeof(float), 16) + 16;
+namespace gr {
+namespace {
+
+constexpr int TG_PREFIX = 3;   // prefix tokens ahead of the history
+
+const char* tiger_prefix_check(const gr_tiger_params* p, const gr_tiger_prefix_params* pp, int S) {
+  if (!p) return "null params";
+  if (!pp) return "null prefix params";
+  if (pp->bert_dim < 4 || pp->bert_dim > AD_MAX_BERT || pp->bert_dim % 4)
+    return "bert_dim must be a multiple of 4 in [4, 1024]";
+  if (pp->n_vec < 1 || pp->n_vec > AD_MAX_VEC) return "n_vec must be 1..16";
+  if (pp->n_heads < 1 || p->d_model % pp->n_heads) return "d_model must be a multiple of the adapters' num_heads";
+  if (S < 1 || S > TG_MAX_S - TG_PREFIX)
+    return "the history must hold 1..125 tokens (128 encoder positions with the three prefix tokens)";
+  return nullptr;
 }
 
-extern "C" int gr_tiger_generate_f32(const gr_tiger_params* p, const int64_t* input_ids,
-                                     const int64_t* attention_mask, int64_t B, int32_t S, int32_t num_beams,
-                                     int32_t max_length, int64_t* sequences, float* scores, float* enc_out,
-                                     float* step_logits, void* workspace, size_t workspace_bytes, void* stream) {
-  using namespace gr;
+size_t tiger_plain_bytes(const gr_tiger_params* p, int64_t B, int S, int nb, int T) {
+  const size_t f = align_up(tiger_cross_floats(p, B, S), 4) + tiger_self_floats(p, B, nb, T);
+  return align_up(f * sizeof(float), 16) + 16;
+}
+
+size_t tiger_mask_bytes(int64_t B, int S) { return align_up((size_t)B * (S + TG_PREFIX) * sizeof(int64_t), 16); }
+
+size_t tiger_prefix_bytes(const gr_tiger_params* p, int64_t B) {
+  return align_up((size_t)B * TG_PREFIX * p->d_model * sizeof(float), 16);
+}
+
+// Both entries: pp == nullptr is gr_tiger_generate_f32 (two launches); otherwise the adapter launch comes
+// first and the encoder and the search run on S + 3 positions with the mask it wrote.
+int tiger_generate(const char* fn, const gr_tiger_params* p, const gr_tiger_prefix_params* pp, const int64_t* input_ids,
+                   const int64_t* attention_mask, const float* const* prof, int64_t B, int32_t S, int32_t num_beams,
+                   int32_t max_length, int64_t* sequences, float* scores, float* prefix_out, float* enc_out,
+                   float* step_logits, void* workspace, size_t workspace_bytes, void* stream, bool prefixed) {
   clear_error();
-  if (const char* why = tiger_check(p, B, S, num_beams, max_length)) {
+  const std::string who = std::string(fn) + ": ";
+  if (prefixed) {
+    if (const char* why = tiger_prefix_check(p, pp, S)) return fail(!p || !pp ? GR_ERR_ARG : GR_ERR_UNSUPPORTED, who + why);
+  }
+  const int St = prefixed ? S + TG_PREFIX : S;   // encoder positions
+  if (const char* why = tiger_check(p, B, St, num_beams, max_length)) {
     const bool arg = !p || B < 0;
-    return fail(arg ? GR_ERR_ARG : GR_ERR_UNSUPPORTED, std::string("gr_tiger_generate_f32: ") + why);
+    return fail(arg ? GR_ERR_ARG : GR_ERR_UNSUPPORTED, who + why);
   }
   if (p->eos_id < 0 || p->eos_id >= p->vocab || p->pad_id < 0 || p->pad_id >= p->vocab || p->fill_id < 0 ||
       p->fill_id >= p->vocab)
-    return fail(GR_ERR_ARG, "gr_tiger_generate_f32: pad, eos and fill ids must lie in [0, vocab)");
-  const size_t need = gr_tiger_workspace_bytes(p, B, S, num_beams, max_length);
+    return fail(GR_ERR_ARG, who + "pad, eos and fill ids must lie in [0, vocab)");
+  if (prefixed) {
+    bool ok = true;
+    for (int l = 0; l < 3; ++l)
+      for (int i = 0; i < 14; ++i) ok = ok && pp->adapter[l][i] && aligned16(pp->adapter[l][i]);
+    if (!ok) return fail(GR_ERR_ARG, who + "an adapter weight pointer is null or not 16-byte aligned");
+    for (int l = 0; l < 3; ++l)
+      if (!prof[l] || !aligned16(prof[l]))
+        return fail(GR_ERR_ARG, who + "a prof_lvl pointer is null or not 16-byte aligned");
+  }
+  const size_t plain = tiger_plain_bytes(p, B, St, num_beams, max_length);
+  const size_t need = prefixed ? plain + tiger_mask_bytes(B, S) + tiger_prefix_bytes(p, B) : plain;
   if (!workspace || workspace_bytes < need || !aligned16(workspace))
-    return fail(GR_ERR_WORKSPACE, "gr_tiger_generate_f32: workspace missing, misaligned or smaller than "
-                                  "gr_tiger_workspace_bytes");
-  if (!input_ids || !sequences || !scores) return fail(GR_ERR_ARG, "gr_tiger_generate_f32: null pointer");
+    return fail(GR_ERR_WORKSPACE, who + "workspace missing, misaligned or smaller than " +
+                                      (prefixed ? "gr_tiger_prefix_workspace_bytes" : "gr_tiger_workspace_bytes"));
+  if (!input_ids || !sequences || !scores) return fail(GR_ERR_ARG, who + "null pointer");
   bool ok = p->shared && p->lm_head && p->enc_rel && p->dec_rel && p->enc_final_ln && p->dec_final_ln &&
             p->enc_bucket && p->dec_bucket && aligned16(p->shared) && aligned16(p->lm_head);
   for (int l = 0; ok && l < p->n_enc; ++l)
     for (int i = 0; i < 8; ++i) ok = ok && p->enc[l][i] && aligned16(p->enc[l][i]);
   for (int l = 0; ok && l < p->n_dec; ++l)
     for (int i = 0; i < 13; ++i) ok = ok && p->dec[l][i] && aligned16(p->dec[l][i]);
-  if (!ok) return fail(GR_ERR_ARG, "gr_tiger_generate_f32: a weight pointer is null or not 16-byte aligned");
+  if (!ok) return fail(GR_ERR_ARG, who + "a weight pointer is null or not 16-byte aligned");
   if (B == 0) return GR_OK;
   const int inner = p->n_heads * p->d_kv;
-  const EncLayout EL = enc_layout(S, p->d_model, inner, p->d_kv, p->n_heads, p->d_ff, TG_ENC_THREADS / 64);
+  const EncLayout EL = enc_layout(St, p->d_model, inner, p->d_kv, p->n_heads, p->d_ff, TG_ENC_THREADS / 64);
   const size_t enc_lds = (size_t)EL.total * sizeof(float), srch_lds = (size_t)SR_TOTAL * sizeof(float);
   constexpr size_t kLdsMax = 159 * 1024;   // dynamic part; the kernels' static LDS is under 1 KB
   if (enc_lds > kLdsMax || srch_lds > kLdsMax)
-    return fail(GR_ERR_UNSUPPORTED, "gr_tiger_generate_f32: the per-user state does not fit in LDS");
+    return fail(GR_ERR_UNSUPPORTED, who + "the per-user state does not fit in LDS");
   // the limit is a property of the kernel on the current device: raised on each device's first call
   static std::atomic<uint64_t> lds_raised{0};
   int devid = 0;
-  if (hipGetDevice(&devid) != hipSuccess) return fail(GR_ERR_HIP, "gr_tiger_generate_f32: no current device");
+  if (hipGetDevice(&devid) != hipSuccess) return fail(GR_ERR_HIP, who + "no current device");
   const uint64_t bit = 1ull << (devid & 63);
   if (!(lds_raised.load() & bit)) {
     const bool lds_ok =
-        hipFuncSetAttribute(reinterpret_cast<const void*>(tiger_encoder_kernel),
+        hipFuncSetAttribute(reinterpret_cast<const void*>(tiger_encoder_kernel<false>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax) == hipSuccess &&
+        hipFuncSetAttribute(reinterpret_cast<const void*>(tiger_encoder_kernel<true>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax) == hipSuccess &&
         hipFuncSetAttribute(reinterpret_cast<const void*>(tiger_search_kernel),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax) == hipSuccess;
-    if (!lds_ok) return fail(GR_ERR_HIP, "gr_tiger_generate_f32: cannot raise the dynamic LDS limit");
+    if (!lds_ok) return fail(GR_ERR_HIP, who + "cannot raise the dynamic LDS limit");
     lds_raised.fetch_or(bit);
   }
   float* cross = static_cast<float*>(workspace);
-  float* selfkv = cross + align_up(tiger_cross_floats(p, B, S), 4);
+  float* selfkv = cross + align_up(tiger_cross_floats(p, B, St), 4);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  tiger_encoder_kernel<<<dim3((unsigned)B), dim3(TG_ENC_THREADS), enc_lds, st>>>(*p, input_ids, attention_mask, S, cross,
-                                                                            enc_out);
-  if (int rc = check_launch("tiger_encoder_kernel")) return rc;
+  if (prefixed) {
+    int64_t* ext_mask = reinterpret_cast<int64_t*>(static_cast<char*>(workspace) + plain);
+    float* prefix = reinterpret_cast<float*>(static_cast<char*>(workspace) + plain + tiger_mask_bytes(B, S));
+    tiger_adapter_kernel<<<dim3((unsigned)B, TG_PREFIX), dim3(AD_THREADS), 0, st>>>(
+        *pp, p->shared, p->vocab, p->d_model, input_ids, attention_mask, prof[0], prof[1], prof[2], S, ext_mask, prefix,
+        prefix_out);
+    if (int rc = check_launch("tiger_adapter_kernel")) return rc;
+    tiger_encoder_kernel<true><<<dim3((unsigned)B), dim3(TG_ENC_THREADS), enc_lds, st>>>(*p, input_ids, ext_mask, St,
+                                                                                     cross, enc_out, prefix);
+    if (int rc = check_launch("tiger_encoder_kernel<true>")) return rc;
+    attention_mask = ext_mask;
+  } else {
+    tiger_encoder_kernel<false><<<dim3((unsigned)B), dim3(TG_ENC_THREADS), enc_lds, st>>>(*p, input_ids, attention_mask, S,
+                                                                                     cross, enc_out, nullptr);
+    if (int rc = check_launch("tiger_encoder_kernel")) return rc;
+  }
   tiger_search_kernel<<<dim3((unsigned)B), dim3(TG_SRCH_THREADS), srch_lds, st>>>(
-      *p, attention_mask, S, num_beams, max_length, cross, selfkv, sequences, scores, step_logits);
+      *p, attention_mask, St, num_beams, max_length, cross, selfkv, sequences, scores, step_logits);
   return check_launch("tiger_search_kernel");
+}
+
+}  // namespace
+}  // namespace gr
+
+extern "C" size_t gr_tiger_workspace_bytes(const gr_tiger_params* p, int64_t B, int32_t S, int32_t num_beams,
+                                           int32_t max_length) {
+  if (gr::tiger_check(p, B, S, num_beams, max_length)) return 0;
+  return gr::tiger_plain_bytes(p, B, S, num_beams, max_length);
+}
+
+extern "C" int gr_tiger_generate_f32(const gr_tiger_params* p, const int64_t* input_ids,
+                                     const int64_t* attention_mask, int64_t B, int32_t S, int32_t num_beams,
+                                     int32_t max_length, int64_t* sequences, float* scores, float* enc_out,
+                                     float* step_logits, void* workspace, size_t workspace_bytes, void* stream) {
+  return gr::tiger_generate("gr_tiger_generate_f32", p, nullptr, input_ids, attention_mask, nullptr, B, S, num_beams,
+                            max_length, sequences, scores, nullptr, enc_out, step_logits, workspace, workspace_bytes,
+                            stream, false);
+}
+
+extern "C" size_t gr_tiger_prefix_workspace_bytes(const gr_tiger_params* p, const gr_tiger_prefix_params* pp,
+                                                  int64_t B, int32_t S, int32_t num_beams, int32_t max_length) {
+  using namespace gr;
+  if (tiger_prefix_check(p, pp, S) || tiger_check(p, B, S + TG_PREFIX, num_beams, max_length)) return 0;
+  return tiger_plain_bytes(p, B, S + TG_PREFIX, num_beams, max_length) + tiger_mask_bytes(B, S) + tiger_prefix_bytes(p, B);
+}
+
+extern "C" int gr_tiger_generate_prefix_f32(const gr_tiger_params* p, const gr_tiger_prefix_params* pp,
+                                            const int64_t* input_ids, const int64_t* attention_mask,
+                                            const float* prof1, const float* prof2, const float* prof3, int64_t B,
+                                            int32_t S, int32_t num_beams, int32_t max_length, int64_t* sequences,
+                                            float* scores, float* prefix_out, float* enc_out, float* step_logits,
+                                            void* workspace, size_t workspace_bytes, void* stream) {
+  const float* prof[3] = {prof1, prof2, prof3};
+  return gr::tiger_generate("gr_tiger_generate_prefix_f32", p, pp, input_ids, attention_mask, prof, B, S, num_beams,
+                            max_length, sequences, scores, prefix_out, enc_out, step_logits, workspace, workspace_bytes,
+                            stream, true);
 }
 
 extern "C" int gr_beam_hits_i64(const int64_t* preds, int64_t B, int32_t k, int32_t pred_len, int64_t ld_pred,

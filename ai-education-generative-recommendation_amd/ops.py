@@ -1729,6 +1729,123 @@ def tiger_generate(binding, input_ids, attention_mask=None, num_beams=20, max_le
     return out
 
 
+TIGER_ADAPTER_KEYS = ("bert_proj.weight", "bert_proj.bias", "cross_attn.in_proj_weight", "cross_attn.in_proj_bias",
+                      "cross_attn.out_proj.weight", "cross_attn.out_proj.bias", "ffn.0.weight", "ffn.0.bias",
+                      "ffn.2.weight", "ffn.2.bias", "norm1.weight", "norm1.bias", "norm2.weight", "norm2.bias")
+TIGER_PREFIX_ENVELOPE = ("with prof_lvl1..3: at most 125 history tokens (128 encoder positions with the three prefix "
+                         "tokens); bert_dim a multiple of 4 in [4, 1024]; 1..16 vectors per level; d_model a multiple "
+                         "of num_heads")
+
+
+def tiger_prefix_check(cfg, bert_dim, n_vec=None, S=None):
+    """Raise NotImplementedError, naming the limit, for what the adapter kernel does not cover."""
+    def no(msg):
+        raise NotImplementedError(f"TIGER: {msg} (the gfx950 kernels cover: {TIGER_ENVELOPE}; {TIGER_PREFIX_ENVELOPE}); "
+                                  "there is no CPU fallback")
+    if not 4 <= int(bert_dim) <= 1024 or int(bert_dim) % 4:
+        no(f"bert_dim={bert_dim} must be a multiple of 4 in [4, 1024]")
+    if int(cfg["d_model"]) % int(cfg["num_heads"]):
+        no(f"d_model={cfg['d_model']} must be a multiple of num_heads={cfg['num_heads']} (the adapters' head width)")
+    if n_vec is not None and not 1 <= n_vec <= 16:
+        no(f"n_vec={n_vec} vectors per level; 1..16 are supported")
+    if S is not None and not 1 <= S <= 125:
+        no(f"a history of {S} tokens; with the three prefix tokens at most 125 are supported")
+
+
+class TigerPrefixBinding:
+    """Device-pointer view of a prefix model: the T5 parameters (``.t5``, a ``TigerBinding``) and the three
+    adapters (``gr_tiger_prefix_params``).  ``adapters``: name -> tensor with the reference's names
+    (``adapter_lvl1.bert_proj.weight``, ...).  The pointers are the tensors' own storage, so in-place
+    weight updates are seen by the next call."""
+
+    def __init__(self, cfg, tensors, adapters, ln_eps=1e-5):
+        self.t5 = TigerBinding(cfg, tensors)
+        self.cfg = cfg
+        self.device = self.t5.device
+        self.bert_dim = int(adapters["adapter_lvl1.bert_proj.weight"].shape[1])
+        tiger_prefix_check(cfg, self.bert_dim)
+        self.keep = []
+        d = int(cfg["d_model"])
+        shapes = {"bert_proj.weight": (d, self.bert_dim), "cross_attn.in_proj_weight": (3 * d, d),
+                  "cross_attn.in_proj_bias": (3 * d,), "cross_attn.out_proj.weight": (d, d),
+                  "ffn.0.weight": (4 * d, d), "ffn.0.bias": (4 * d,), "ffn.2.weight": (d, 4 * d)}
+        pp = L.TigerPrefixParams()
+        pp.bert_dim, pp.n_heads, pp.eps = self.bert_dim, int(cfg["num_heads"]), float(ln_eps)
+        for lvl in range(3):
+            for i, k in enumerate(TIGER_ADAPTER_KEYS):
+                t = adapters[f"adapter_lvl{lvl + 1}.{k}"]
+                if tuple(t.shape) != shapes.get(k, (d,)):
+                    raise RuntimeError(f"adapter_lvl{lvl + 1}.{k} must be {shapes.get(k, (d,))}, got {tuple(t.shape)}")
+                if t.device != self.device:
+                    raise RuntimeError("the adapters and the T5 parameters must be on one device")
+                pp.adapter[lvl][i] = self.t5._f(t)
+        self.params = pp
+        self._ws = {}
+
+    def ref(self, n_vec):
+        self.params.n_vec = n_vec
+        return ctypes.byref(self.params)
+
+    def workspace_bytes(self, n_vec, B, S, num_beams, max_length):
+        key = (n_vec, B, S, num_beams, max_length)
+        n = self._ws.get(key)
+        if n is None:
+            n = self._ws[key] = L.lib().gr_tiger_prefix_workspace_bytes(self.t5.ref, self.ref(n_vec), B, S, num_beams,
+                                                                        max_length)
+        return n
+
+
+def tiger_generate_prefix(binding, input_ids, attention_mask, prof_lvl1, prof_lvl2, prof_lvl3, num_beams=20,
+                          max_length=5, with_prefix=False, with_encoder=False, with_logits=False):
+    """``gr_tiger_generate_prefix_f32``: the three adapters, T5 encode on S + 3 positions and the whole beam
+    search in one C call (three launches), nothing synchronises.  prof_lvl1..3 [B, n_vec, bert_dim] fp32.
+    -> (sequences [B, num_beams, max_length] int64, scores [B, num_beams] fp32[, prefix tokens
+    [B, 3, d_model]][, encoder output [B, S + 3, d_model]][, step logits [B, max_length - 1, num_beams,
+    vocab]])."""
+    prof = [prof_lvl1, prof_lvl2, prof_lvl3]
+    L.require_gpu(input_ids, *prof)
+    if input_ids.dim() != 2 or input_ids.dtype != torch.int64:
+        raise RuntimeError(f"tiger_generate_prefix takes [B, S] int64 token ids, got {tuple(input_ids.shape)} "
+                           f"{input_ids.dtype}")
+    B, S = input_ids.shape
+    num_beams, max_length = int(num_beams), int(max_length)
+    n_vec = int(prof[0].shape[1]) if prof[0].dim() == 3 else -1
+    for i, t in enumerate(prof):
+        if t.dtype != torch.float32 or tuple(t.shape) != (B, n_vec, binding.bert_dim):
+            raise RuntimeError(f"prof_lvl{i + 1} must be float32 [{B}, n_vec, {binding.bert_dim}], got {t.dtype} "
+                               f"{tuple(t.shape)}")
+    tiger_prefix_check(binding.cfg, binding.bert_dim, n_vec, S)
+    tiger_check_config(binding.cfg, num_beams, S + 3, max_length)
+    prof = [t.contiguous() for t in prof]
+    input_ids = input_ids.contiguous()
+    if attention_mask is not None:
+        L.require_gpu(attention_mask)
+        if tuple(attention_mask.shape) != (B, S):
+            raise RuntimeError(f"attention_mask must be [{B}, {S}], got {tuple(attention_mask.shape)}")
+        if attention_mask.dtype != torch.int64:
+            attention_mask = attention_mask.to(torch.int64)
+        attention_mask = attention_mask.contiguous()
+    dev = input_ids.device
+    V, D = binding.t5.params.vocab, binding.t5.params.d_model
+    seqs = torch.empty((B, num_beams, max_length), dtype=torch.int64, device=dev)
+    scores = torch.empty((B, num_beams), dtype=torch.float32, device=dev)
+    prefix = torch.empty((B, 3, D), dtype=torch.float32, device=dev) if with_prefix else None
+    enc = torch.empty((B, S + 3, D), dtype=torch.float32, device=dev) if with_encoder else None
+    logits = torch.empty((B, max_length - 1, num_beams, V), dtype=torch.float32, device=dev) if with_logits else None
+    nbytes = binding.workspace_bytes(n_vec, B, S, num_beams, max_length)
+    wsp = L.workspace(nbytes, dev)
+    with L.on(dev):
+        L.check(L.lib().gr_tiger_generate_prefix_f32(
+            binding.t5.ref, binding.ref(n_vec), L.ptr(input_ids), L.ptr(attention_mask), L.ptr(prof[0]), L.ptr(prof[1]),
+            L.ptr(prof[2]), B, S, num_beams, max_length, L.ptr(seqs), L.ptr(scores), L.ptr(prefix), L.ptr(enc),
+            L.ptr(logits), L.ptr(wsp), nbytes, L.stream_of(dev)), "gr_tiger_generate_prefix_f32")
+    out = (seqs, scores)
+    for on, t in ((with_prefix, prefix), (with_encoder, enc), (with_logits, logits)):
+        if on:
+            out += (t,)
+    return out
+
+
 def beam_hits(preds, labels, skip=0):
     """``calculate_pos_index`` (RQVAE-T5/utils.py:6-32) on the device: preds [B, k, T] int64 (the first
     ``skip`` tokens of each hypothesis dropped, the rest zero-padded or cut to the labels' width), labels

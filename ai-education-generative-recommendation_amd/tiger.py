@@ -156,11 +156,13 @@ def codes_to_tokens(codes, codebook_size):
     return codes + np.arange(codes.shape[-1], dtype=codes.dtype) * codebook_size + 1
 
 
-def collate(histories, targets, max_len):
+def collate(histories, targets, max_len, prof_lvl1=None, prof_lvl2=None, prof_lvl3=None):
     """``GenRecDataLoader.collate_fn`` after ``pad_or_truncate``: each history ([n_i, L] tokens) keeps its
     last ``max_len`` items and is left-padded with zero codes, then flattened; the mask is 1 where the
     token is not 0; the flattened targets are right-padded with -100.  -> dict of int64 tensors
-    ``history`` [B, max_len * L], ``attention_mask`` and ``target``."""
+    ``history`` [B, max_len * L], ``attention_mask`` and ``target``.  ``prof_lvl1..3`` (the prefix variant,
+    RQVAE-T5-prefix/data_vision.py:170-172): per level one (n_vec, bert_dim) array per user, stacked as
+    float32 ``prof_lvl1..3`` [B, n_vec, bert_dim]."""
     hs = [np.asarray(h, dtype=np.int64) for h in histories]
     L_ = hs[0].shape[-1]
     hist = np.zeros((len(hs), max_len, L_), np.int64)
@@ -174,8 +176,12 @@ def collate(histories, targets, max_len):
     tgt = np.full((len(ts), width), -100, np.int64)
     for i, t in enumerate(ts):
         tgt[i, :len(t)] = t
-    return {"history": torch.from_numpy(hist), "target": torch.from_numpy(tgt),
-            "attention_mask": torch.from_numpy((hist != 0).astype(np.int64))}
+    out = {"history": torch.from_numpy(hist), "target": torch.from_numpy(tgt),
+           "attention_mask": torch.from_numpy((hist != 0).astype(np.int64))}
+    for name, prof in (("prof_lvl1", prof_lvl1), ("prof_lvl2", prof_lvl2), ("prof_lvl3", prof_lvl3)):
+        if prof is not None:
+            out[name] = torch.from_numpy(np.stack([np.asarray(v, dtype=np.float32) for v in prof]))
+    return out
 
 
 def crop_like_library(seqs, eos_id):
@@ -193,7 +199,8 @@ def crop_like_library(seqs, eos_id):
 
 @torch.no_grad()
 def evaluate_model(model, batches, topk_list, beam_size, device=None):
-    """RQVAE-T5/utils.py:44-92: one generate per batch at max(max(topk_list), beam_size) beams, the start
+    """RQVAE-T5/utils.py:44-92 (and RQVAE-T5-prefix/utils.py:44-102: a batch that carries ``prof_lvl1..3``
+    passes them to the model): one generate per batch at max(max(topk_list), beam_size) beams, the start
     token dropped, hypotheses padded or cut to the label width, the first exact match per user found
     on the device (``gr_beam_hits_i64``; the columns the library would have cropped compare as the zeros
     the reference pads with, ``crop_like_library``), Recall@k and NDCG@k as per-batch means averaged over the
@@ -207,7 +214,10 @@ def evaluate_model(model, batches, topk_list, beam_size, device=None):
         ids = batch["history"].to(device)
         mask = batch["attention_mask"].to(device)
         labels = batch["target"].to(device)
-        seqs, _ = model.generate_scored(ids, mask, beams)
+        prof = {}
+        if batch.get("prof_lvl1") is not None:      # RQVAE-T5-prefix/utils.py:61-77
+            prof = {k: batch[k].to(device) for k in ("prof_lvl1", "prof_lvl2", "prof_lvl3")}
+        seqs, _ = model.generate_scored(ids, mask, beams, **prof)
         seqs = crop_like_library(seqs, model.binding().params.eos_id)
         pos = ops.beam_hits(seqs, labels, skip=1).cpu()
         ranks = torch.arange(1, pos.shape[-1] + 1)

@@ -690,6 +690,46 @@ int gr_tiger_generate_f32(const gr_tiger_params* p, const int64_t* input_ids, co
                           float* scores, float* enc_out, float* step_logits, void* workspace,
                           size_t workspace_bytes, void* stream);
 
+/* TIGER prefix variant (RQVAE-T5-prefix/model.py: three ProfessionalAdapter modules, each turning the
+ * history's token embeddings and the user's n_vec BERT vectors of one level of the professional
+ * hierarchy into one prefix token; the three tokens are prepended to the encoder input and the beam
+ * search runs on S + 3 encoder positions).  Inference only, eval-mode arithmetic (no dropout).
+ *
+ * gr_tiger_prefix_params: adapter[level] = {bert_proj.weight [d, bert_dim], bert_proj.bias,
+ * cross_attn.in_proj_weight [3 d, d], in_proj_bias, cross_attn.out_proj.weight [d, d], out_proj.bias,
+ * ffn.0.weight [4 d, d], ffn.0.bias, ffn.2.weight [d, 4 d], ffn.2.bias, norm1.weight, norm1.bias,
+ * norm2.weight, norm2.bias}: fp32 device pointers, 16-byte aligned.  n_heads is the adapters'
+ * nn.MultiheadAttention head count: the head width is d_model / n_heads (not d_kv) and the scores are
+ * scaled by its inverse square root.  eps is the two LayerNorms' (biased variance).
+ *
+ * gr_tiger_generate_prefix_f32 enqueues three launches and never synchronises: tiger_adapter_kernel
+ * (one workgroup per user and level; the embeddings of all S positions, padding included, are
+ * attended to the n_vec projected vectors, normalised, fed forward and averaged over S in a fixed
+ * order, so a call is bitwise repeatable; it also writes the [B, S + 3] key mask, whose first three
+ * columns are 1), then gr_tiger_generate_f32's encoder and search kernels on S + 3 positions.
+ *   prof1..3[B, n_vec, bert_dim] fp32, 16-byte aligned
+ *   prefix_out[B, 3, d_model] (optional): the three prefix tokens
+ *   enc_out[B, S + 3, d_model] (optional); the other arguments as in gr_tiger_generate_f32
+ * Envelope: gr_tiger_generate_f32's with S + 3 in place of S (so S <= 125), bert_dim a multiple of 4
+ * in [4, 1024], 1 <= n_vec <= 16, d_model % n_heads == 0.  The prefix variant's deployed width
+ * (d_model 128, d_ff 512, 8 heads) is outside gr_tiger_params' envelope and is refused by it.
+ * workspace: gr_tiger_prefix_workspace_bytes(...) = gr_tiger_workspace_bytes at S + 3, the int64 mask
+ * and the prefix tokens (0 outside the envelope). */
+typedef struct gr_tiger_prefix_params {
+  int32_t bert_dim, n_vec, n_heads, reserved;
+  float eps, reserved_f;
+  const float* adapter[3][14];
+} gr_tiger_prefix_params;
+
+size_t gr_tiger_prefix_workspace_bytes(const gr_tiger_params* p, const gr_tiger_prefix_params* pp, int64_t B,
+                                       int32_t S, int32_t num_beams, int32_t max_length);
+int gr_tiger_generate_prefix_f32(const gr_tiger_params* p, const gr_tiger_prefix_params* pp,
+                                 const int64_t* input_ids, const int64_t* attention_mask, const float* prof1,
+                                 const float* prof2, const float* prof3, int64_t B, int32_t S, int32_t num_beams,
+                                 int32_t max_length, int64_t* sequences, float* scores, float* prefix_out,
+                                 float* enc_out, float* step_logits, void* workspace, size_t workspace_bytes,
+                                 void* stream);
+
 /* calculate_pos_index of RQVAE-T5/utils.py:6-32: hits[b, j] = 1 for the first beam j whose tokens
  * equal labels[b, :], 0 elsewhere.  preds: beam j of user b starts at preds + (b * k + j) * ld_pred
  * and holds pred_len tokens; positions past pred_len compare as 0 (evaluate_model's zero padding) and
