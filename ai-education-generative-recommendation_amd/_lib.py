@@ -85,6 +85,10 @@ SIGNATURES = {
     "gr_rq_encoder_pack_f32": (ctypes.c_int, [_i32, _vp, _vp, _vp, _vp]),
     "gr_rq_encode_packed_f32": (ctypes.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp,
                                                _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gr_rq_codebook_image_floats": (_sz, [_i32, _i32, _vp]),
+    "gr_rq_codebook_pack_f32": (ctypes.c_int, [_i32, _i32, _vp, _vp, _vp, _vp]),
+    "gr_rq_encode_image_f32": (ctypes.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp,
+                                              _vp, _vp, _vp, _vp, _sz, _vp]),
     "gr_rq_mlp_workspace_bytes": (_sz, [_i64, _i32, _vp]),
     "gr_rq_mlp_f32": (ctypes.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "gr_mlp_exact_f32": (ctypes.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _i32,
@@ -95,6 +99,8 @@ SIGNATURES = {
     "gr_rq_filter_bound_f32": (_f32, [_f32, _f32]),
     "gr_rq_filter_launches": (_i64, []),
     "gr_rq_filter_diag_counts": (None, [_vp]),
+    "gr_rq_leftover_launches": (_i64, []),
+    "gr_rq_filter_plan": (ctypes.c_int, [_i64, _i32, _i32, _vp, _vp, _vp]),
     "gr_rq_encode_sk_workspace_bytes": (_sz, [_i64, _i32, _i32, _vp]),
     "gr_rq_encode_sk_f32": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _i64,
                                            _vp, _vp, _sz, _vp]),

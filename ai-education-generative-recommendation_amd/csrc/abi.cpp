@@ -54,6 +54,10 @@ static std::atomic<int64_t> g_attn_k16{1};
 // rq_filter (index-only quantize calls at e = 32, codebooks up to 1024 codes: 1 = split-bf16 filter
 // passes and the exact formula on the near-minimum codes only, 0 = every distance exact)
 static std::atomic<int64_t> g_rq_filter{1};
+// rq_tail_merge (encode calls that run the fused encoder with leftover tiles and the filtered
+// quantizer: 1 = the quantizer's workgroups finish the leftover tiles' layers 2-3 themselves, two
+// launches per call; 0 = rq_leftover_kernel between the two, three launches)
+static std::atomic<int64_t> g_rq_tail_merge{1};
 
 // kmeans_small (1: gr_kmeans_f32 in one launch of one workgroup when the rows fit in LDS, 0: always
 // one launch per phase over row tiles; the same phase code either way)
@@ -63,6 +67,7 @@ static const Opt kOpts[] = {
     {"rq_fused", &g_rq_fused, 0, 1},   {"sas_fused", &g_sas_fused, 0, 3}, {"sas_rowtile", &g_sas_rowtile, 0, 1},
     {"lin_wres", &g_lin_wres, 0, 1},   {"emb_proj", &g_emb_proj, 0, 1},   {"topk_half", &g_topk_half, 0, 2},
     {"attn_k16", &g_attn_k16, 0, 1},   {"rq_filter", &g_rq_filter, 0, 1}, {"kmeans_small", &g_kmeans_small, 0, 1},
+    {"rq_tail_merge", &g_rq_tail_merge, 0, 1},
 };
 
 static const Opt* find_opt(const char* name) {

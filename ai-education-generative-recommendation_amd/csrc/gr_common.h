@@ -330,12 +330,23 @@ __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 
+// Layers 2-3 of the fused encoder's leftover tiles, handed back by gr_rq_encoder_fused_launch for the
+// quantizer launch to finish: tiles [t0, t0 + left) of the call, their relu(h1) in h1g ([left][32][256]),
+// W2 (16x16x4 order) and W3 from the packed image, z the encoder's output buffer.
+struct RqPending {
+  const float* h1g = nullptr;
+  int t0 = 0, left = 0;
+  const float *W2 = nullptr, *b2 = nullptr, *W3 = nullptr, *b3 = nullptr;
+  float* z = nullptr;
+};
+
 }  // namespace gr
 
 // Internal launchers shared between translation units (all enqueue on `stream`, no sync).
 int gr_rq_encoder_fused_launch(const float* x, int64_t n, int32_t n_linear, const int32_t* dims,
                                const float* const* weights, const float* const* biases,
-                               float* z_out, float* pack, hipStream_t st, bool pack_is_ready, float* scratch);
+                               float* z_out, float* pack, hipStream_t st, bool pack_is_ready, float* scratch,
+                               gr::RqPending* pending = nullptr);
 int gr_rq_encoder_pack_launch(int32_t n_linear, const int32_t* dims, const float* const* weights, float* pack,
                               hipStream_t st);
 size_t gr_rq_fused_pack_floats(int32_t n_linear, const int32_t* dims);

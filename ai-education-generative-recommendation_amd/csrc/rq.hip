@@ -32,6 +32,7 @@
 #include <atomic>
 
 #include "gr_common.h"
+#include "rq_fused.h"
 #include "rq_quant.h"
 
 #ifndef GR_QDIAG
@@ -49,7 +50,6 @@ struct RQLevels {
   int K[GR_MAX_LEVELS];
 };
 
-constexpr int RQ_W = 8;              // waves per quantize workgroup
 constexpr int RQ_SPLIT_MAX = 3;      // leftover tiles per workgroup split into code quarters (c % 4)
 constexpr size_t RQ_PART_BYTES = 2 * RQ_SPLIT_MAX * 4 * 32 * 3 * sizeof(float);
 
@@ -356,8 +356,9 @@ __global__ __launch_bounds__(RQ_W * 64) void rq_quantize_kernel(
 // 16t + 8 + 2(i - 4) + h: the features a lane's residual registers hold), swizzled like the fp32
 // image; the norms; and, when it fits (K <= 512), the fp32 image for the walk and the winner's row
 // (else those rows come from global memory).  Codebooks of more than 1024 codes, e != 32 and the
-// calls that return distances stay on rq_quantize_kernel.  Tile plan: 8 waves, tile t_begin + w + 8i
-// for wave w (no code-quarter split, no resident levels); GR_FMAXT tiles per wave in registers.
+// calls that return distances stay on rq_quantize_kernel.  Tile plan: rq_filter_range (rq_fused.h)
+// gives the workgroup its tiles, wave w takes entries w + 8i of that list (no code-quarter split, no
+// resident levels); GR_FMAXT tiles per wave in registers.
 #ifndef GR_FDIAG
 #define GR_FDIAG 0   // diagnostic builds only (scripts/build_variant.sh): 1 no walk, 2 no pass 2 and no
 #endif               // walk, 4 no pass at all: staging, norms and the residual update (wrong IDs in
@@ -367,9 +368,6 @@ __global__ __launch_bounds__(RQ_W * 64) void rq_quantize_kernel(
 #endif
 #ifndef GR_FLIVE
 #define GR_FLIVE 1   // 0: recompute the MFMAs in pass 2 at every K (A/B builds)
-#endif
-#ifndef GR_FMAXT
-#define GR_FMAXT 2   // item tiles per wave held in registers (3: 238 VGPRs, 4 spills)
 #endif
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -395,30 +393,141 @@ __device__ __forceinline__ f32x16 filter_tile(const bf16x8 (&ah)[2], const bf16x
   return acc;
 }
 
+// One level's LDS images: the bf16 hi | lo image, the norms (+inf past K up to the rows the kernel
+// sweeps), each wave's maximum of the norms in wmax[0 .. W) and, when f32_lds, the fp32 image -- the
+// layout of rq_filter_kernel's dynamic LDS, filter_lds_floats(kch, f32_lds) floats.  Two sources, one
+// routine: derived from the codebook (img null), or copied from the image rq_cb_pack_kernel made with
+// this routine (every wmax slot then holds the level's maximum).  No barrier.
+// (rounded up to 1 KiB, one wave instruction of the LDS-DMA copy: filter_stage_dma)
+__host__ __device__ inline size_t filter_lds_floats(int kch, int f32_lds) {
+  return ((size_t)kch * 32 * (f32_lds ? 2 : 1) + (size_t)kch + 16 + 255) & ~(size_t)255;
+}
+#ifndef GR_FDMA
+#define GR_FDMA 1   // 0: a packed image is always staged by the single-buffer copy (A/B builds)
+#endif
+// A level's image into an LDS buffer by LDS-DMA, 16 bytes per lane: wave w moves the 1 KiB pieces
+// w, w + W, ... -- lane-linear on both sides (the image IS the LDS layout, swizzle included), no
+// registers.  Nothing is waited for here: the bytes have landed once the issuing wave's vmcnt has
+// drained, which the next __syncthreads() does for every wave.
+__device__ __forceinline__ void filter_stage_dma(const float* __restrict__ img, float* buf, int img_floats, int tid) {
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+  for (int c = w; c < img_floats / 256; c += RQ_W)
+    __builtin_amdgcn_global_load_lds(
+        reinterpret_cast<const __attribute__((address_space(1))) void*>(reinterpret_cast<uintptr_t>(img + c * 256 + lane * 4)),
+        (__attribute__((address_space(3))) void*)(buf + c * 256), 16, 0, 0);
+}
 template <bool LIVE>
+__device__ __forceinline__ void filter_stage(const float* __restrict__ cb, int K, int kch, int f32_lds, float* sm,
+                                             const float* __restrict__ img, int img_floats, int tid) {
+#pragma clang fp contract(off)
+  constexpr int EP = 32, W = RQ_W, NT = W * 64;
+  if (img) {   // workgroup-uniform: a straight, lane-linear copy
+    for (int f = tid; f < img_floats / 4; f += NT)
+      *reinterpret_cast<f32x4*>(sm + 4 * f) = *reinterpret_cast<const f32x4*>(img + 4 * f);
+    return;
+  }
+  float* bimg = sm;
+  float* cns = bimg + kch * EP;
+  float* wmax = cns + kch;
+  float* fimg = wmax + 16;
+  const int lane = tid & 63, w = tid >> 6, ct_n = (K + 31) >> 5;
+  for (int f = tid; f < 2 * K; f += NT) {   // 16 features of one code -> the four bf16 slots of step t
+    const int c = f >> 1, t = f & 1;
+    float x[16];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(cb + (int64_t)c * EP + 16 * t + 4 * q);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) x[4 * q + i] = v[i];
+    }
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh) {
+      bf16x8 vh, vl;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        __bf16 a, b;
+        split_bf16(x[(i < 4 ? 2 * i : 8 + 2 * (i - 4)) + hh], a, b);
+        vh[i] = a;
+        vl[i] = b;
+      }
+      *reinterpret_cast<bf16x8*>(bimg + cb_off<EP>(c, 2 * hh + t)) = vh;
+      *reinterpret_cast<bf16x8*>(bimg + cb_off<EP>(c, 4 + 2 * hh + t)) = vl;
+    }
+  }
+  if (f32_lds) stage_rows<EP, NT, true>(cb, EP, 0, K, fimg, tid);
+  float cmax = 0.f;   // max of the level's norms (a NaN norm is skipped: its code can never win)
+  for (int c = tid; c < (LIVE ? 256 : ct_n * 32); c += NT) {
+    float s = __builtin_inff();   // codes past K can never win
+    if (c < K) {
+      const float* row = cb + (int64_t)c * EP;
+      s = aten_rowsq([&](int f) { return row[f]; }, EP);
+      cmax = fmaxf(cmax, s);
+    }
+    cns[c] = s;
+  }
+  cmax = xmax<32>(xmax<16>(xmax<8>(xmax<4>(xmax<2>(xmax<1>(cmax))))));
+  if (lane == 0) wmax[w] = cmax;
+}
+
+// TAIL: the call's last tail.left tiles are the fused encoder's leftover tiles, whose layers 2-3 are
+// still pending (gr_rq_encoder_fused_launch handed them back): workgroup b < tail.left first finishes
+// leftover tile tail.t0 + b (rq_leftover_tile, what rq_leftover_kernel runs, its images aliasing this
+// kernel's LDS), then quantizes it with its main tiles (rq_filter_range) -- no workgroup waits for
+// another, and the encoder is followed by this launch alone.
+// DBUF (LIVE with a packed image): the levels' images alternate between two LDS buffers (below).
+template <bool LIVE, bool TAIL, bool DBUF>
 __global__ __launch_bounds__(RQ_W * 64) void rq_filter_kernel(
     const float* __restrict__ z, int64_t n, int L, RQLevels lv, int kch, int f32_lds,
-    int64_t* __restrict__ idx_out, int tiles, uint32_t* __restrict__ cand_out) {
+    int64_t* __restrict__ idx_out, int tiles, uint32_t* __restrict__ cand_out, RqPending tail,
+    const float* __restrict__ img, int img_floats) {
 #pragma clang fp contract(off)
-  constexpr int EP = 32, HQ = 4, W = RQ_W, NT = W * 64, MAXT = GR_FMAXT;
+  constexpr int EP = 32, HQ = 4, W = RQ_W, MAXT = GR_FMAXT;
   if (LIVE) f32_lds = 1;   // 256 codes: the fp32 image always fits
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  float* bimg = sm;                    // [kch] rows of 8 swizzled 16-byte slots: bf16 hi | lo
-  float* cns = bimg + kch * EP;        // [kch]
-  float* wmax = cns + kch;             // [W] per-wave max of the level's norms (+ padding to 16 floats)
-  float* fimg = wmax + 16;             // [kch][EP] the exact kernel's fp32 image (f32_lds)
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 31, h = lane >> 5;
-  const int t_begin = (int)((int64_t)blockIdx.x * tiles / gridDim.x);
-  const int t_end = (int)((int64_t)(blockIdx.x + 1) * tiles / gridDim.x);
-  const int my = (t_end - t_begin - w + W - 1) / W;   // this wave's tiles t_begin + w + i W (<= MAXT)
+  // Tile list of the workgroup: its main tiles [t_begin, t_end), then (an owner) its leftover tile;
+  // wave w takes entries w + i W.
+  const int left = TAIL ? tail.left : 0;
+  const bool owner = TAIL && (int)blockIdx.x < left;
+  int t_begin, t_end;
+  rq_filter_range(tiles, (int)gridDim.x, left, (int)blockIdx.x, t_begin, t_end);
+  const int cm = t_end - t_begin, lt = TAIL ? tail.t0 + (int)blockIdx.x : 0;
+  const int my = (cm + (owner ? 1 : 0) - w + W - 1) / W;   // this wave's entries (<= MAXT)
+  auto tile_at = [&](int i) -> int { return (TAIL && w + i * W >= cm) ? lt : t_begin + w + i * W; };
+
+  if constexpr (TAIL) {
+    if (owner) {   // workgroup-uniform
+      using FC = FusedCfg<256, 128>;
+      float *h1s = sm, *h2s = h1s + FT * FC::P1, *w3s = h2s + FT * FC::P2;
+      // z of the tile goes to global memory (with_z callers read it) and, for this workgroup's own
+      // quantization, to an LDS image over the start of h1s: layer 3 reads h2s and w3s only, behind
+      // the barrier that ends layer 2's reads of h1s.  The barrier below publishes the image to the
+      // wave that quantizes the tile; the level loop's first barrier ends every read of it before
+      // the codebook images overwrite it.  No global read-back, so nothing depends on when the z
+      // store becomes visible, and z (read-only here) is never read where this kernel wrote it.
+      rq_leftover_tile<256, 128, true>(tail.h1g + (int64_t)blockIdx.x * FT * 256, n, lt, tail.W2, tail.b2, tail.W3,
+                                       tail.b3, tail.z, h1s, h2s, w3s, h1s);
+      __syncthreads();
+    }
+  }
 
   // residual of this lane's item: half h holds features 8j + 2s + h
   f32x4 res[MAXT][HQ];
 #pragma unroll
   for (int i = 0; i < MAXT; ++i) {
-    const int64_t item = (int64_t)(t_begin + w + i * W) * 32 + r;
+    const int64_t item = (int64_t)tile_at(i) * 32 + r;
     const bool ok = i < my && item < n;
     const int64_t ic = ok ? item : 0;
+    if (TAIL && owner && i < my && w + i * W == cm) {   // wave-uniform: the leftover tile, from its LDS image
+#pragma unroll
+      for (int j = 0; j < HQ; ++j) {
+        const f32x4 lo = *reinterpret_cast<const f32x4*>(sm + r * ZLP + 8 * j);
+        const f32x4 hi = *reinterpret_cast<const f32x4*>(sm + r * ZLP + 8 * j + 4);
+        const f32x4 v = h ? f32x4{lo[1], lo[3], hi[1], hi[3]} : f32x4{lo[0], lo[2], hi[0], hi[2]};
+        res[i][j] = ok ? v : f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+      continue;
+    }
 #pragma unroll
     for (int j = 0; j < HQ; ++j) {
       const f32x4 lo = *reinterpret_cast<const f32x4*>(z + ic * EP + 8 * j);
@@ -432,44 +541,30 @@ __global__ __launch_bounds__(RQ_W * 64) void rq_filter_kernel(
     const int K = lv.K[l];
     const float* __restrict__ cb = lv.cb[l];
     const int ct_n = (K + 31) >> 5;
+    if (DBUF) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's copy of level l has landed
     __syncthreads();   // the previous level's images fully consumed
-    for (int f = tid; f < 2 * K; f += NT) {   // 16 features of one code -> the four bf16 slots of step t
-      const int c = f >> 1, t = f & 1;
-      float x[16];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(cb + (int64_t)c * EP + 16 * t + 4 * q);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) x[4 * q + i] = v[i];
+    // DBUF (a packed image and room for two buffers): level l sits in buffer l & 1, copied by LDS-DMA
+    // while level l - 1 was computed -- the wait and the barrier above retired this wave's copy and
+    // every other wave's, and has freed the other buffer for level l + 1's copy, which is
+    // issued here and lands under this level's passes.  Level 0 is copied and waited for first.
+    float* lb = sm;
+    if constexpr (DBUF) {
+      lb = sm + (l & 1) * img_floats;
+      if (l == 0) {
+        filter_stage_dma(img, lb, img_floats, tid);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
       }
-#pragma unroll
-      for (int hh = 0; hh < 2; ++hh) {
-        bf16x8 vh, vl;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          __bf16 a, b;
-          split_bf16(x[(i < 4 ? 2 * i : 8 + 2 * (i - 4)) + hh], a, b);
-          vh[i] = a;
-          vl[i] = b;
-        }
-        *reinterpret_cast<bf16x8*>(bimg + cb_off<EP>(c, 2 * hh + t)) = vh;
-        *reinterpret_cast<bf16x8*>(bimg + cb_off<EP>(c, 4 + 2 * hh + t)) = vl;
-      }
+      if (l + 1 < L) filter_stage_dma(img + (size_t)(l + 1) * img_floats, sm + ((l + 1) & 1) * img_floats, img_floats, tid);
+    } else {
+      filter_stage<LIVE>(cb, K, kch, f32_lds, sm, img ? img + (size_t)l * img_floats : nullptr, img_floats, tid);
     }
-    if (f32_lds) stage_rows<EP, NT, true>(cb, EP, 0, K, fimg, tid);
-    float cmax = 0.f;   // max of the level's norms (a NaN norm is skipped: its code can never win)
-    for (int c = tid; c < (LIVE ? 256 : ct_n * 32); c += NT) {
-      float s = __builtin_inff();   // codes past K can never win
-      if (c < K) {
-        const float* row = cb + (int64_t)c * EP;
-        s = aten_rowsq([&](int f) { return row[f]; }, EP);
-        cmax = fmaxf(cmax, s);
-      }
-      cns[c] = s;
-    }
-    cmax = xmax<32>(xmax<16>(xmax<8>(xmax<4>(xmax<2>(xmax<1>(cmax))))));
-    if (lane == 0) wmax[w] = cmax;
-    __syncthreads();
+    float* bimg = lb;                    // [kch] rows of 8 swizzled 16-byte slots: bf16 hi | lo
+    float* cns = bimg + kch * EP;        // [kch]
+    float* wmax = cns + kch;             // [W] the waves' maxima of the level's norms (+ padding to 16 floats)
+    float* fimg = wmax + 16;             // [kch][EP] the exact kernel's fp32 image (f32_lds)
+    float cmax = 0.f;
+    if (!DBUF) __syncthreads();
 #pragma unroll
     for (int i = 0; i < W; ++i) cmax = fmaxf(cmax, wmax[i]);
 
@@ -601,7 +696,7 @@ __global__ __launch_bounds__(RQ_W * 64) void rq_filter_kernel(
       merge_min<false>(best[i], sec, bi[i], __shfl_xor(best[i], 32), 0.f, __shfl_xor(bi[i], 32));
       int b = bi[i];
       if (b >= K || b < 0) b = 0;   // no finite distance (NaN/inf input): torch.argmin -> 0
-      const int64_t item = (int64_t)(t_begin + w + i * W) * 32 + r;
+      const int64_t item = (int64_t)tile_at(i) * 32 + r;
       if (h == 0 && item < n) idx_out[item * L + l] = (int64_t)b;
       if (GR_FDIAG == 3) {
         const uint32_t tot = ncand[i] + __shfl_xor(ncand[i], 32);
@@ -717,6 +812,29 @@ __global__ __launch_bounds__(RQ_W * 64) void rq_filter_kernel(
   }
 }
 
+// The images filter_stage copies from, level l at out + l * img_floats: one workgroup per level runs
+// the kernel's own staging into LDS (rows past K zeroed first), folds the waves' maxima of the norms
+// into every wmax slot, and copies the LDS bytes out.
+template <bool LIVE>
+__global__ __launch_bounds__(RQ_W * 64) void rq_cb_pack_kernel(RQLevels lv, int kch, int f32_lds,
+                                                              float* __restrict__ out, int img_floats) {
+  constexpr int W = RQ_W, NT = W * 64;
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int tid = threadIdx.x, l = blockIdx.x;
+  for (int f = tid; f < img_floats; f += NT) sm[f] = 0.f;
+  __syncthreads();
+  filter_stage<LIVE>(lv.cb[l], lv.K[l], kch, f32_lds, sm, nullptr, 0, tid);
+  __syncthreads();
+  float* wmax = sm + kch * 32 + kch;
+  float cmax = 0.f;
+#pragma unroll
+  for (int i = 0; i < W; ++i) cmax = fmaxf(cmax, wmax[i]);
+  __syncthreads();
+  if (tid < 16) wmax[tid] = tid < W ? cmax : 0.f;
+  __syncthreads();
+  for (int f = tid; f < img_floats; f += NT) out[(size_t)l * img_floats + f] = sm[f];
+}
+
 __global__ __launch_bounds__(256) void rq_code_norms_kernel(const float* __restrict__ cb, int K,
                                                             int e, float* __restrict__ cn) {
   const int c = blockIdx.x * 256 + threadIdx.x;
@@ -777,36 +895,93 @@ static bool filter_ok(int e, int L, const RQLevels& lv, const float* best, const
   return true;
 }
 
-static int launch_filter(const float* z, int64_t n, int L, const RQLevels& lv, int64_t* idx, hipStream_t st) {
+// The grid of a filtered call of `tiles` tiles whose last `left` are pending leftover tiles: grid_in
+// workgroups, more only while a workgroup would exceed the register-resident residuals (RQ_W x
+// GR_FMAXT tiles) under rq_filter_range.  0: no such grid.
+static int64_t filter_grid(int64_t tiles, int64_t grid_in, int left) {
+  const int cap = RQ_W * GR_FMAXT;
+  int64_t grid = grid_in;
+  const int64_t min_grid = (tiles + cap - 1) / cap;
+  if (grid < min_grid) grid = min_grid;
+  if (grid < left || left > tiles || tiles > 0x7fffffffLL) return 0;
+  while (grid <= 0x7fffffffLL && rq_filter_max_count((int)tiles, (int)grid, left) > cap) ++grid;
+  return grid > 0x7fffffffLL ? 0 : grid;
+}
+
+// The filtered kernel's form for a set of levels: LIVE (every K <= 256: the kernel sweeps 256 rows at
+// every level), the rows of its LDS images, whether the fp32 image is among them.
+struct FilterShape {
+  bool live;
+  int kch, f32_lds;
+  size_t floats;   // filter_lds_floats: one level's images
+};
+static FilterShape filter_shape(int L, const RQLevels& lv) {
   int kmax = 0;
   for (int l = 0; l < L; ++l) kmax = lv.K[l] > kmax ? lv.K[l] : kmax;
-  const bool live = GR_FLIVE && kmax <= 256;   // the kernel then sweeps 256 rows at every level
-  const int kch = live ? 256 : (kmax + 31) & ~31;
-  const int f32_lds = kch <= RQF_F32_KMAX;
-  const size_t lds = (size_t)kch * 32 * 4 * (f32_lds ? 2 : 1) + (size_t)kch * 4 + 16 * 4;
+  FilterShape s;
+  s.live = GR_FLIVE && kmax <= 256;
+  s.kch = s.live ? 256 : (kmax + 31) & ~31;
+  s.f32_lds = s.kch <= RQF_F32_KMAX;
+  s.floats = filter_lds_floats(s.kch, s.f32_lds);
+  return s;
+}
+
+// tail: the fused encoder's pending leftover tiles (null or tail->h1g null: none); z is then tail->z.
+// img: the levels' packed images (launch_cb_pack), or null: the kernel derives them from the codebooks.
+static int launch_filter(const float* z, int64_t n, int L, const RQLevels& lv, int64_t* idx, hipStream_t st,
+                         const RqPending* tail = nullptr, const float* img = nullptr) {
+  const FilterShape fs = filter_shape(L, lv);
+  const bool live = fs.live;
+  const int kch = fs.kch, f32_lds = fs.f32_lds;
+  size_t lds = fs.floats * sizeof(float);
+  const bool merged = tail && tail->h1g;
+  // a packed image at K <= 256 (two buffers of 66 KiB) is double-buffered by LDS-DMA
+  const bool dbuf = GR_FDMA && live && img && L > 1 && 2 * lds <= 160 * 1024;
+  if (dbuf) lds *= 2;
+  // the prologue's images alias the codebook images: the larger of the two sizes
+  if (merged && lds < FusedCfg<256, 128>::TAIL_LDS * sizeof(float)) lds = FusedCfg<256, 128>::TAIL_LDS * sizeof(float);
   const int64_t tiles = (n + 31) / 32;
   // persistent, as launch_quantize_e: one workgroup per CU, more only when a range would exceed
   // the register-resident residuals
   int64_t grid = (int64_t)cu_count();
-  const int64_t min_grid = (tiles + RQ_W * GR_FMAXT - 1) / (RQ_W * GR_FMAXT);
-  if (grid < min_grid) grid = min_grid;
   if (grid > tiles) grid = tiles;
-  if (grid > 0x7fffffffLL || tiles > 0x7fffffffLL) return fail(GR_ERR_UNSUPPORTED, "rq quantize: n too large");
-  auto k = live ? rq_filter_kernel<true> : rq_filter_kernel<false>;
+  grid = filter_grid(tiles, grid, merged ? tail->left : 0);
+  // a merged call that fails here has not finished its leftover tiles: their z was never written
+  if (grid == 0)
+    return fail(GR_ERR_UNSUPPORTED, merged ? "rq encode: n too large (the pending leftover tiles were not finished)"
+                                           : "rq quantize: n too large");
+  auto k = merged ? (live ? rq_filter_kernel<true, true, false> : rq_filter_kernel<false, true, false>)
+                  : (live ? rq_filter_kernel<true, false, false> : rq_filter_kernel<false, false, false>);
+#if GR_FDMA
+  if (dbuf) k = merged ? rq_filter_kernel<true, true, true> : rq_filter_kernel<true, false, true>;
+#endif
   if (lds > 64 * 1024 &&
       hipFuncSetAttribute(reinterpret_cast<const void*>(k),
                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return fail(GR_ERR_HIP, "rq quantize: cannot raise the LDS limit");
+    return fail(GR_ERR_HIP, merged ? "rq encode: cannot raise the LDS limit (the pending leftover tiles were not finished)"
+                                   : "rq quantize: cannot raise the LDS limit");
   hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(RQ_W * 64), lds, st, z, n, L, lv, kch, f32_lds,
-                     idx, (int)tiles, g_filter_counts.load());
+                     idx, (int)tiles, g_filter_counts.load(), merged ? *tail : RqPending{}, img, (int)fs.floats);
   g_filter_launches.fetch_add(1);
   return check_launch("gr_rq_quantize_f32");
 }
 
+// The packed images of L levels (filter_stage's second source) into `out`, L x filter_shape().floats.
+static int launch_cb_pack(int L, const RQLevels& lv, float* out, hipStream_t st) {
+  const FilterShape fs = filter_shape(L, lv);
+  auto k = fs.live ? rq_cb_pack_kernel<true> : rq_cb_pack_kernel<false>;
+  const size_t lds = fs.floats * sizeof(float);
+  if (lds > 64 * 1024 &&
+      hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    return fail(GR_ERR_HIP, "rq codebook pack: cannot raise the LDS limit");
+  hipLaunchKernelGGL(k, dim3((unsigned)L), dim3(RQ_W * 64), lds, st, lv, fs.kch, fs.f32_lds, out, (int)fs.floats);
+  return check_launch("gr_rq_codebook_pack_f32");
+}
+
 static int launch_quantize(const float* z, int64_t n, int e, int L, const RQLevels& lv,
-                           int64_t* idx, float* best, float* gap, hipStream_t st) {
+                           int64_t* idx, float* best, float* gap, hipStream_t st, const float* img = nullptr) {
   if (n == 0) return GR_OK;
-  if (filter_ok(e, L, lv, best, gap)) return launch_filter(z, n, L, lv, idx, st);
+  if (filter_ok(e, L, lv, best, gap)) return launch_filter(z, n, L, lv, idx, st, nullptr, img);
   if (e <= 16) return launch_quantize_e<16>(z, n, e, L, lv, idx, best, gap, st);
   if (e <= 32) return launch_quantize_e<32>(z, n, e, L, lv, idx, best, gap, st);
   if (e <= 64) return launch_quantize_e<64>(z, n, e, L, lv, idx, best, gap, st);
@@ -855,6 +1030,23 @@ extern "C" int32_t gr_mkl_plan(int64_t M, int32_t K, int32_t N, int32_t* kind, i
 extern "C" float gr_rq_filter_bound_f32(float rn, float cmax2) { return gr::rq_filter_bound(rn, cmax2); }
 
 extern "C" int64_t gr_rq_filter_launches(void) { return gr::g_filter_launches.load(); }
+
+extern "C" int gr_rq_filter_plan(int64_t tiles, int32_t grid_in, int32_t left, int32_t* begins_out,
+                                 int32_t* counts_out, int32_t* grid_out) {
+  using namespace gr;
+  clear_error();
+  if (tiles < 1 || grid_in < 1 || left < 0 || !grid_out) return fail(GR_ERR_ARG, "gr_rq_filter_plan: bad arguments");
+  const int64_t grid = filter_grid(tiles, grid_in, left);
+  if (grid == 0) return fail(GR_ERR_UNSUPPORTED, "gr_rq_filter_plan: left > grid or tiles, or too many tiles");
+  *grid_out = (int32_t)grid;
+  for (int b = 0; b < (int)grid && (begins_out || counts_out); ++b) {
+    int mb, me;
+    rq_filter_range((int)tiles, (int)grid, left, b, mb, me);
+    if (begins_out) begins_out[b] = mb;
+    if (counts_out) counts_out[b] = me - mb + (b < left ? 1 : 0);
+  }
+  return GR_OK;
+}
 
 extern "C" void gr_rq_filter_diag_counts(uint32_t* counts) { gr::g_filter_counts.store(counts); }
 
@@ -909,7 +1101,8 @@ static size_t mlp_ws_bytes(int64_t n, int32_t n_linear, const int32_t* dims) {
 static int mlp_exact(const float* x, int64_t n, int32_t n_linear, const int32_t* dims, const float* const* weights,
                      const float* const* biases, const float* const* bn_mean, const float* const* bn_var,
                      const float* const* bn_w, const float* const* bn_b, float bn_eps, int32_t act, float* z_out,
-                     void* workspace, hipStream_t st, const float* packed = nullptr) {
+                     void* workspace, hipStream_t st, const float* packed = nullptr,
+                     gr::RqPending* pending = nullptr) {
   using namespace gr;
   if (!mlp_chain(n, n_linear, dims))   // the reference's 1-15-row calls (or in_features % 4 != 0)
     return gr_rq_rows_launch(x, n, n, nullptr, 0, n_linear, dims, weights, biases, bn_mean, bn_var, bn_w, bn_b,
@@ -920,7 +1113,7 @@ static int mlp_exact(const float* x, int64_t n, int32_t n_linear, const int32_t*
   if (!bn_mean && act == GR_ACT_RELU && option("rq_fused") == 1) {
     const int rc = gr_rq_encoder_fused_launch(x, n, n_linear, dims, weights, biases, z_out,
                                               packed ? const_cast<float*>(packed) : reinterpret_cast<float*>(ws + 2 * ab),
-                                              st, packed != nullptr, buf[0]);
+                                              st, packed != nullptr, buf[0], pending);
     if (rc != GR_ERR_UNSUPPORTED) return rc;
     clear_error();
   }
@@ -960,18 +1153,57 @@ extern "C" int gr_rq_encoder_pack_f32(int32_t n_linear, const int32_t* dims, con
   return rc;
 }
 
+extern "C" size_t gr_rq_codebook_image_floats(int32_t e, int32_t L, const int32_t* K) {
+  using namespace gr;
+  if (e != 32 || L < 1 || L > GR_MAX_LEVELS || !K) return 0;
+  RQLevels lv{};
+  for (int l = 0; l < L; ++l) {
+    if (K[l] < 1 || K[l] > RQF_KMAX) return 0;
+    lv.K[l] = K[l];
+  }
+  return (size_t)L * filter_shape(L, lv).floats;
+}
+
+extern "C" int gr_rq_codebook_pack_f32(int32_t e, int32_t L, const int32_t* K, const float* const* codebooks,
+                                       float* image, void* stream) {
+  using namespace gr;
+  clear_error();
+  int rc = check_levels(e, L, K, codebooks);
+  if (rc) return rc;
+  if (gr_rq_codebook_image_floats(e, L, K) == 0)
+    return fail(GR_ERR_UNSUPPORTED, "gr_rq_codebook_pack_f32: the filtered quantizer takes e_dim 32 and K <= 1024");
+  if (!image || !aligned16(image)) return fail(GR_ERR_ARG, "gr_rq_codebook_pack_f32: image null or not 16-byte aligned");
+  RQLevels lv{};
+  for (int l = 0; l < L; ++l) {
+    lv.cb[l] = codebooks[l];
+    lv.K[l] = K[l];
+  }
+  return launch_cb_pack(L, lv, image, reinterpret_cast<hipStream_t>(stream));
+}
+
 extern "C" int gr_rq_encode_packed_f32(const float* x, int64_t n, int32_t n_linear, const int32_t* dims,
                                        const float* const* weights, const float* const* biases,
                                        const float* packed, int32_t L, const int32_t* K,
                                        const float* const* codebooks, int64_t* idx_out, float* best_out,
                                        float* gap_out, float* z_out, void* workspace, size_t workspace_bytes,
                                        void* stream) {
+  return gr_rq_encode_image_f32(x, n, n_linear, dims, weights, biases, packed, L, K, codebooks, nullptr, idx_out,
+                                best_out, gap_out, z_out, workspace, workspace_bytes, stream);
+}
+
+extern "C" int gr_rq_encode_image_f32(const float* x, int64_t n, int32_t n_linear, const int32_t* dims,
+                                      const float* const* weights, const float* const* biases,
+                                      const float* packed, int32_t L, const int32_t* K,
+                                      const float* const* codebooks, const float* cb_image, int64_t* idx_out,
+                                      float* best_out, float* gap_out, float* z_out, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
   using namespace gr;
   clear_error();
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (n_linear < 1 || n_linear > GR_MAX_LINEAR || !dims || !weights)
     return fail(GR_ERR_ARG, "gr_rq_encode_f32: bad encoder description");
   if (packed && !aligned16(packed)) return fail(GR_ERR_ARG, "gr_rq_encode_packed_f32: packed not 16-byte aligned");
+  if (cb_image && !aligned16(cb_image)) return fail(GR_ERR_ARG, "gr_rq_encode_image_f32: cb_image not 16-byte aligned");
   const int e = dims[n_linear];
   int rc = check_levels(e, L, K, codebooks);
   if (rc) return rc;
@@ -1008,10 +1240,16 @@ extern "C" int gr_rq_encode_packed_f32(const float* x, int64_t n, int32_t n_line
     lv.cb[l] = codebooks[l];
     lv.K[l] = K[l];
   }
+  // The fused encoder's leftover tiles finish in the filtered quantizer's launch ("rq_tail_merge"):
+  // the encoder hands their layers 2-3 back instead of launching rq_leftover_kernel.
+  RqPending pend{};
+  const bool merge = option("rq_tail_merge") == 1 && filter_ok(e, L, lv, best_out, gap_out);
   rc = mlp_exact(x, n, n_linear, dims, weights, biases, nullptr, nullptr, nullptr, nullptr, 0.f, GR_ACT_RELU,
-                 zb, workspace, st, packed);
+                 zb, workspace, st, packed, merge ? &pend : nullptr);
   if (rc) return rc;
-  return launch_quantize(zb, n, e, L, lv, idx_out, best_out, gap_out, st);
+  // cb_image serves the filtered kernel alone; a call it does not take reads the codebooks
+  if (pend.h1g) return launch_filter(zb, n, L, lv, idx_out, st, &pend, cb_image);
+  return launch_quantize(zb, n, e, L, lv, idx_out, best_out, gap_out, st, cb_image);
 }
 
 extern "C" int gr_rq_encode_f32(const float* x, int64_t n, int32_t n_linear, const int32_t* dims,

@@ -325,6 +325,10 @@ class RqBinding:
         nf = L.lib().gr_rq_encoder_pack_floats(len(self.ws), self.dims_c)
         self.packed = torch.empty(nf, dtype=torch.float32, device=self.device) if nf else None
         self._pack_key = None
+        # the filtered quantizer's packed codebook image (frozen codebooks only, see cb_image_ptr)
+        nc = L.lib().gr_rq_codebook_image_floats(self.dims[-1], len(self.cbs), self.ks_c)
+        self.cb_image = torch.empty(nc, dtype=torch.float32, device=self.device) if nc else None
+        self._cb_key = None
 
     # Re-use one packed encoder image across calls, re-packed whenever a weight's version counter
     # (load_state_dict, optimizer steps, any in-place op) or the graph-replay epoch moves (a
@@ -339,38 +343,61 @@ class RqBinding:
         (``frozen = False``, or not the fused encoder shape)."""
         if self.packed is None or not self.frozen:
             return None
-        key = tuple(w._version for w in self.ws) + (_WEIGHT_EPOCH[0],)
+
+        def pack(image):
+            L.check(L.lib().gr_rq_encoder_pack_f32(len(self.ws), self.dims_c, self.w_arr, L.ptr(image),
+                                                   L.stream_of(self.device)), "gr_rq_encoder_pack_f32")
+        return self._image_ptr("packed", "_pack_key", "_streams", self.ws, pack, "packed encoder image")
+
+    def cb_image_ptr(self):
+        """Device pointer of the up-to-date packed codebook image (the filtered quantizer's per-level
+        LDS images, ``gr_rq_codebook_pack_f32``), cached like the encoder image under the codebooks'
+        version counters and the graph-replay epoch; None: the kernel derives the images from the
+        codebooks on every call (``frozen = False``, or codebooks the filtered quantizer does not take)."""
+        if self.cb_image is None or not self.frozen:
+            return None
+
+        def pack(image):
+            L.check(L.lib().gr_rq_codebook_pack_f32(self.dims[-1], len(self.cbs), self.ks_c, self.c_arr, L.ptr(image),
+                                                    L.stream_of(self.device)), "gr_rq_codebook_pack_f32")
+        return self._image_ptr("cb_image", "_cb_key", "_cb_streams", self.cbs, pack, "packed codebook image")
+
+    def _image_ptr(self, attr, key_attr, streams_attr, params, pack, what):
+        """The cached image ``attr`` of ``params``, re-packed into a fresh tensor when its key moved."""
+        image = getattr(self, attr)
+        key = tuple(w._version for w in params) + (_WEIGHT_EPOCH[0],)
         capturing = torch.cuda.is_current_stream_capturing()
-        if key != self._pack_key and capturing:
+        if key != getattr(self, key_attr) and capturing:
             # a pack recorded into a graph would run only at replay, leaving the eager image stale
-            raise RuntimeError("rq_encode: the packed encoder image is out of date inside a graph capture; "
+            raise RuntimeError(f"rq_encode: the {what} is out of date inside a graph capture; "
                                "run one eager get_indices after the last weight change, then capture "
                                "(graphs that encode must be re-captured after weight changes)")
         if capturing:
             # a captured graph bakes in this image's pointer: keep the image alive for the binding's
             # lifetime, so replays after a later re-pack read the old weights, never freed memory
             refs = self.__dict__.setdefault("_graph_images", [])
-            if not any(r is self.packed for r in refs):
-                refs.append(self.packed)
-        if key != self._pack_key:
-            if self._pack_key is not None:
+            if not any(r is image for r in refs):
+                refs.append(image)
+        if key != getattr(self, key_attr):
+            if getattr(self, key_attr) is not None:
                 # a re-pack writes a fresh image on this stream; the previous one goes back to the
                 # caching allocator, which does not hand it out again before the work of every
                 # stream recorded on it (below) has finished
-                self.packed = torch.empty_like(self.packed)
-                self._streams = set()
+                image = torch.empty_like(image)
+                setattr(self, attr, image)
+                setattr(self, streams_attr, set())
             with L.on(self.device):
-                L.check(L.lib().gr_rq_encoder_pack_f32(len(self.ws), self.dims_c, self.w_arr, L.ptr(self.packed),
-                                                       L.stream_of(self.device)), "gr_rq_encoder_pack_f32")
-            self._pack_key = key
+                pack(image)
+            setattr(self, key_attr, key)
         st = L.stream_of(self.device)
-        streams = getattr(self, "_streams", None)
+        streams = getattr(self, streams_attr, None)
         if streams is None:
-            streams = self._streams = set()
+            streams = set()
+            setattr(self, streams_attr, streams)
         if st not in streams:   # an encode on another stream than the allocating one
-            self.packed.record_stream(torch.cuda.current_stream(self.device))
+            image.record_stream(torch.cuda.current_stream(self.device))
             streams.add(st)
-        return self.packed.data_ptr()
+        return image.data_ptr()
 
     def encode_fast(self, x):
         """rq_encode's common call -- fp32 contiguous [n, in_dim] rows on the binding's (current)
@@ -381,7 +408,7 @@ class RqBinding:
                 or not x.is_contiguous() or x.get_device() != self.dev_index
                 or self.dev_index != torch.cuda.current_device() or torch.cuda.is_current_stream_capturing()):
             return None
-        pk = self.packed_ptr()
+        pk, ci = self.packed_ptr(), self.cb_image_ptr()
         n = x.shape[0]
         st = L.stream_of(self.device)
         nbytes = self._ws_bytes.get(n) or self.workspace_bytes(n)
@@ -389,11 +416,11 @@ class RqBinding:
         if ws is None or ws.numel() < nbytes:
             ws = scratch(nbytes, self.device)
         idx = torch.empty((n, len(self.cbs)), dtype=torch.int64, device=self.device)
-        rc = L.lib().gr_rq_encode_packed_f32(x.data_ptr(), n, self.n_linear, self.dims_c, self.w_arr, self.b_arr,
-                                             pk, len(self.cbs), self.ks_c, self.c_arr, idx.data_ptr(), None, None,
-                                             None, ws.data_ptr(), nbytes, st)
+        rc = L.lib().gr_rq_encode_image_f32(x.data_ptr(), n, self.n_linear, self.dims_c, self.w_arr, self.b_arr,
+                                            pk, len(self.cbs), self.ks_c, self.c_arr, ci, idx.data_ptr(), None, None,
+                                            None, ws.data_ptr(), nbytes, st)
         if rc:
-            L.check(rc, "gr_rq_encode_packed_f32")
+            L.check(rc, "gr_rq_encode_image_f32")
         return idx
 
     def workspace_bytes(self, n):
@@ -470,10 +497,11 @@ def rq_encode(x, weights=None, biases=None, codebooks=None, with_gap=False, with
     best = torch.empty((n, nl), dtype=torch.float32, device=dev) if with_gap else None
     z = torch.empty((n, b.dims[-1]), dtype=torch.float32, device=dev) if with_z else None
     with L.on(dev):
-        L.check(L.lib().gr_rq_encode_packed_f32(x2.data_ptr(), n, b.n_linear, b.dims_c, b.w_arr, b.b_arr,
-                                                b.packed_ptr(), nl, b.ks_c, b.c_arr, idx.data_ptr(), L.ptr(best),
-                                                L.ptr(gap), L.ptr(z), wsp.data_ptr(), nbytes, L.stream_of(dev)),
-                "gr_rq_encode_packed_f32")
+        L.check(L.lib().gr_rq_encode_image_f32(x2.data_ptr(), n, b.n_linear, b.dims_c, b.w_arr, b.b_arr,
+                                               b.packed_ptr(), nl, b.ks_c, b.c_arr, b.cb_image_ptr(), idx.data_ptr(),
+                                               L.ptr(best), L.ptr(gap), L.ptr(z), wsp.data_ptr(), nbytes,
+                                               L.stream_of(dev)),
+                "gr_rq_encode_image_f32")
     out = [idx]
     if with_gap:
         out += [best, gap]

@@ -84,6 +84,11 @@ const char* gr_last_error(void);
  *                   workgroup when n <= 256, n K e <= 2^20 (e padded) and the rows and
  *                   the workspace fit in LDS; 0: always one launch per phase over row tiles.  Both forms
  *                   run the same phase code in the same order: bitwise the same results.
+ *   "rq_tail_merge" 1 (default): an encode call (gr_rq_encode_f32 / gr_rq_encode_packed_f32) that
+ *                   runs the fused encoder with leftover tiles and the filtered quantizer is two
+ *                   launches: the quantizer's workgroups finish the leftover tiles' layers 2-3
+ *                   themselves before they quantize them; 0: rq_leftover_kernel runs between the two
+ *                   (three launches).  z and the IDs are bitwise the same.
  * The final block of a last-position forward (predict, last_hidden; gr_sasrec_plan reports the
  * choice): the H form when the tail kernel takes the shape (d / 4, head width / 4 and mlp / 4 powers
  * of two, at most 8 heads, d and mlp <= 256, 16-byte aligned weights); otherwise the pruned final
@@ -171,6 +176,26 @@ int gr_rq_encode_packed_f32(const float* x, int64_t n, int32_t n_linear, const i
                             float* gap_out, float* z_out, void* workspace, size_t workspace_bytes,
                             void* stream);
 
+/* The filtered quantizer's packed codebook image (e_dim 32, every K <= 1024; 0 floats otherwise): per
+ * level exactly what the kernel's LDS holds after it has staged that level -- the split-bf16 image
+ * (hi = rne(c), lo = rne(c - hi), one swizzled 128-byte row per code), the ATen-order norms (+inf past
+ * K up to the rows the kernel sweeps), the level's largest norm, and the swizzled fp32 image when the
+ * levels have at most 512 codes.  A caller that keeps the codebooks fixed between calls packs once
+ * (gr_rq_codebook_pack_f32, `image` 16-byte aligned, gr_rq_codebook_image_floats floats) and passes
+ * the image to gr_rq_encode_image_f32 (gr_rq_encode_packed_f32's arguments plus cb_image): the kernel
+ * then stages a level by a straight copy.  cb_image = NULL, and every call the filtered kernel does not
+ * take: the images are derived from `codebooks` in-kernel.  The image must have been packed from the
+ * same K and the codebooks' current values; the IDs are bitwise the same either way. */
+size_t gr_rq_codebook_image_floats(int32_t e, int32_t L, const int32_t* K);
+int gr_rq_codebook_pack_f32(int32_t e, int32_t L, const int32_t* K, const float* const* codebooks,
+                            float* image, void* stream);
+int gr_rq_encode_image_f32(const float* x, int64_t n, int32_t n_linear, const int32_t* dims,
+                           const float* const* weights, const float* const* biases,
+                           const float* packed, int32_t L, const int32_t* K,
+                           const float* const* codebooks, const float* cb_image, int64_t* idx_out,
+                           float* best_out, float* gap_out, float* z_out, void* workspace,
+                           size_t workspace_bytes, void* stream);
+
 /* MLPLayers.forward in eval mode (RQ-VAE/models/layers.py:42-43): z_out[n, dims[n_linear]] = the
  * encoder output alone (ReLU after every Linear but the last).  Same kernels as gr_rq_encode_f32. */
 size_t gr_rq_mlp_workspace_bytes(int64_t n, int32_t n_linear, const int32_t* dims);
@@ -217,10 +242,21 @@ int32_t gr_mkl_plan(int64_t M, int32_t K, int32_t N, int32_t* kind, int32_t* kb)
  * a_k = |c_k|^2 - 2 r.c_k is within E of the exact kernel's distance minus |r|^2, and every code with
  * a_k <= min a + 2E is re-scored exactly.  gr_rq_filter_launches: launches of the filtered kernel by
  * this process so far.  gr_rq_filter_diag_counts: a device buffer [n][L] (uint32) that diagnostic
- * builds (-DGR_FDIAG=3) fill with the number of codes re-scored per item and level; NULL: none. */
+ * builds (-DGR_FDIAG=3) fill with the number of codes re-scored per item and level; NULL: none.
+ * gr_rq_leftover_launches: launches of rq_leftover_kernel (the fused encoder's leftover tiles as a
+ * launch of their own: every caller but the merged encode path of "rq_tail_merge") so far.
+ * gr_rq_filter_plan: the filtered kernel's tile plan (host arithmetic, no device) for `tiles` 32-item
+ * tiles whose last `left` are pending leftover tiles, from grid_in workgroups: *grid_out workgroups
+ * (grid_in, or more while one would exceed its 16 register-resident tiles), workgroup b taking main
+ * tiles [begins_out[b], begins_out[b] + counts_out[b] - (b < left)) plus, when b < left, leftover
+ * tile tiles - left + b, counts_out[b] tiles in all.  begins_out / counts_out: *grid_out entries
+ * (at most max(grid_in, tiles)), or NULL.  GR_ERR_UNSUPPORTED when left exceeds the grid or tiles. */
 float gr_rq_filter_bound_f32(float rn, float cmax2);
 int64_t gr_rq_filter_launches(void);
 void gr_rq_filter_diag_counts(uint32_t* counts);
+int64_t gr_rq_leftover_launches(void);
+int gr_rq_filter_plan(int64_t tiles, int32_t grid_in, int32_t left, int32_t* begins_out, int32_t* counts_out,
+                      int32_t* grid_out);
 
 /* MLPLayers.forward in train mode (RQ-VAE/models/layers.py:18-43, [Dropout -> Linear -> ReLU] x
  * (n_linear - 1), then Dropout -> Linear; RQVAE.forward under RQ-VAE/train.py:113).  Dropout p_drop
