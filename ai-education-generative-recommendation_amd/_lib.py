@@ -69,6 +69,18 @@ class TigerPrefixParams(ctypes.Structure):
                [("eps", _f32), ("reserved_f", _f32), ("adapter", (_vp * 14) * 3)]
 
 
+GR_T5E_MAX_LAYERS = 8
+
+
+class T5EmbedParams(ctypes.Structure):
+    """Mirror of ``gr_t5_embed_params`` (include/gr_amd.h)."""
+    _fields_ = [(f, _i32) for f in ("d_model", "d_kv", "n_heads", "d_ff", "n_layers", "in_dim", "out_dim",
+                                    "n_buckets")] + \
+               [("eps", _f32), ("reserved", _f32)] + \
+               [(f, _vp) for f in ("in_w", "in_b", "out_w", "out_b", "rel", "bucket", "final_ln")] + \
+               [("layer", (_vp * 8) * GR_T5E_MAX_LAYERS)]
+
+
 # (name, restype, argtypes) for every entry point of include/gr_amd.h
 SIGNATURES = {
     "gr_version": (ctypes.c_char_p, []),
@@ -173,6 +185,8 @@ SIGNATURES = {
                                                     _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp,
                                                     _vp, _vp, _vp, _sz, _vp]),
     "gr_beam_hits_i64": (ctypes.c_int, [_vp, _i64, _i32, _i32, _i64, _vp, _i32, _vp, _vp]),
+    "gr_t5_embed_workspace_bytes": (_sz, [ctypes.POINTER(T5EmbedParams), _i64, _i32]),
+    "gr_t5_embed_f32": (ctypes.c_int, [ctypes.POINTER(T5EmbedParams), _vp, _vp, _i64, _i32, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -1894,3 +1894,114 @@ def beam_hits(preds, labels, skip=0):
         L.check(L.lib().gr_beam_hits_i64(preds.data_ptr() + 8 * skip, B, k, T - skip, T, L.ptr(labels),
                                          labels.shape[1], L.ptr(hits), L.stream_of(preds.device)), "gr_beam_hits_i64")
     return hits.view(torch.bool)
+
+
+T5E_LAYER_KEYS = TIGER_ENC_KEYS
+T5E_ENVELOPE = ("d_model a multiple of 32 in [32, 512]; d_kv in {8, 16, 32, 64} with num_heads * d_kv <= 256; d_ff a "
+                "multiple of 32 in [32, 1024]; input and target widths multiples of 4 in [4, 1024]; 1..8 blocks; "
+                "32 relative-attention buckets; 1..32 positions; at most 2^20 users per call")
+
+
+def t5_embed_check(cfg, S=None, B=None):
+    """Raise NotImplementedError, naming the limit, for what gr_t5_embed_f32 does not cover.  ``cfg``: d_model,
+    d_kv, num_heads, d_ff, num_layers, input_emb_dim, target_emb_dim (the widths of gr_t5_embed_params)."""
+    def no(msg):
+        raise NotImplementedError(f"T5 embedding retriever: {msg} (the gfx950 kernels cover: {T5E_ENVELOPE}); there is "
+                                  "no CPU fallback")
+    d, dkv, H, dff, nl, din, dout = (int(cfg[k]) for k in ("d_model", "d_kv", "num_heads", "d_ff", "num_layers",
+                                                           "input_emb_dim", "target_emb_dim"))
+    if cfg.get("feed_forward_proj", "relu") != "relu":
+        no(f"feed_forward_proj={cfg['feed_forward_proj']!r} is not built, only 'relu'")
+    if d < 32 or d > 512 or d % 32:
+        no(f"d_model={d} must be a multiple of 32 in [32, 512]")
+    if dkv not in (8, 16, 32, 64):
+        no(f"d_kv={dkv} must be 8, 16, 32 or 64")
+    if H < 1 or H * dkv > 256:
+        no(f"num_heads * d_kv = {H * dkv} must be at most 256")
+    if dff < 32 or dff > 1024 or dff % 32:
+        no(f"d_ff={dff} must be a multiple of 32 in [32, 1024]")
+    for name, v in (("input_emb_dim", din), ("target_emb_dim", dout)):
+        if v < 4 or v > 1024 or v % 4:
+            no(f"{name}={v} must be a multiple of 4 in [4, 1024]")
+    if not 1 <= nl <= L.GR_T5E_MAX_LAYERS:
+        no(f"num_layers={nl} must be 1..{L.GR_T5E_MAX_LAYERS}")
+    if S is not None and not 1 <= S <= 32:
+        no(f"a sequence of {S} positions; 1..32 are supported")
+    if B is not None and B > (1 << 20):
+        no(f"a batch of {B} users; at most 2^20 per call")
+
+
+class T5EmbedBinding:
+    """Device-pointer view of the retriever's parameters (``gr_t5_embed_params``).  ``tensors``: name -> tensor
+    with the reference's names below ``TIGER`` (``input_proj.weight``, ``output_proj.bias``,
+    ``model.encoder.block.0.layer.0.SelfAttention.q.weight``, ...).  The pointers are the tensors' own
+    storage, so in-place weight updates are seen by the next call."""
+
+    def __init__(self, cfg, tensors):
+        t5_embed_check(cfg)
+        self.cfg = cfg
+        self.keep = []
+        dev = tensors["input_proj.weight"].device
+        self.device = dev
+        p = L.T5EmbedParams()
+        p.d_model, p.d_kv, p.n_heads, p.d_ff = (int(cfg[k]) for k in ("d_model", "d_kv", "num_heads", "d_ff"))
+        p.n_layers, p.in_dim, p.out_dim = int(cfg["num_layers"]), int(cfg["input_emb_dim"]), int(cfg["target_emb_dim"])
+        p.n_buckets = 32
+        p.eps = float(cfg.get("layer_norm_epsilon", 1e-6))
+        f = self._f
+        p.in_w, p.in_b = f(tensors["input_proj.weight"]), f(tensors["input_proj.bias"])
+        p.out_w, p.out_b = f(tensors["output_proj.weight"]), f(tensors["output_proj.bias"])
+        p.rel = f(tensors[f"model.encoder.block.0.{TIGER_REL}.weight"])
+        p.final_ln = f(tensors["model.encoder.final_layer_norm.weight"])
+        for l in range(p.n_layers):
+            for i, k in enumerate(T5E_LAYER_KEYS):
+                p.layer[l][i] = f(tensors[f"model.encoder.block.{l}.{k}.weight"])
+        self.bucket = t5_relative_bucket(torch.arange(-127, 128), True).to(torch.int32).to(dev)
+        p.bucket = self.bucket.data_ptr()
+        self.params = p
+        self.ref = ctypes.byref(p)
+        self._ws = {}
+
+    def _f(self, t):
+        L.require_gpu(t)
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise TypeError("the T5 embedding kernels take contiguous float32 parameters")
+        self.keep.append(t)
+        return t.data_ptr()
+
+    def workspace_bytes(self, B, S):
+        n = self._ws.get((B, S))
+        if n is None:
+            n = self._ws[(B, S)] = L.lib().gr_t5_embed_workspace_bytes(self.ref, B, S)
+        return n
+
+
+def t5_embed(binding, seq_embs, attention_mask=None, with_hidden=False):
+    """``gr_t5_embed_f32``: input_proj, the T5 encoder stack, masked mean pooling, output_proj and the L2
+    normalisation in one C call, nothing synchronises.  seq_embs [B, S, in_dim] fp32, attention_mask [B, S]
+    (0 = not a key, not pooled; None: all live) -> pred [B, out_dim] unit rows[, hidden [B, S, d_model]: the
+    final-norm states, unspecified where the mask is 0]."""
+    L.require_gpu(seq_embs)
+    p = binding.params
+    if seq_embs.dim() != 3 or seq_embs.shape[-1] != p.in_dim:
+        raise RuntimeError(f"t5_embed takes [B, S, {p.in_dim}] vectors, got {tuple(seq_embs.shape)}")
+    seq_embs = L.as_f32(seq_embs)
+    B, S, _ = seq_embs.shape
+    t5_embed_check(binding.cfg, S, B)
+    if attention_mask is not None:
+        L.require_gpu(attention_mask)
+        if tuple(attention_mask.shape) != (B, S):
+            raise RuntimeError(f"attention_mask must be [{B}, {S}], got {tuple(attention_mask.shape)}")
+        if attention_mask.dtype != torch.int64:
+            attention_mask = attention_mask.to(torch.int64)
+        attention_mask = attention_mask.contiguous()
+    dev = seq_embs.device
+    pred = torch.empty((B, p.out_dim), dtype=torch.float32, device=dev)
+    hidden = torch.empty((B, S, p.d_model), dtype=torch.float32, device=dev) if with_hidden else None
+    if B > 0:
+        nbytes = binding.workspace_bytes(B, S)
+        wsp = L.workspace(nbytes, dev)
+        with L.on(dev):
+            L.check(L.lib().gr_t5_embed_f32(binding.ref, L.ptr(seq_embs), L.ptr(attention_mask), B, S, L.ptr(pred),
+                                            L.ptr(hidden), L.ptr(wsp), nbytes, L.stream_of(dev)), "gr_t5_embed_f32")
+    return (pred, hidden) if with_hidden else pred

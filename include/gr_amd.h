@@ -773,6 +773,59 @@ int gr_tiger_generate_prefix_f32(const gr_tiger_params* p, const gr_tiger_prefix
 int gr_beam_hits_i64(const int64_t* preds, int64_t B, int32_t k, int32_t pred_len, int64_t ld_pred,
                      const int64_t* labels, int32_t label_len, uint8_t* hits, void* stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* T5 embedding retriever (T5/model.py:46-65 TIGER.forward: input_proj, an eval-mode bidirectional
+ * T5 encoder stack on inputs_embeds, masked mean pooling, output_proj, L2 normalisation).
+ *
+ * gr_t5_embed_params: dimensions and device pointers (fp32, row-major [out, in], 16-byte aligned).
+ * in_w [d_model, in_dim], in_b [d_model]; out_w [out_dim, d_model], out_b [out_dim]; rel [n_buckets,
+ * n_heads]: block 0's relative_attention_bias, used by every block; bucket[255]: the bucket of key -
+ * query distance r at index r + 127 (bidirectional, device int32; gr_tiger_params' enc_bucket);
+ * final_ln [d_model]; layer[l] = {layer.0.layer_norm, q, k, v, o, layer.1.layer_norm, wi, wo}.
+ *
+ * Math (all fp32, softmax in fp32, no 1/sqrt(d_kv) scale, no embedding scale):
+ *   x = seq_embs . in_w^T + in_b
+ *   per block: x += o(softmax(q k^T + bias + mask) v) on RMSNorm(x); x += wo(relu(wi(RMSNorm(x))))
+ *   RMSNorm(x) = w * (x * rsqrt(mean(x^2) + eps)); bias[h, i, j] = rel[bucket(j - i), h] on the
+ *   original positions; key j is removed wherever attention_mask[b, j] == 0 (any other value: live)
+ *   hidden = RMSNorm_final(x); pooled = sum_j live hidden / max(count live, 1e-9)
+ *   pred = pooled . out_w^T + out_b; pred_out = pred / max(|pred|_2, 1e-8)
+ * Masks with holes are legal.  Rows with mask 0 are never keys and never pooled, so what seq_embs
+ * holds there (any finite value) does not reach pred_out.  A user with no live position yields
+ * pooled = 0 and pred_out = normalize(out_b); the reference's data never has one (position 0 is the
+ * user vector).  hidden_out (optional): the final-norm hidden states; masked-out rows are unspecified.
+ *
+ * gr_t5_embed_f32 enqueues 1 + 4 n_layers + 3 launches and never synchronises: input_proj; per block
+ * RMSNorm + q/k/v, per-user attention + o + residual, RMSNorm + wi + relu, wo + residual; then final
+ * norm + pooling, output_proj, normalise.  No floating-point atomics: every output element has one
+ * fixed summation order that depends on neither B nor the user's place in the batch, so two calls
+ * give the same bits and a sub-batch gives the bits of the whole batch's rows.
+ *   seq_embs[B, S, in_dim] fp32 16-byte aligned; attention_mask[B, S] int64 or NULL (all live)
+ *   pred_out[B, out_dim]; hidden_out[B, S, d_model] or NULL
+ * Envelope (GR_ERR_UNSUPPORTED outside, with the field named, before any launch): d_model a multiple
+ * of 32 in [32, 512]; d_kv in {8, 16, 32, 64} with n_heads * d_kv <= 256; d_ff a multiple of 32 in
+ * [32, 1024]; in_dim and out_dim multiples of 4 in [4, 1024]; n_layers 1..8; n_buckets 32; S 1..32;
+ * B 0..2^20 (B = 0: GR_OK, no launch).
+ * workspace: gr_t5_embed_workspace_bytes(p, B, S) bytes, 16-byte aligned (0 outside the envelope). */
+#define GR_T5E_MAX_LAYERS 8
+typedef struct gr_t5_embed_params {
+  int32_t d_model, d_kv, n_heads, d_ff, n_layers, in_dim, out_dim, n_buckets;
+  float eps, reserved;
+  const float* in_w;
+  const float* in_b;
+  const float* out_w;
+  const float* out_b;
+  const float* rel;
+  const int32_t* bucket;
+  const float* final_ln;
+  const float* layer[GR_T5E_MAX_LAYERS][8];
+} gr_t5_embed_params;
+
+size_t gr_t5_embed_workspace_bytes(const gr_t5_embed_params* p, int64_t B, int32_t S);
+int gr_t5_embed_f32(const gr_t5_embed_params* p, const float* seq_embs, const int64_t* attention_mask,
+                    int64_t B, int32_t S, float* pred_out, float* hidden_out, void* workspace,
+                    size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
