@@ -117,3 +117,28 @@ def test_against_the_live_library():
     assert out.sequences.shape[1] == width
     assert torch.equal(s.view(-1, 5)[:, :width], out.sequences)
     assert (c.view(-1) - out.sequences_scores).abs().max() <= 1e-6
+
+
+# The seeded envelope cases (tests/tiger_cases.py) with more than one beam.  Left out: the one-beam cases
+# v2_b1_T2 and b1_T8, because the library switches to greedy decoding at one beam and returns no
+# sequences_scores (the kernel's contract there is the restatement's beam search with k = 1); and nomask,
+# because without a mask the library infers one from the pad ids among the inputs, while the kernels take
+# None as all ones, which is env_max itself.
+@pytest.mark.parametrize("name", ["env_max", "v65_b32", "holes_pad3", "stop_T8"])
+def test_envelope_cases_against_the_live_library(name):
+    transformers = pytest.importorskip("transformers", reason="transformers is not installed")
+    import tiger_cases as tc
+    c = tc.case(name)
+    model = transformers.T5ForConditionalGeneration(transformers.T5Config(
+        decoder_start_token_id=c.cfg["pad_token_id"], **c.cfg)).eval()
+    model.load_state_dict(c.sd)
+    with torch.no_grad():
+        out = model.generate(input_ids=c.ids, attention_mask=c.mask, max_length=c.T, num_beams=c.beams,
+                             num_return_sequences=c.beams, return_dict_in_generate=True, output_scores=True)
+    assert model.config.layer_norm_epsilon == c.cfg["layer_norm_epsilon"]
+    assert getattr(model.config, "scale_decoder_outputs", True) is True
+    s, sc, tr = tc.restated(name, torch.float32)
+    width = out.sequences.shape[1]
+    assert width == c.T                                  # a user that never stops early keeps the library from cropping
+    assert torch.equal(s.view(-1, c.T), out.sequences)
+    assert (sc.view(-1) - out.sequences_scores).abs().max() <= 1e-6
