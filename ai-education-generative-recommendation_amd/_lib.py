@@ -81,6 +81,19 @@ class T5EmbedParams(ctypes.Structure):
                [("layer", (_vp * 8) * GR_T5E_MAX_LAYERS)]
 
 
+GR_BERT_MAX_LAYERS = 24
+GR_BERT_POOL_NONE, GR_BERT_POOL_MEAN_NO_CLS, GR_BERT_POOL_CLS = 0, 1, 2
+
+
+class BertParams(ctypes.Structure):
+    """Mirror of ``gr_bert_params`` (include/gr_amd.h)."""
+    _fields_ = [(f, _i32) for f in ("vocab_size", "hidden_size", "num_heads", "head_dim", "intermediate_size",
+                                    "num_layers", "max_position", "type_vocab_size", "hidden_act", "position_type")] + \
+               [("eps", _f32), ("reserved", _f32)] + \
+               [(f, _vp) for f in ("word", "position", "token_type", "emb_ln_w", "emb_ln_b")] + \
+               [("layer", (_vp * 16) * GR_BERT_MAX_LAYERS)]
+
+
 # (name, restype, argtypes) for every entry point of include/gr_amd.h
 SIGNATURES = {
     "gr_version": (ctypes.c_char_p, []),
@@ -187,6 +200,9 @@ SIGNATURES = {
     "gr_beam_hits_i64": (ctypes.c_int, [_vp, _i64, _i32, _i32, _i64, _vp, _i32, _vp, _vp]),
     "gr_t5_embed_workspace_bytes": (_sz, [ctypes.POINTER(T5EmbedParams), _i64, _i32]),
     "gr_t5_embed_f32": (ctypes.c_int, [ctypes.POINTER(T5EmbedParams), _vp, _vp, _i64, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "gr_bert_embed_workspace_bytes": (_sz, [ctypes.POINTER(BertParams), _i64, _i32]),
+    "gr_bert_embed_f32": (ctypes.c_int, [ctypes.POINTER(BertParams), _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp,
+                                         _sz, _vp]),
 }
 
 _lib = None

@@ -62,12 +62,15 @@ static std::atomic<int64_t> g_rq_tail_merge{1};
 // kmeans_small (1: gr_kmeans_f32 in one launch of one workgroup when the rows fit in LDS, 0: always
 // one launch per phase over row tiles; the same phase code either way)
 static std::atomic<int64_t> g_kmeans_small{1};
+// bert_tile (gr_bert_embed_f32's GEMM tile: 0 = per launch, the tile that leaves the fewest compute units
+// idle; 1 = 128 x 128, 2 = 64 x 128, 3 = 128 x 96 everywhere; the same summation order in each)
+static std::atomic<int64_t> g_bert_tile{0};
 
 static const Opt kOpts[] = {
     {"rq_fused", &g_rq_fused, 0, 1},   {"sas_fused", &g_sas_fused, 0, 3}, {"sas_rowtile", &g_sas_rowtile, 0, 1},
     {"lin_wres", &g_lin_wres, 0, 1},   {"emb_proj", &g_emb_proj, 0, 1},   {"topk_half", &g_topk_half, 0, 2},
     {"attn_k16", &g_attn_k16, 0, 1},   {"rq_filter", &g_rq_filter, 0, 1}, {"kmeans_small", &g_kmeans_small, 0, 1},
-    {"rq_tail_merge", &g_rq_tail_merge, 0, 1},
+    {"rq_tail_merge", &g_rq_tail_merge, 0, 1}, {"bert_tile", &g_bert_tile, 0, 3},
 };
 
 static const Opt* find_opt(const char* name) {

@@ -1,0 +1,536 @@
+// BERT text encoder (transformers' BertModel, eager attention, absolute positions, eval mode) with the
+// reference's two poolings (T5/item_encode.py:11-34,59-78, major-encode/bert_emb.py:131-168) -- gr_bert_embed_f32.
+//
+// bert-base is 340 MB of fp32 weights over up to 512 positions, so every projection is a row-tiled GEMM
+// over all B * S token rows (the weights are read once per call, not once per sequence) and only the
+// attention step runs per sequence.
+//
+//   be_embed_ln_kernel   a wave per token row: (word[id] + token_type[type]) + position[s], LayerNorm.
+//   be_gemm_kernel<WM, TM, TN, EPI>   y = epi(A . W^T + bias) per 256-thread workgroup, K staged 32 deep
+//       through a double-buffered LDS image (t5_embed.hip's staging: rows padded to 36 floats, one float4
+//       per operand per 8-deep slice).  Each wave owns TM x TN blocks of 32 x 32 outputs, one
+//       v_mfma_f32_32x32x2_f32 accumulator chain each: 128 x 128 outputs as 2 x 2 waves of four chains (the
+//       guide's 128 x 128 x 32 block), 64 x 128 as 2 x 2 waves of two, 128 x 96 as 4 x 1 waves of three.
+//       be_gemm picks per launch the tile that leaves the fewest compute units idle (option "bert_tile"
+//       forces one).  Each output element is a sum, in k order, of fma chains of 256 consecutive k each
+//       (per 8-deep slice in the order 0 4 1 5 2 6 3 7): a chain is closed into a second accumulator every
+//       eight stages, because one chain over K = 3072 rounds about three times as much as the blocked sum.
+//       Every tile uses that order, so the choice changes no bit.  Up to three weight matrices side by
+//       side (q/k/v: one launch).
+//       Epilogues: bias; bias + exact-erf GELU; bias + residual.
+//   be_attn_kernel<HD>   one workgroup per (sequence, head, 128 queries), a wave per 32 queries.  Key / value
+//       tiles of 32 positions stream through a double-buffered LDS image shared by the four waves; tiles
+//       with no live key are never loaded.  Scores are taken transposed (A rows are keys, B columns are
+//       queries) so a query's 32 scores sit in one lane pair; fp32 online softmax (running max and sum per
+//       query, the accumulator rescaled once per visited tile, tiles in ascending order); P . v takes the
+//       probability registers as they stand as the A operand.
+//   be_ln_kernel         a wave per row: LayerNorm of the GEMM's bias + residual output.
+//   be_pool_kernel       a thread per feature, the live rows after position 0 added in position order with a
+//       compensated sum (mean_no_cls) or row 0 (cls); zeros for a sequence with no live key.
+//
+// LayerNorm is two-pass (mean, then centred squares), biased variance, eps inside the square root.
+// Every output element has one summation order that depends on neither B nor the row's tile position,
+// and nothing uses atomics, so a call is bitwise repeatable and batch-invariant.
+#include "gr_common.h"
+
+namespace gr {
+namespace {
+
+constexpr int BE_MAX_S = 512, BE_MAX_H = 1024, BE_MAX_I = 4096;
+constexpr int64_t BE_MAX_B = 1ll << 16;
+constexpr int BE_BK = 32, BE_PITCH = BE_BK + 4, BE_NT = 256;
+constexpr int BE_KFLUSH = 8;               // 32-deep stages per fma chain: 256 deep
+constexpr int BE_QT = 128, BE_KT = 32;     // queries per workgroup, keys per streamed tile
+enum { BE_EPI_BIAS = 0, BE_EPI_GELU = 1, BE_EPI_RESID = 2 };
+
+struct BeSeg {   // up to three [seg_n, K] weight matrices side by side, and their biases
+  const float* w[3];
+  const float* b[3];
+};
+
+// WM waves down the tile's rows (4 / WM across its columns), each owning TM x TN blocks of 32 x 32 outputs.
+template <int WM, int TM, int TN, int EPI>
+__global__ __launch_bounds__(BE_NT, 2) void be_gemm_kernel(const float* __restrict__ x, BeSeg sg, int seg_n,
+                                                           const float* __restrict__ residual, float* __restrict__ y,
+                                                           int64_t M, int N, int K, int tiles_n) {
+  constexpr int WN = 4 / WM, BM = 32 * WM * TM, BN = 32 * WN * TN;
+  __shared__ __attribute__((aligned(16))) float lds[2][(BM + BN) * BE_PITCH];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave / WN, wn = wave % WN, r = lane & 31, h = lane >> 5;
+  const int tni = blockIdx.x % tiles_n;
+  const int64_t m0 = (int64_t)(blockIdx.x / tiles_n) * BM;
+  const int n0 = tni * BN;
+
+  constexpr int AV = BM * BE_BK / 4 / BE_NT, BV = BN * BE_BK / 4 / BE_NT;
+  f32x4 ra[AV], rb[BV];
+  auto gload = [&](int k0) {
+#pragma unroll
+    for (int i = 0; i < AV; ++i) {
+      const int f = tid + BE_NT * i, row = f >> 3, kk = k0 + (f & 7) * 4;
+      const int64_t g = m0 + row;
+      ra[i] = (g < M && kk < K) ? *reinterpret_cast<const f32x4*>(x + g * K + kk) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int i = 0; i < BV; ++i) {
+      const int f = tid + BE_NT * i, row = f >> 3, kk = k0 + (f & 7) * 4;
+      const int gn = n0 + row;
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (gn < N && kk < K) {
+        const int seg = gn / seg_n, wr = gn - seg * seg_n;
+        const float* wp = seg == 0 ? sg.w[0] : seg == 1 ? sg.w[1] : sg.w[2];
+        v = *reinterpret_cast<const f32x4*>(wp + (int64_t)wr * K + kk);
+      }
+      rb[i] = v;
+    }
+  };
+  auto swrite = [&](int buf) {
+    float* s = lds[buf];
+#pragma unroll
+    for (int i = 0; i < AV; ++i) {
+      const int f = tid + BE_NT * i;
+      *reinterpret_cast<f32x4*>(s + (f >> 3) * BE_PITCH + (f & 7) * 4) = ra[i];
+    }
+#pragma unroll
+    for (int i = 0; i < BV; ++i) {
+      const int f = tid + BE_NT * i;
+      *reinterpret_cast<f32x4*>(s + (BM + (f >> 3)) * BE_PITCH + (f & 7) * 4) = rb[i];
+    }
+  };
+
+  f32x16 acc[TM][TN], tot[TM][TN];
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int v = 0; v < 16; ++v) acc[i][j][v] = tot[i][j][v] = 0.f;
+
+  const int nk = (K + BE_BK - 1) / BE_BK;
+  gload(0);
+  swrite(0);
+  __syncthreads();
+  for (int kt = 0; kt < nk; ++kt) {
+    const int cur = kt & 1;
+    if (kt + 1 < nk) gload((kt + 1) * BE_BK);
+    const float* As = lds[cur] + (wm * 32 * TM + r) * BE_PITCH + 4 * h;
+    const float* Bs = lds[cur] + (BM + wn * 32 * TN + r) * BE_PITCH + 4 * h;
+#pragma unroll
+    for (int kc = 0; kc < BE_BK / 8; ++kc) {
+      f32x4 a[TM], b[TN];
+#pragma unroll
+      for (int i = 0; i < TM; ++i) a[i] = *reinterpret_cast<const f32x4*>(As + i * 32 * BE_PITCH + kc * 8);
+#pragma unroll
+      for (int j = 0; j < TN; ++j) b[j] = *reinterpret_cast<const f32x4*>(Bs + j * 32 * BE_PITCH + kc * 8);
+#pragma unroll
+      for (int s = 0; s < 4; ++s)
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+          for (int j = 0; j < TN; ++j) acc[i][j] = mfma32(a[i][s], b[j][s], acc[i][j]);
+    }
+    if ((kt + 1) % BE_KFLUSH == 0 || kt + 1 == nk) {   // close the 256-deep chain: a short chain rounds less
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+          tot[i][j] += acc[i][j];
+#pragma unroll
+          for (int v = 0; v < 16; ++v) acc[i][j][v] = 0.f;
+        }
+    }
+    if (kt + 1 < nk) swrite(cur ^ 1);
+    __syncthreads();
+  }
+
+#pragma unroll
+  for (int j = 0; j < TN; ++j) {
+    const int col = n0 + wn * 32 * TN + j * 32 + r;
+    if (col >= N) continue;
+    const int seg = col / seg_n;
+    const float* bp = seg == 0 ? sg.b[0] : seg == 1 ? sg.b[1] : sg.b[2];
+    const float bv = bp[col - seg * seg_n];
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+#pragma unroll
+      for (int v = 0; v < 16; ++v) {
+        const int64_t row = m0 + wm * 32 * TM + i * 32 + mfma32_row(v, h);
+        if (row < M) {
+          float o = tot[i][j][v] + bv;
+          if constexpr (EPI == BE_EPI_GELU) o = 0.5f * o * (1.0f + erff(o * 0.70710678118654752440f));
+          if constexpr (EPI == BE_EPI_RESID) o = residual[row * N + col] + o;
+          y[row * N + col] = o;
+        }
+      }
+    }
+  }
+}
+
+// LayerNorm of the row a wave holds as xv[t] = x[lane + 64 t] (0 past H), written to out.
+__device__ __forceinline__ void be_ln_row(float (&xv)[BE_MAX_H / 64], int lane, int H, const float* __restrict__ w,
+                                          const float* __restrict__ b, float eps, float* __restrict__ out) {
+  float s = 0.f;
+#pragma unroll
+  for (int t = 0; t < BE_MAX_H / 64; ++t) s += xv[t];
+  const float mean = wave_sum(s) / (float)H;
+  float ss = 0.f;
+#pragma unroll
+  for (int t = 0; t < BE_MAX_H / 64; ++t) {
+    xv[t] = lane + 64 * t < H ? xv[t] - mean : 0.f;
+    ss = fmaf(xv[t], xv[t], ss);
+  }
+  const float rstd = 1.0f / sqrtf(wave_sum(ss) / (float)H + eps);
+#pragma unroll
+  for (int t = 0; t < BE_MAX_H / 64; ++t) {
+    const int c = lane + 64 * t;
+    if (c < H) out[c] = (xv[t] * rstd) * w[c] + b[c];
+  }
+}
+
+__global__ __launch_bounds__(256) void be_embed_ln_kernel(const int64_t* __restrict__ ids,
+                                                          const int64_t* __restrict__ type_ids,
+                                                          const float* __restrict__ word, const float* __restrict__ pos,
+                                                          const float* __restrict__ type, const float* __restrict__ lnw,
+                                                          const float* __restrict__ lnb, float eps, int vocab,
+                                                          int type_vocab, int S, int H, int64_t M, float* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= M) return;
+  int64_t id = ids[row];
+  id = id < 0 ? 0 : id >= vocab ? vocab - 1 : id;
+  int64_t tt = type_ids != nullptr ? type_ids[row] : 0;
+  tt = tt < 0 ? 0 : tt >= type_vocab ? type_vocab - 1 : tt;
+  const int s = (int)(row % S);
+  const float* wr = word + id * H;
+  const float* tr = type + tt * H;
+  const float* pr = pos + (int64_t)s * H;
+  float xv[BE_MAX_H / 64];
+#pragma unroll
+  for (int t = 0; t < BE_MAX_H / 64; ++t) {
+    const int c = lane + 64 * t;
+    xv[t] = c < H ? (wr[c] + tr[c]) + pr[c] : 0.f;
+  }
+  be_ln_row(xv, lane, H, lnw, lnb, eps, out + row * H);
+}
+
+__global__ __launch_bounds__(256) void be_ln_kernel(const float* __restrict__ in, const float* __restrict__ lnw,
+                                                    const float* __restrict__ lnb, float eps, int H, int64_t M,
+                                                    float* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= M) return;
+  float xv[BE_MAX_H / 64];
+#pragma unroll
+  for (int t = 0; t < BE_MAX_H / 64; ++t) {
+    const int c = lane + 64 * t;
+    xv[t] = c < H ? in[row * H + c] : 0.f;
+  }
+  be_ln_row(xv, lane, H, lnw, lnb, eps, out + row * H);
+}
+
+template <int HD>
+__global__ __launch_bounds__(256) void be_attn_kernel(const float* __restrict__ qkv, const int64_t* __restrict__ mask,
+                                                      float* __restrict__ ctx, int S, int NH, int nqt, float scale) {
+  constexpr int P = HD + 4, NKC = HD / 8, NDB = HD / 32, LV = 2 * BE_KT * HD / 4 / 256;
+  __shared__ __attribute__((aligned(16))) float kv[2][2 * BE_KT * P];
+  __shared__ uint32_t livebits[BE_MAX_S / BE_KT];
+  __shared__ int tiles[BE_MAX_S / BE_KT];
+  __shared__ int ntl_s;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r = lane & 31, h = lane >> 5;
+  const int qt = blockIdx.x % nqt, head = (blockIdx.x / nqt) % NH;
+  const int64_t b = blockIdx.x / (nqt * NH);
+  const int Hd = NH * HD, ld = 3 * Hd;
+  const float* base = qkv + b * S * ld + head * HD;
+  const int nt = (S + BE_KT - 1) / BE_KT;
+
+  // bit j of livebits[t]: position 32 t + j is a key; tiles[]: the tiles that hold one, ascending
+  for (int t = wave; t < nt; t += 4) {
+    const int j = BE_KT * t + lane;
+    const bool live = lane < BE_KT && j < S && (mask == nullptr || mask[b * S + j] != 0);
+    const uint32_t bits = (uint32_t)__ballot(live);
+    if (lane == 0) livebits[t] = bits;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int n = 0;
+    for (int t = 0; t < nt; ++t)
+      if (livebits[t] != 0u) tiles[n++] = t;
+    ntl_s = n;
+  }
+  __syncthreads();
+  const int ntl = ntl_s;
+
+  const int q0 = qt * BE_QT + 32 * wave;
+  const bool active = q0 < S;             // wave-uniform
+  const int qrow = q0 + r < S ? q0 + r : S - 1;   // rows past S read row S - 1, never stored
+  f32x4 q[NKC];
+#pragma unroll
+  for (int kc = 0; kc < NKC; ++kc) q[kc] = *reinterpret_cast<const f32x4*>(base + (int64_t)qrow * ld + 8 * kc + 4 * h);
+
+  f32x4 rk[LV];
+  auto gload = [&](int t) {
+#pragma unroll
+    for (int i = 0; i < LV; ++i) {
+      const int f = tid + 256 * i, mat = f / (BE_KT * HD / 4), rem = f % (BE_KT * HD / 4);
+      const int row = rem / (HD / 4), c4 = rem % (HD / 4);
+      const int key = BE_KT * t + row < S ? BE_KT * t + row : S - 1;   // past S: finite, weighted 0
+      rk[i] = *reinterpret_cast<const f32x4*>(base + (int64_t)key * ld + (1 + mat) * Hd + 4 * c4);
+    }
+  };
+  auto swrite = [&](int buf) {
+#pragma unroll
+    for (int i = 0; i < LV; ++i) {
+      const int f = tid + 256 * i, mat = f / (BE_KT * HD / 4), rem = f % (BE_KT * HD / 4);
+      const int row = rem / (HD / 4), c4 = rem % (HD / 4);
+      *reinterpret_cast<f32x4*>(&kv[buf][(mat * BE_KT + row) * P + 4 * c4]) = rk[i];
+    }
+  };
+
+  f32x16 o[NDB];
+#pragma unroll
+  for (int d = 0; d < NDB; ++d)
+#pragma unroll
+    for (int v = 0; v < 16; ++v) o[d][v] = 0.f;
+  float m = -INFINITY, l = 0.f;   // of query r, the same in both lanes of the pair
+
+  if (ntl > 0) {
+    gload(tiles[0]);
+    swrite(0);
+  }
+  __syncthreads();
+  for (int it = 0; it < ntl; ++it) {
+    const int cur = it & 1;
+    if (it + 1 < ntl) gload(tiles[it + 1]);
+    if (active) {
+      const uint32_t bits = livebits[tiles[it]];
+      const float* Ks = kv[cur] + r * P + 4 * h;
+      const float* Vs = kv[cur] + BE_KT * P;
+      // scores, transposed: D register v of lane (r, h) is key mfma32_row(v, h) against query r
+      f32x16 sc;
+#pragma unroll
+      for (int v = 0; v < 16; ++v) sc[v] = 0.f;
+#pragma unroll
+      for (int kc = 0; kc < NKC; ++kc) {
+        const f32x4 kf = *reinterpret_cast<const f32x4*>(Ks + 8 * kc);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) sc = mfma32(kf[s], q[kc][s], sc);
+      }
+      float mt = -INFINITY;
+#pragma unroll
+      for (int v = 0; v < 16; ++v) {
+        const float a = ((bits >> mfma32_row(v, h)) & 1u) ? sc[v] * scale : -INFINITY;
+        sc[v] = a;
+        mt = fmaxf(mt, a);
+      }
+      mt = xmax<32>(mt);                       // the other sixteen keys of this query; finite: the tile has a live key
+      const float mn = fmaxf(m, mt);
+      const float alpha = expf(m - mn);        // 0 on the first visited tile (m = -inf)
+      float sum = 0.f;
+#pragma unroll
+      for (int v = 0; v < 16; ++v) {
+        sc[v] = expf(sc[v] - mn);              // exactly 0 for a masked key
+        sum += sc[v];
+      }
+      sum = xsum<32>(sum);
+      l = fmaf(l, alpha, sum);
+      m = mn;
+      // the accumulator's rows are queries mfma32_row(v, h): fetch their alpha from the lanes that own them
+      float av[16];
+#pragma unroll
+      for (int v = 0; v < 16; ++v) av[v] = __shfl(alpha, mfma32_row(v, h), 64);
+#pragma unroll
+      for (int d = 0; d < NDB; ++d) {
+#pragma unroll
+        for (int v = 0; v < 16; ++v) o[d][v] = o[d][v] * av[v];
+        // step s takes key mfma32_row(s, h) from lane half h: register s of the probabilities as they stand
+#pragma unroll
+        for (int s = 0; s < 16; ++s) o[d] = mfma32(sc[s], Vs[mfma32_row(s, h) * P + 32 * d + r], o[d]);
+      }
+    }
+    if (it + 1 < ntl) swrite(cur ^ 1);
+    __syncthreads();
+  }
+
+  if (active) {
+    float lv[16];
+#pragma unroll
+    for (int v = 0; v < 16; ++v) lv[v] = __shfl(l, mfma32_row(v, h), 64);
+#pragma unroll
+    for (int d = 0; d < NDB; ++d)
+#pragma unroll
+      for (int v = 0; v < 16; ++v) {
+        const int qi = q0 + mfma32_row(v, h);
+        if (qi < S) ctx[(b * S + qi) * Hd + head * HD + 32 * d + r] = lv[v] > 0.f ? o[d][v] / lv[v] : 0.f;
+      }
+  }
+}
+
+// mode 0: no pooling; 1: mean over the live rows after position 0; 2: row 0.  A sequence with no live
+// key gets zeros in pooled and in hidden_out.  hid: the last hidden state (hidden_out itself when given).
+__global__ __launch_bounds__(256) void be_pool_kernel(const float* hid, const int64_t* __restrict__ mask, int S, int H,
+                                                      int mode, float* __restrict__ pooled, float* hidden_out) {
+  const int c = blockIdx.y * 256 + threadIdx.x;
+  const int64_t b = blockIdx.x;
+  const bool col = c < H;
+  bool any = false;
+  int cnt = 0;
+  float acc = 0.f, lost = 0.f;   // compensated (Kahan) sum in position order: up to 511 rows
+  for (int i = 0; i < S; ++i) {
+    const bool lv = mask == nullptr || mask[b * S + i] != 0;
+    any = any || lv;
+    if (i >= 1 && lv) {
+      ++cnt;
+      if (mode == 1 && col) {
+        const float y = hid[(b * S + i) * H + c] - lost;
+        const float t = acc + y;
+        lost = (t - acc) - y;
+        acc = t;
+      }
+    }
+  }
+  if (!col) return;
+  if (mode == 1) pooled[b * H + c] = acc / fmaxf((float)cnt, 1e-9f);
+  if (mode == 2) pooled[b * H + c] = any ? hid[b * S * H + c] : 0.f;
+  if (!any && hidden_out != nullptr)
+    for (int i = 0; i < S; ++i) hidden_out[(b * S + i) * H + c] = 0.f;
+}
+
+const char* be_check(const gr_bert_params* p, int64_t B, int S) {
+  if (!p) return "null params";
+  if (B < 0) return "negative batch size";
+  if (p->hidden_size < 32 || p->hidden_size > BE_MAX_H || p->hidden_size % 32)
+    return "hidden_size must be a multiple of 32 in [32, 1024]";
+  if (p->head_dim != 32 && p->head_dim != 64) return "head_dim must be 32 or 64";
+  if (p->num_heads < 1 || p->num_heads * p->head_dim != p->hidden_size)
+    return "num_heads * head_dim must equal hidden_size";
+  if (p->intermediate_size < 32 || p->intermediate_size > BE_MAX_I || p->intermediate_size % 32)
+    return "intermediate_size must be a multiple of 32 in [32, 4096]";
+  if (p->num_layers < 1 || p->num_layers > GR_BERT_MAX_LAYERS) return "num_layers must be 1..24";
+  if (p->hidden_act != GR_BERT_ACT_GELU) return "hidden_act must be gelu";
+  if (p->position_type != GR_BERT_POS_ABSOLUTE) return "position_embedding_type must be absolute";
+  if (p->vocab_size < 1) return "vocab_size must be positive";
+  if (p->type_vocab_size < 1) return "type_vocab_size must be positive";
+  if (p->max_position < 1) return "max_position_embeddings must be positive";
+  if (S < 1 || S > BE_MAX_S) return "S must be 1..512 positions";
+  if (S > p->max_position) return "S must not exceed max_position_embeddings";
+  if (B > BE_MAX_B) return "B must be at most 65536 sequences";
+  return nullptr;
+}
+
+struct BeLayout {   // float offsets into the workspace
+  size_t x, t, qkv, ctx, ff, total;
+};
+
+BeLayout be_layout(const gr_bert_params* p, int64_t B, int S) {
+  const size_t M = (size_t)B * S, H = (size_t)p->hidden_size;
+  BeLayout L;
+  size_t o = 0;
+  L.x = o;   o += align_up(M * H, 4);
+  L.t = o;   o += align_up(M * H, 4);
+  L.qkv = o; o += align_up(M * 3 * H, 4);
+  L.ctx = o; o += align_up(M * H, 4);
+  L.ff = o;  o += align_up(M * (size_t)p->intermediate_size, 4);
+  L.total = o;
+  return L;
+}
+
+size_t be_bytes(const gr_bert_params* p, int64_t B, int S) { return be_layout(p, B, S).total * sizeof(float) + 16; }
+
+template <int EPI>
+int be_gemm(const char* what, const float* x, const BeSeg& sg, int seg_n, const float* residual, float* y, int64_t M,
+            int N, int K, hipStream_t st) {
+  // Three tiles, the same bits from each.  A compute unit works through its workgroups at one MFMA rate
+  // however many are resident, so a launch takes ceil(workgroups / compute units) rounds of one tile's
+  // work: take the tile with the least rounds x tile area (bert-base at 4096 rows: q/k/v is 2.25 rounds of
+  // 128 x 128 but exactly 3 of 128 x 96; the 768-wide outputs are 0.75 of 128 x 128 but exactly 1 of
+  // 128 x 96).  The factors charge the smaller tiles' extra operand traffic per multiply-add.
+  struct Tile { int bm, bn; double cost; };
+  const Tile tiles[3] = {{128, 128, 1.0}, {64, 128, 1.10}, {128, 96, 1.03}};
+  const int64_t cus = cu_count();
+  int pick = (int)option("bert_tile") - 1;
+  if (pick < 0) {
+    double best = 0.0;
+    for (int t = 0; t < 3; ++t) {
+      const int64_t wgs = ((M + tiles[t].bm - 1) / tiles[t].bm) * ((N + tiles[t].bn - 1) / tiles[t].bn);
+      const double c = (double)((wgs + cus - 1) / cus) * tiles[t].bm * tiles[t].bn * tiles[t].cost;
+      if (pick < 0 || c < best) pick = t, best = c;
+    }
+  }
+  const int tn = (N + tiles[pick].bn - 1) / tiles[pick].bn;
+  const dim3 grid((unsigned)(((M + tiles[pick].bm - 1) / tiles[pick].bm) * tn));
+  if (pick == 0) be_gemm_kernel<2, 2, 2, EPI><<<grid, dim3(BE_NT), 0, st>>>(x, sg, seg_n, residual, y, M, N, K, tn);
+  else if (pick == 1) be_gemm_kernel<2, 1, 2, EPI><<<grid, dim3(BE_NT), 0, st>>>(x, sg, seg_n, residual, y, M, N, K, tn);
+  else be_gemm_kernel<4, 1, 3, EPI><<<grid, dim3(BE_NT), 0, st>>>(x, sg, seg_n, residual, y, M, N, K, tn);
+  return check_launch(what);
+}
+
+}  // namespace
+}  // namespace gr
+
+extern "C" size_t gr_bert_embed_workspace_bytes(const gr_bert_params* p, int64_t B, int32_t S) {
+  if (gr::be_check(p, B, S)) return 0;
+  return gr::be_bytes(p, B, S);
+}
+
+extern "C" int gr_bert_embed_f32(const gr_bert_params* p, const int64_t* input_ids, const int64_t* attention_mask,
+                                 const int64_t* token_type_ids, int64_t B, int32_t S, int32_t pooling,
+                                 float* pooled_out, float* hidden_out, void* workspace, size_t workspace_bytes,
+                                 void* stream) {
+  using namespace gr;
+  clear_error();
+  const std::string who = "gr_bert_embed_f32: ";
+  if (const char* why = be_check(p, B, S)) return fail(!p || B < 0 ? GR_ERR_ARG : GR_ERR_UNSUPPORTED, who + why);
+  if (pooling != GR_BERT_POOL_NONE && pooling != GR_BERT_POOL_MEAN_NO_CLS && pooling != GR_BERT_POOL_CLS)
+    return fail(GR_ERR_ARG, who + "pooling must be GR_BERT_POOL_NONE, _MEAN_NO_CLS or _CLS");
+  if (B == 0) return GR_OK;
+  if (!workspace || workspace_bytes < be_bytes(p, B, S) || !aligned16(workspace))
+    return fail(GR_ERR_WORKSPACE, who + "workspace missing, misaligned or smaller than gr_bert_embed_workspace_bytes");
+  if (!input_ids) return fail(GR_ERR_ARG, who + "input_ids is null");
+  if (pooling != GR_BERT_POOL_NONE && !pooled_out) return fail(GR_ERR_ARG, who + "pooled_out is null");
+  if (pooling == GR_BERT_POOL_NONE && !hidden_out)
+    return fail(GR_ERR_ARG, who + "hidden_out is null and pooling is GR_BERT_POOL_NONE: nothing to compute");
+  if (hidden_out && !aligned16(hidden_out)) return fail(GR_ERR_ARG, who + "hidden_out must be 16-byte aligned");
+  bool ok = p->word && p->position && p->token_type && p->emb_ln_w && p->emb_ln_b;
+  for (int l = 0; ok && l < p->num_layers; ++l)
+    for (int i = 0; i < 16; ++i) ok = ok && p->layer[l][i] && aligned16(p->layer[l][i]);
+  if (!ok) return fail(GR_ERR_ARG, who + "a weight pointer is null or not 16-byte aligned");
+
+  const int H = p->hidden_size, I = p->intermediate_size, NH = p->num_heads, HD = p->head_dim;
+  const int64_t M = B * S;
+  const BeLayout L = be_layout(p, B, S);
+  float* ws = static_cast<float*>(workspace);
+  float *X = ws + L.x, *T = ws + L.t, *QKV = ws + L.qkv, *CTX = ws + L.ctx, *FF = ws + L.ff;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const unsigned row_blocks = (unsigned)((M + 3) / 4);
+  const float scale = sas_scale(HD);
+  const int nqt = (S + BE_QT - 1) / BE_QT;
+
+  be_embed_ln_kernel<<<dim3(row_blocks), dim3(256), 0, st>>>(input_ids, token_type_ids, p->word, p->position,
+                                                              p->token_type, p->emb_ln_w, p->emb_ln_b, p->eps,
+                                                              p->vocab_size, p->type_vocab_size, S, H, M, X);
+  if (int rc = check_launch("be_embed_ln_kernel")) return rc;
+  float* last = hidden_out ? hidden_out : X;
+  for (int l = 0; l < p->num_layers; ++l) {
+    const float* const* w = p->layer[l];
+    const BeSeg qkv_w = {{w[0], w[2], w[4]}, {w[1], w[3], w[5]}};
+    if (int rc = be_gemm<BE_EPI_BIAS>("bert q/k/v", X, qkv_w, H, nullptr, QKV, M, 3 * H, H, st)) return rc;
+    const dim3 ag((unsigned)(B * NH * nqt));
+    if (HD == 64) be_attn_kernel<64><<<ag, dim3(256), 0, st>>>(QKV, attention_mask, CTX, S, NH, nqt, scale);
+    else be_attn_kernel<32><<<ag, dim3(256), 0, st>>>(QKV, attention_mask, CTX, S, NH, nqt, scale);
+    if (int rc = check_launch("be_attn_kernel")) return rc;
+    const BeSeg ao = {{w[6], nullptr, nullptr}, {w[7], nullptr, nullptr}};
+    if (int rc = be_gemm<BE_EPI_RESID>("bert attention output + residual", CTX, ao, H, X, T, M, H, H, st)) return rc;
+    be_ln_kernel<<<dim3(row_blocks), dim3(256), 0, st>>>(T, w[8], w[9], p->eps, H, M, X);
+    if (int rc = check_launch("be_ln_kernel")) return rc;
+    const BeSeg inter = {{w[10], nullptr, nullptr}, {w[11], nullptr, nullptr}};
+    if (int rc = be_gemm<BE_EPI_GELU>("bert intermediate + gelu", X, inter, I, nullptr, FF, M, I, H, st)) return rc;
+    const BeSeg outw = {{w[12], nullptr, nullptr}, {w[13], nullptr, nullptr}};
+    if (int rc = be_gemm<BE_EPI_RESID>("bert output + residual", FF, outw, H, X, T, M, H, I, st)) return rc;
+    be_ln_kernel<<<dim3(row_blocks), dim3(256), 0, st>>>(T, w[14], w[15], p->eps, H, M,
+                                                         l + 1 == p->num_layers ? last : X);
+    if (int rc = check_launch("be_ln_kernel")) return rc;
+  }
+  be_pool_kernel<<<dim3((unsigned)B, (unsigned)((H + 255) / 256)), dim3(256), 0, st>>>(last, attention_mask, S, H, pooling,
+                                                                                       pooled_out, hidden_out);
+  return check_launch("be_pool_kernel");
+}

@@ -2005,3 +2005,144 @@ def t5_embed(binding, seq_embs, attention_mask=None, with_hidden=False):
             L.check(L.lib().gr_t5_embed_f32(binding.ref, L.ptr(seq_embs), L.ptr(attention_mask), B, S, L.ptr(pred),
                                             L.ptr(hidden), L.ptr(wsp), nbytes, L.stream_of(dev)), "gr_t5_embed_f32")
     return (pred, hidden) if with_hidden else pred
+
+
+BERT_LAYER_KEYS = ("attention.self.query.weight", "attention.self.query.bias", "attention.self.key.weight",
+                   "attention.self.key.bias", "attention.self.value.weight", "attention.self.value.bias",
+                   "attention.output.dense.weight", "attention.output.dense.bias",
+                   "attention.output.LayerNorm.weight", "attention.output.LayerNorm.bias",
+                   "intermediate.dense.weight", "intermediate.dense.bias", "output.dense.weight", "output.dense.bias",
+                   "output.LayerNorm.weight", "output.LayerNorm.bias")
+BERT_MAX_B = 1 << 16
+BERT_ENVELOPE = ("hidden_size a multiple of 32 up to 1024, = num_attention_heads * head width with the head width 32 "
+                 "or 64; intermediate_size a multiple of 32 up to 4096; 1..24 layers; hidden_act 'gelu'; absolute "
+                 "positions; 1..min(512, max_position_embeddings) positions; at most 65536 sequences per call")
+BERT_POOLINGS = {None: L.GR_BERT_POOL_NONE, "none": L.GR_BERT_POOL_NONE, "mean_no_cls": L.GR_BERT_POOL_MEAN_NO_CLS,
+                 "cls": L.GR_BERT_POOL_CLS}
+
+
+def bert_check(cfg, S=None, B=None):
+    """Raise NotImplementedError, naming the field, for what gr_bert_embed_f32 does not cover.  ``cfg``: HF's
+    ``BertConfig`` field names."""
+    def no(msg):
+        raise NotImplementedError(f"BERT encoder: {msg} (the gfx950 kernels cover: {BERT_ENVELOPE}); there is no CPU "
+                                  "fallback")
+    H, nh, I, nl = (int(cfg[k]) for k in ("hidden_size", "num_attention_heads", "intermediate_size",
+                                          "num_hidden_layers"))
+    if cfg.get("hidden_act", "gelu") != "gelu":
+        no(f"hidden_act={cfg['hidden_act']!r} is not built, only 'gelu'")
+    if cfg.get("position_embedding_type", "absolute") not in (None, "absolute"):
+        no(f"position_embedding_type={cfg['position_embedding_type']!r} is not built, only 'absolute'")
+    if H < 32 or H > 1024 or H % 32:
+        no(f"hidden_size={H} must be a multiple of 32 in [32, 1024]")
+    if nh < 1 or H % nh or H // nh not in (32, 64):
+        no(f"num_attention_heads={nh} must split hidden_size={H} into heads of 32 or 64")
+    if I < 32 or I > 4096 or I % 32:
+        no(f"intermediate_size={I} must be a multiple of 32 in [32, 4096]")
+    if not 1 <= nl <= L.GR_BERT_MAX_LAYERS:
+        no(f"num_hidden_layers={nl} must be 1..{L.GR_BERT_MAX_LAYERS}")
+    for k in ("vocab_size", "type_vocab_size", "max_position_embeddings"):
+        if int(cfg[k]) < 1:
+            no(f"{k}={cfg[k]} must be positive")
+    top = min(512, int(cfg["max_position_embeddings"]))
+    if S is not None and not 1 <= S <= top:
+        no(f"a sequence of {S} positions; 1..{top} are supported (max_position_embeddings="
+           f"{cfg['max_position_embeddings']})")
+    if B is not None and B > BERT_MAX_B:
+        no(f"a batch of {B} sequences; at most {BERT_MAX_B} per call")
+
+
+class BertBinding:
+    """Device-pointer view of a BERT encoder's parameters (``gr_bert_params``).  ``tensors``: name -> tensor with
+    ``BertModel``'s names (``embeddings.word_embeddings.weight``, ``encoder.layer.0.attention.self.query.weight``,
+    ...; the pooler is not read).  The pointers are the tensors' own storage, so in-place weight updates are
+    seen by the next call."""
+
+    def __init__(self, cfg, tensors):
+        bert_check(cfg)
+        self.cfg = cfg
+        self.keep = []
+        self.device = tensors["embeddings.word_embeddings.weight"].device
+        H, nh, I = int(cfg["hidden_size"]), int(cfg["num_attention_heads"]), int(cfg["intermediate_size"])
+        p = L.BertParams()
+        p.vocab_size, p.hidden_size, p.num_heads, p.head_dim = int(cfg["vocab_size"]), H, nh, H // nh
+        p.intermediate_size, p.num_layers = I, int(cfg["num_hidden_layers"])
+        p.max_position, p.type_vocab_size = int(cfg["max_position_embeddings"]), int(cfg["type_vocab_size"])
+        p.hidden_act = p.position_type = 0
+        p.eps = float(cfg.get("layer_norm_eps", 1e-12))
+        f = self._f
+        e = "embeddings."
+        p.word = f(tensors[e + "word_embeddings.weight"], (p.vocab_size, H))
+        p.position = f(tensors[e + "position_embeddings.weight"], (p.max_position, H))
+        p.token_type = f(tensors[e + "token_type_embeddings.weight"], (p.type_vocab_size, H))
+        p.emb_ln_w, p.emb_ln_b = f(tensors[e + "LayerNorm.weight"], (H,)), f(tensors[e + "LayerNorm.bias"], (H,))
+        shapes = {"intermediate.dense.weight": (I, H), "intermediate.dense.bias": (I,), "output.dense.weight": (H, I)}
+        for k in ("attention.self.query", "attention.self.key", "attention.self.value", "attention.output.dense"):
+            shapes[k + ".weight"] = (H, H)
+        for l in range(p.num_layers):
+            for i, k in enumerate(BERT_LAYER_KEYS):
+                p.layer[l][i] = f(tensors[f"encoder.layer.{l}.{k}"], shapes.get(k, (H,)), f"encoder.layer.{l}.{k}")
+        self.params = p
+        self.ref = ctypes.byref(p)
+        self._ws = {}
+
+    def _f(self, t, shape, name="an embedding parameter"):
+        L.require_gpu(t)
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise TypeError("the BERT kernels take contiguous float32 parameters")
+        if tuple(t.shape) != tuple(shape):
+            raise RuntimeError(f"{name} must be {tuple(shape)}, got {tuple(t.shape)}")
+        if t.device != self.device:
+            raise RuntimeError("the BERT parameters must be on one device")
+        self.keep.append(t)
+        return t.data_ptr()
+
+    def workspace_bytes(self, B, S):
+        n = self._ws.get((B, S))
+        if n is None:
+            n = self._ws[(B, S)] = L.lib().gr_bert_embed_workspace_bytes(self.ref, B, S)
+        return n
+
+
+def _bert_ids(name, t, B, S):
+    L.require_gpu(t)
+    if tuple(t.shape) != (B, S):
+        raise RuntimeError(f"{name} must be [{B}, {S}], got {tuple(t.shape)}")
+    if t.dtype != torch.int64:
+        t = t.to(torch.int64)
+    return t.contiguous()
+
+
+def bert_embed(binding, input_ids, attention_mask=None, token_type_ids=None, pooling="mean_no_cls", with_hidden=False):
+    """``gr_bert_embed_f32``: embeddings, the encoder stack and the pooling in one C call, nothing synchronises.
+    input_ids [B, S]; attention_mask [B, S] (0 = not a key, not pooled; None: all live); token_type_ids [B, S] or
+    None (zeros).  pooling "mean_no_cls" (the live rows after position 0, 0 when there is none), "cls" (row 0) or
+    None -> pooled [B, H][, hidden [B, S, H] with ``with_hidden``], or hidden alone when pooling is None.  A
+    sequence with no live key gives zeros."""
+    if pooling not in BERT_POOLINGS:
+        raise ValueError(f"pooling={pooling!r} must be 'mean_no_cls', 'cls' or None")
+    mode = BERT_POOLINGS[pooling]
+    if input_ids.dim() != 2:
+        raise RuntimeError(f"bert_embed takes [B, S] token ids, got {tuple(input_ids.shape)}")
+    B, S = input_ids.shape
+    input_ids = _bert_ids("input_ids", input_ids, B, S)
+    bert_check(binding.cfg, S, B)
+    if attention_mask is not None:
+        attention_mask = _bert_ids("attention_mask", attention_mask, B, S)
+    if token_type_ids is not None:
+        token_type_ids = _bert_ids("token_type_ids", token_type_ids, B, S)
+    dev = input_ids.device
+    H = binding.params.hidden_size
+    want_hidden = with_hidden or mode == L.GR_BERT_POOL_NONE
+    pooled = torch.empty((B, H), dtype=torch.float32, device=dev) if mode != L.GR_BERT_POOL_NONE else None
+    hidden = torch.empty((B, S, H), dtype=torch.float32, device=dev) if want_hidden else None
+    if B > 0:
+        nbytes = binding.workspace_bytes(B, S)
+        wsp = L.workspace(nbytes, dev)
+        with L.on(dev):
+            L.check(L.lib().gr_bert_embed_f32(binding.ref, L.ptr(input_ids), L.ptr(attention_mask),
+                                              L.ptr(token_type_ids), B, S, mode, L.ptr(pooled), L.ptr(hidden),
+                                              L.ptr(wsp), nbytes, L.stream_of(dev)), "gr_bert_embed_f32")
+    if pooled is None:
+        return hidden
+    return (pooled, hidden) if with_hidden else pooled

@@ -89,6 +89,10 @@ const char* gr_last_error(void);
  *                   launches: the quantizer's workgroups finish the leftover tiles' layers 2-3
  *                   themselves before they quantize them; 0: rq_leftover_kernel runs between the two
  *                   (three launches).  z and the IDs are bitwise the same.
+ *   "bert_tile"     0 (default): each GEMM of gr_bert_embed_f32 takes, of 128 x 128, 64 x 128 and
+ *                   128 x 96 outputs per workgroup, the tile that leaves the fewest compute units idle at
+ *                   its shape; 1 / 2 / 3: that tile on every GEMM.  One summation order: bitwise the
+ *                   same results.
  * The final block of a last-position forward (predict, last_hidden; gr_sasrec_plan reports the
  * choice): the H form when the tail kernel takes the shape (d / 4, head width / 4 and mlp / 4 powers
  * of two, at most 8 heads, d and mlp <= 256, 16-byte aligned weights); otherwise the pruned final
@@ -825,6 +829,67 @@ size_t gr_t5_embed_workspace_bytes(const gr_t5_embed_params* p, int64_t B, int32
 int gr_t5_embed_f32(const gr_t5_embed_params* p, const float* seq_embs, const int64_t* attention_mask,
                     int64_t B, int32_t S, float* pred_out, float* hidden_out, void* workspace,
                     size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------ */
+/* BERT text encoder (transformers' BertModel in eval mode, eager attention, absolute positions) with
+ * the reference's two poolings (T5/item_encode.py:11-34,59-78; major-encode/bert_emb.py:131-168).
+ *
+ * gr_bert_params: dimensions and device pointers (fp32, nn.Linear weights row-major [out, in]).
+ * word [vocab_size, H], position [max_position, H], token_type [type_vocab_size, H], emb_ln_w / emb_ln_b
+ * [H]; layer[l] = {query.weight, query.bias, key.weight, key.bias, value.weight, value.bias,
+ * attention.output.dense.weight, .bias, attention.output.LayerNorm.weight, .bias, intermediate.dense.weight,
+ * .bias, output.dense.weight, .bias, output.LayerNorm.weight, .bias}, each 16-byte aligned.
+ *
+ * Math (all fp32; H = hidden_size = num_heads * head_dim):
+ *   x = LN((word[id] + token_type[type]) + position[s]); ids and type ids are clamped into their tables,
+ *   token_type_ids NULL means type 0
+ *   per layer: a = softmax_j((q_i . k_j) / sqrt(head_dim)) v per head, over the live keys: key j is removed
+ *   wherever attention_mask[b, j] == 0 (any other value: live) and gets probability exactly 0 -- what HF's
+ *   additive finfo.min gives whenever the sequence has a live key;
+ *   x = LN(x + dense(a)); x = LN(x + output(gelu(intermediate(x)))), gelu(t) = t (1 + erf(t / sqrt 2)) / 2
+ *   LN(t) = (t - mean) / sqrt(var + eps) * w + b, biased variance, two-pass
+ *   GR_BERT_POOL_MEAN_NO_CLS: pooled = sum_{j >= 1, live} x_j / max(#{j >= 1, live}, 1e-9)  (0 when none is)
+ *   GR_BERT_POOL_CLS: pooled = x_0.  The pooler (pooler.dense) is never evaluated.
+ * Masks with holes are legal.  A sequence with no live key yields zeros in pooled_out and hidden_out.
+ * Rows of hidden_out at masked positions are what the encoder computes there; nothing live reads them.
+ *
+ * gr_bert_embed_f32 enqueues 2 + 7 num_layers launches and never synchronises: embeddings + LN; per layer
+ * q/k/v (one GEMM), attention, output dense + residual, LN, intermediate + gelu, output + residual, LN;
+ * pooling.  No floating-point atomics: every output element has one fixed summation order that depends
+ * on neither B nor the sequence's place in the batch, so two calls give the same bits and a sub-batch
+ * gives the bits of the whole batch's rows.
+ *   input_ids[B, S] int64; attention_mask[B, S] int64 or NULL (all live); token_type_ids[B, S] int64 or NULL
+ *   pooled_out[B, H] (NULL only with GR_BERT_POOL_NONE); hidden_out[B, S, H] 16-byte aligned, or NULL (NULL
+ *   with GR_BERT_POOL_NONE is GR_ERR_ARG: nothing to compute)
+ * Envelope (GR_ERR_UNSUPPORTED outside, with the field named, before any launch): hidden_size a multiple
+ * of 32 in [32, 1024] = num_heads * head_dim, head_dim 32 or 64; intermediate_size a multiple of 32 in
+ * [32, 4096]; num_layers 1..24; hidden_act gelu; absolute positions; 1 <= S <= min(512,
+ * max_position); B 0..65536 (B = 0: GR_OK, no launch).  B's bound keeps every 1-D grid (at most B * 512 / 64
+ * row tiles x 32 column tiles = 2^24 workgroups) and B * num_heads * 4 attention workgroups below 2^31.
+ * workspace: gr_bert_embed_workspace_bytes(p, B, S) bytes, 16-byte aligned (0 outside the envelope):
+ * B * S * (6 H + intermediate_size) floats. */
+#define GR_BERT_MAX_LAYERS 24
+#define GR_BERT_ACT_GELU 0
+#define GR_BERT_POS_ABSOLUTE 0
+#define GR_BERT_POOL_NONE 0
+#define GR_BERT_POOL_MEAN_NO_CLS 1
+#define GR_BERT_POOL_CLS 2
+typedef struct gr_bert_params {
+  int32_t vocab_size, hidden_size, num_heads, head_dim, intermediate_size, num_layers, max_position,
+      type_vocab_size, hidden_act, position_type;
+  float eps, reserved;
+  const float* word;
+  const float* position;
+  const float* token_type;
+  const float* emb_ln_w;
+  const float* emb_ln_b;
+  const float* layer[GR_BERT_MAX_LAYERS][16];
+} gr_bert_params;
+
+size_t gr_bert_embed_workspace_bytes(const gr_bert_params* p, int64_t B, int32_t S);
+int gr_bert_embed_f32(const gr_bert_params* p, const int64_t* input_ids, const int64_t* attention_mask,
+                      const int64_t* token_type_ids, int64_t B, int32_t S, int32_t pooling, float* pooled_out,
+                      float* hidden_out, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
