@@ -197,6 +197,14 @@ SIGNATURES = {
     "gr_tiger_generate_prefix_f32": (ctypes.c_int, [ctypes.POINTER(TigerParams), ctypes.POINTER(TigerPrefixParams),
                                                     _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp,
                                                     _vp, _vp, _vp, _sz, _vp]),
+    "gr_tiger_forward_workspace_bytes": (_sz, [ctypes.POINTER(TigerParams), _i64, _i32, _i32]),
+    "gr_tiger_forward_f32": (ctypes.c_int, [ctypes.POINTER(TigerParams), _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp,
+                                            _vp, _vp, _sz, _vp]),
+    "gr_tiger_forward_prefix_workspace_bytes": (_sz, [ctypes.POINTER(TigerParams), ctypes.POINTER(TigerPrefixParams),
+                                                      _i64, _i32, _i32]),
+    "gr_tiger_forward_prefix_f32": (ctypes.c_int, [ctypes.POINTER(TigerParams), ctypes.POINTER(TigerPrefixParams),
+                                                   _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp,
+                                                   _vp, _sz, _vp]),
     "gr_beam_hits_i64": (ctypes.c_int, [_vp, _i64, _i32, _i32, _i64, _vp, _i32, _vp, _vp]),
     "gr_t5_embed_workspace_bytes": (_sz, [ctypes.POINTER(T5EmbedParams), _i64, _i32]),
     "gr_t5_embed_f32": (ctypes.c_int, [ctypes.POINTER(T5EmbedParams), _vp, _vp, _i64, _i32, _vp, _vp, _vp, _sz, _vp]),

@@ -22,6 +22,9 @@
 //                         the mean.  It writes the prefix token and (level 0) the [S + 3] key mask.
 // tiger_encoder_kernel<true> is the encoder with rows 0..2 taken from those tokens (<false>: the plain
 // entry's, whose code is what it was); the search kernel is launched unchanged on S + 3 keys.
+//
+// The teacher-forced forward (gr_tiger_forward_f32, gr_tiger_forward_prefix_f32) launches the same encoder
+// (and adapter) kernels and then tiger_teacher_kernel and tiger_loss_kernel, further down in this file.
 #include <atomic>
 
 #include "gr_common.h"
@@ -873,6 +876,45 @@ size_t tiger_prefix_bytes(const gr_tiger_params* p, int64_t B) {
   return align_up((size_t)B * TG_PREFIX * p->d_model * sizeof(float), 16);
 }
 
+// The checks the generate and the forward entries share, in the order their callers make them.
+int tiger_check_ids_and_prefix(const std::string& who, const gr_tiger_params* p, const gr_tiger_prefix_params* pp,
+                               const float* const* prof, bool prefixed) {
+  if (p->eos_id < 0 || p->eos_id >= p->vocab || p->pad_id < 0 || p->pad_id >= p->vocab || p->fill_id < 0 ||
+      p->fill_id >= p->vocab)
+    return fail(GR_ERR_ARG, who + "pad, eos and fill ids must lie in [0, vocab)");
+  if (prefixed) {
+    bool ok = true;
+    for (int l = 0; l < 3; ++l)
+      for (int i = 0; i < 14; ++i) ok = ok && pp->adapter[l][i] && aligned16(pp->adapter[l][i]);
+    if (!ok) return fail(GR_ERR_ARG, who + "an adapter weight pointer is null or not 16-byte aligned");
+    for (int l = 0; l < 3; ++l)
+      if (!prof[l] || !aligned16(prof[l]))
+        return fail(GR_ERR_ARG, who + "a prof_lvl pointer is null or not 16-byte aligned");
+  }
+  return GR_OK;
+}
+
+bool tiger_weights_ok(const gr_tiger_params* p) {
+  bool ok = p->shared && p->lm_head && p->enc_rel && p->dec_rel && p->enc_final_ln && p->dec_final_ln &&
+            p->enc_bucket && p->dec_bucket && aligned16(p->shared) && aligned16(p->lm_head);
+  for (int l = 0; ok && l < p->n_enc; ++l)
+    for (int i = 0; i < 8; ++i) ok = ok && p->enc[l][i] && aligned16(p->enc[l][i]);
+  for (int l = 0; ok && l < p->n_dec; ++l)
+    for (int i = 0; i < 13; ++i) ok = ok && p->dec[l][i] && aligned16(p->dec[l][i]);
+  return ok;
+}
+
+constexpr size_t kTigerLdsMax = 159 * 1024;   // dynamic part; the kernels' static LDS is under 1 KB
+
+size_t tiger_enc_lds(const gr_tiger_params* p, int St) {
+  const EncLayout EL = enc_layout(St, p->d_model, p->n_heads * p->d_kv, p->d_kv, p->n_heads, p->d_ff, TG_ENC_THREADS / 64);
+  return (size_t)EL.total * sizeof(float);
+}
+
+// Raises the dynamic LDS limit of the encoder, search and teacher kernels (defined below, after the last of them):
+// the limit is a property of the kernel on the current device, raised on each device's first call.
+int tiger_raise_lds(const std::string& who);
+
 // Both entries: pp == nullptr is gr_tiger_generate_f32 (two launches); otherwise the adapter launch comes
 // first and the encoder and the search run on S + 3 positions with the mask it wrote.
 int tiger_generate(const char* fn, const gr_tiger_params* p, const gr_tiger_prefix_params* pp, const int64_t* input_ids,
@@ -889,54 +931,19 @@ int tiger_generate(const char* fn, const gr_tiger_params* p, const gr_tiger_pref
     const bool arg = !p || B < 0;
     return fail(arg ? GR_ERR_ARG : GR_ERR_UNSUPPORTED, who + why);
   }
-  if (p->eos_id < 0 || p->eos_id >= p->vocab || p->pad_id < 0 || p->pad_id >= p->vocab || p->fill_id < 0 ||
-      p->fill_id >= p->vocab)
-    return fail(GR_ERR_ARG, who + "pad, eos and fill ids must lie in [0, vocab)");
-  if (prefixed) {
-    bool ok = true;
-    for (int l = 0; l < 3; ++l)
-      for (int i = 0; i < 14; ++i) ok = ok && pp->adapter[l][i] && aligned16(pp->adapter[l][i]);
-    if (!ok) return fail(GR_ERR_ARG, who + "an adapter weight pointer is null or not 16-byte aligned");
-    for (int l = 0; l < 3; ++l)
-      if (!prof[l] || !aligned16(prof[l]))
-        return fail(GR_ERR_ARG, who + "a prof_lvl pointer is null or not 16-byte aligned");
-  }
+  if (int rc = tiger_check_ids_and_prefix(who, p, pp, prof, prefixed)) return rc;
   const size_t plain = tiger_plain_bytes(p, B, St, num_beams, max_length);
   const size_t need = prefixed ? plain + tiger_mask_bytes(B, S) + tiger_prefix_bytes(p, B) : plain;
   if (!workspace || workspace_bytes < need || !aligned16(workspace))
     return fail(GR_ERR_WORKSPACE, who + "workspace missing, misaligned or smaller than " +
                                       (prefixed ? "gr_tiger_prefix_workspace_bytes" : "gr_tiger_workspace_bytes"));
   if (!input_ids || !sequences || !scores) return fail(GR_ERR_ARG, who + "null pointer");
-  bool ok = p->shared && p->lm_head && p->enc_rel && p->dec_rel && p->enc_final_ln && p->dec_final_ln &&
-            p->enc_bucket && p->dec_bucket && aligned16(p->shared) && aligned16(p->lm_head);
-  for (int l = 0; ok && l < p->n_enc; ++l)
-    for (int i = 0; i < 8; ++i) ok = ok && p->enc[l][i] && aligned16(p->enc[l][i]);
-  for (int l = 0; ok && l < p->n_dec; ++l)
-    for (int i = 0; i < 13; ++i) ok = ok && p->dec[l][i] && aligned16(p->dec[l][i]);
-  if (!ok) return fail(GR_ERR_ARG, who + "a weight pointer is null or not 16-byte aligned");
+  if (!tiger_weights_ok(p)) return fail(GR_ERR_ARG, who + "a weight pointer is null or not 16-byte aligned");
   if (B == 0) return GR_OK;
-  const int inner = p->n_heads * p->d_kv;
-  const EncLayout EL = enc_layout(St, p->d_model, inner, p->d_kv, p->n_heads, p->d_ff, TG_ENC_THREADS / 64);
-  const size_t enc_lds = (size_t)EL.total * sizeof(float), srch_lds = (size_t)SR_TOTAL * sizeof(float);
-  constexpr size_t kLdsMax = 159 * 1024;   // dynamic part; the kernels' static LDS is under 1 KB
-  if (enc_lds > kLdsMax || srch_lds > kLdsMax)
+  const size_t enc_lds = tiger_enc_lds(p, St), srch_lds = (size_t)SR_TOTAL * sizeof(float);
+  if (enc_lds > kTigerLdsMax || srch_lds > kTigerLdsMax)
     return fail(GR_ERR_UNSUPPORTED, who + "the per-user state does not fit in LDS");
-  // the limit is a property of the kernel on the current device: raised on each device's first call
-  static std::atomic<uint64_t> lds_raised{0};
-  int devid = 0;
-  if (hipGetDevice(&devid) != hipSuccess) return fail(GR_ERR_HIP, who + "no current device");
-  const uint64_t bit = 1ull << (devid & 63);
-  if (!(lds_raised.load() & bit)) {
-    const bool lds_ok =
-        hipFuncSetAttribute(reinterpret_cast<const void*>(tiger_encoder_kernel<false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax) == hipSuccess &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(tiger_encoder_kernel<true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax) == hipSuccess &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(tiger_search_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax) == hipSuccess;
-    if (!lds_ok) return fail(GR_ERR_HIP, who + "cannot raise the dynamic LDS limit");
-    lds_raised.fetch_or(bit);
-  }
+  if (int rc = tiger_raise_lds(who)) return rc;
   float* cross = static_cast<float*>(workspace);
   float* selfkv = cross + align_up(tiger_cross_floats(p, B, St), 4);
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -963,6 +970,385 @@ int tiger_generate(const char* fn, const gr_tiger_params* p, const gr_tiger_pref
 
 }  // namespace
 }  // namespace gr
+
+// The teacher-forced forward (gr_tiger_forward_f32, gr_tiger_forward_prefix_f32): T5ForConditionalGeneration.forward
+// with labels in eval mode -- the encoder launch (and the adapter launch) of generate, unchanged, then
+//   tiger_teacher_kernel  the decoder over all Ld label positions at once.  A user has at most 8 rows, so a
+//                         workgroup takes TF_USERS users (32 rows, the search kernel's row block); row r of a
+//                         workgroup is (user r / Ld, position r % Ld).  The current layer's self-attention K/V
+//                         stay in LDS; cross K/V are read per user from the workspace.  A wave per row does the
+//                         fp32 log-softmax and the label's NLL; a thread per user adds its NLLs in position order.
+//   tiger_loss_kernel     one workgroup: the per-user (sum, count) pairs added in a fixed order in double,
+//                         loss = sum / count rounded to fp32 once; no atomics.
+// Every value of a row is an fma chain over k in order (tg_gemm) or a per-row reduction, so a user's logits
+// and NLLs do not depend on its group-mates or on its place in the batch.
+namespace gr {
+namespace {
+
+constexpr int TF_USERS = 4, TF_ROWS = TF_USERS * TG_MAX_T, TF_LOSS_THREADS = 256;
+constexpr int TF_IGNORE = -100, TF_BAD = -1;   // labels in LDS: ignored; outside [0, vocab)
+// The LDS layout is fixed at the envelope's largest shapes (32 rows, d_model and heads * d_kv 64, d_ff 256,
+// 128 keys, 16 waves), as SR_*: 67 KB per workgroup, two workgroups per compute unit.  q, k and v of the
+// layer's attention take the place of the feed-forward's hidden rows (and of the logits).
+constexpr int TF_H = 0, TF_XN = TF_H + TF_ROWS * 64, TF_AO = TF_XN + TF_ROWS * 64, TF_FF = TF_AO + TF_ROWS * 64,
+              TF_Q = TF_FF, TF_K = TF_Q + TF_ROWS * 64, TF_V = TF_K + TF_ROWS * 64,
+              TF_PROW = TF_FF + TF_ROWS * 256, TF_DBIAS = TF_PROW + (TG_SRCH_THREADS / 64) * TG_MAX_S,
+              TF_NLL = TF_DBIAS + 8 * TG_MAX_T, TF_TOK = TF_NLL + TF_ROWS, TF_LAB = TF_TOK + TF_ROWS,
+              TF_KMASK = TF_LAB + TF_ROWS, TF_TOTAL = TF_KMASK + TF_USERS * TG_MAX_S;
+static_assert(TF_V + TF_ROWS * 64 <= TF_PROW && TF_ROWS * TG_MAX_V <= TF_ROWS * 256, "teacher layout");
+
+__global__ __launch_bounds__(TG_SRCH_THREADS) void tiger_teacher_kernel(
+    gr_tiger_params p, const int64_t* __restrict__ amask, const int64_t* __restrict__ labels, int64_t B, int S, int Ld,
+    const float* __restrict__ cross, float* __restrict__ logits_out, float* __restrict__ nll_out,
+    double* __restrict__ pairs) {
+  extern __shared__ __align__(16) float lds[];
+  int D = p.d_model, dkv = p.d_kv, H = p.n_heads, dff = p.d_ff, V = p.vocab;
+  float* h = lds + TF_H;
+  float* xn = lds + TF_XN;
+  float* ao = lds + TF_AO;
+  float* ff = lds + TF_FF;         // feed-forward hidden rows, then the logits
+  float* q = lds + TF_Q;
+  float* sk = lds + TF_K;
+  float* sv = lds + TF_V;
+  float* prow = lds + TF_PROW;
+  float* dbias = lds + TF_DBIAS;   // decoder relative bias of (distance, head)
+  float* nllrow = lds + TF_NLL;
+  int* tok = reinterpret_cast<int*>(lds + TF_TOK);   // the shifted decoder input
+  int* lab = reinterpret_cast<int*>(lds + TF_LAB);
+  int* kmask = reinterpret_cast<int*>(lds + TF_KMASK);
+
+  __shared__ const float* wtab[GR_TIGER_MAX_LAYERS * 13 + 3];   // as in the search kernel
+  const float* const* gshared = wtab + GR_TIGER_MAX_LAYERS * 13;
+  __shared__ int cint[1];
+  __shared__ float cflt[2];
+  const int64_t u0 = (int64_t)blockIdx.x * TF_USERS;
+  const int nu = B - u0 < TF_USERS ? (int)(B - u0) : TF_USERS;
+  int rows = nu * Ld;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  for (int e = tid; e < p.n_dec * 13; e += TG_THREADS) wtab[e] = p.dec[e / 13][e % 13];
+  if (tid == 0) {
+    cint[0] = p.n_dec;
+    cflt[0] = p.eps;
+    cflt[1] = p.lm_scale;
+    wtab[GR_TIGER_MAX_LAYERS * 13] = p.shared;
+    wtab[GR_TIGER_MAX_LAYERS * 13 + 1] = p.lm_head;
+    wtab[GR_TIGER_MAX_LAYERS * 13 + 2] = p.dec_final_ln;
+  }
+  for (int e = tid; e < H * TG_MAX_T; e += TG_THREADS) dbias[e] = p.dec_rel[p.dec_bucket[e / H] * H + e % H];
+  for (int e = tid; e < nu * S; e += TG_THREADS)
+    kmask[(e / S) * TG_MAX_S + e % S] = amask ? (amask[u0 * S + e] != 0) : 1;
+  // T5's _shift_right: the start token, then the labels with -100 replaced by the pad id
+  for (int r = tid; r < rows; r += TG_THREADS) {
+    const int64_t lb = labels[u0 * Ld + r];
+    const int64_t prev = r % Ld ? labels[u0 * Ld + r - 1] : (int64_t)p.pad_id;
+    tok[r] = prev == TF_IGNORE ? p.pad_id : tg_token(prev, V);
+    lab[r] = lb == TF_IGNORE ? TF_IGNORE : (lb < 0 || lb >= V ? TF_BAD : (int)lb);
+  }
+  __syncthreads();
+  for (int e = tid; e < rows * D; e += TG_THREADS) h[e] = gshared[0][(size_t)tok[e / D] * D + e % D];
+  __syncthreads();
+
+  for (int l = 0; l < cint[0]; ++l) {
+    TG_OPAQUE(D); TG_OPAQUE(dkv); TG_OPAQUE(H); TG_OPAQUE(dff); TG_OPAQUE(S); TG_OPAQUE(Ld); TG_OPAQUE(rows);
+    const int inner = H * dkv;
+    const float* const* W = wtab + l * 13;
+    const int n_dec = cint[0];
+    const float eps = cflt[0];
+    // causal self-attention with the decoder's relative bias
+    tg_rmsnorm(xn, h, W[D_LN0], rows, D, eps, 1.f);
+    __syncthreads();
+    tg_gemm<0>(q, inner, xn, D, W[D_Q], inner, D, rows);
+    tg_gemm<0>(sk, inner, xn, D, W[D_K], inner, D, rows);
+    tg_gemm<0>(sv, inner, xn, D, W[D_V], inner, D, rows);
+    __syncthreads();
+    for (int it = tid; it < rows * H; it += TG_THREADS) {
+      const int r = it / H, hd = it % H, t = r % Ld, r0 = r - t;
+      const float* qv = q + r * inner + hd * dkv;
+      float s[TG_MAX_T], mx = -INFINITY;
+#pragma unroll
+      for (int pos = 0; pos < TG_MAX_T; ++pos) {
+        s[pos] = -INFINITY;
+        if (pos <= t) {
+          const float* kr = sk + (r0 + pos) * inner + hd * dkv;
+          float a = 0.f;
+          for (int c = 0; c < dkv; ++c) a = fmaf(qv[c], kr[c], a);
+          s[pos] = a + dbias[(t - pos) * H + hd];
+        }
+        mx = fmaxf(mx, s[pos]);
+      }
+      float sum = 0.f;
+#pragma unroll
+      for (int pos = 0; pos < TG_MAX_T; ++pos) {
+        s[pos] = pos <= t ? expf(s[pos] - mx) : 0.f;
+        sum += s[pos];
+      }
+#pragma unroll
+      for (int pos = 0; pos < TG_MAX_T; ++pos) s[pos] = s[pos] / sum;
+      for (int c = 0; c < dkv; ++c) {
+        float a = 0.f;
+#pragma unroll
+        for (int pos = 0; pos < TG_MAX_T; ++pos)
+          if (pos <= t) a = fmaf(s[pos], sv[(r0 + pos) * inner + hd * dkv + c], a);
+        ao[r * inner + hd * dkv + c] = a;
+      }
+    }
+    __syncthreads();
+    tg_gemm<1>(h, D, ao, inner, W[D_O], D, inner, rows);
+    __syncthreads();
+    // cross-attention over each row's user's encoder keys (no position bias, padding masked)
+    tg_rmsnorm(xn, h, W[D_LN1], rows, D, eps, 1.f);
+    __syncthreads();
+    tg_gemm<0>(q, inner, xn, D, W[D_CQ], inner, D, rows);
+    __syncthreads();
+    for (int it0 = 0; it0 < rows * H; it0 += TG_WAVES) {
+      const int it = it0 + wave;
+      const int r = it / H, hd = it % H, ug = r / Ld;
+      float* pr = prow + wave * TG_MAX_S;
+      const float* cu = cross + (size_t)(u0 + ug) * n_dec * 2 * S * inner;
+      const float* ck = cu + (size_t)(2 * l) * S * inner;
+      const float* cv = cu + (size_t)(2 * l + 1) * S * inner;
+      if (it < rows * H) {
+        const float* qv = q + r * inner + hd * dkv;
+        const int* km = kmask + ug * TG_MAX_S;
+        float s[2], mx = -INFINITY;
+#pragma unroll
+        for (int k2 = 0; k2 < 2; ++k2) {
+          const int j = lane + 64 * k2;
+          s[k2] = -INFINITY;
+          if (j < S && km[j]) {
+            const float4* kr = reinterpret_cast<const float4*>(ck + (size_t)j * inner + hd * dkv);
+            float a = 0.f;
+            for (int c = 0; c < dkv; c += 4) {
+              const float4 kk = kr[c >> 2];
+              a = fmaf(qv[c], kk.x, a);
+              a = fmaf(qv[c + 1], kk.y, a);
+              a = fmaf(qv[c + 2], kk.z, a);
+              a = fmaf(qv[c + 3], kk.w, a);
+            }
+            s[k2] = a;
+          }
+          mx = fmaxf(mx, s[k2]);
+        }
+        mx = wave_max(mx);
+        float sum = 0.f;
+#pragma unroll
+        for (int k2 = 0; k2 < 2; ++k2) {
+          s[k2] = (s[k2] == -INFINITY) ? 0.f : expf(s[k2] - mx);
+          sum += s[k2];
+        }
+        sum = wave_sum(sum);
+#pragma unroll
+        for (int k2 = 0; k2 < 2; ++k2) {
+          const int j = lane + 64 * k2;
+          if (j < S) pr[j] = s[k2] / sum;
+        }
+      }
+      __syncthreads();
+      if (it < rows * H) {
+        const int c = lane % dkv, g = lane / dkv, G = 64 / dkv;
+        float a = 0.f;
+        for (int j = g; j < S; j += G) a = fmaf(pr[j], cv[(size_t)j * inner + hd * dkv + c], a);
+        a = tg_group_sum(a, dkv);
+        if (lane < dkv) ao[r * inner + hd * dkv + c] = a;
+      }
+      __syncthreads();
+    }
+    tg_gemm<1>(h, D, ao, inner, W[D_CO], D, inner, rows);
+    __syncthreads();
+    // feed-forward
+    tg_rmsnorm(xn, h, W[D_LN2], rows, D, eps, 1.f);
+    __syncthreads();
+    tg_gemm<2>(ff, dff, xn, D, W[D_WI], dff, D, rows);
+    __syncthreads();
+    tg_gemm<1>(h, D, ff, dff, W[D_WO], D, dff, rows);
+    __syncthreads();
+  }
+  TG_OPAQUE(D); TG_OPAQUE(V); TG_OPAQUE(Ld); TG_OPAQUE(rows);
+  // lm_head on the scaled final norm; rows of a workgroup are consecutive rows of [B, Ld]
+  tg_rmsnorm(xn, h, gshared[2], rows, D, cflt[0], cflt[1]);
+  __syncthreads();
+  tg_gemm<0>(ff, V, xn, D, gshared[1], V, D, rows);
+  __syncthreads();
+  if (logits_out)
+    for (int e = tid; e < rows * V; e += TG_THREADS) logits_out[(size_t)u0 * Ld * V + e] = ff[e];
+  // -log_softmax(logits)[label]: 0 where the label is ignored, NaN where it is outside [0, vocab) (the
+  // read itself uses a clamped index)
+  for (int r = wave; r < rows; r += TG_WAVES) {
+    float v[2], mx = -INFINITY;
+#pragma unroll
+    for (int k2 = 0; k2 < 2; ++k2) {
+      const int j = lane + 64 * k2;
+      v[k2] = j < V ? ff[r * V + j] : -INFINITY;
+      mx = fmaxf(mx, v[k2]);
+    }
+    mx = wave_max(mx);
+    float sum = 0.f;
+#pragma unroll
+    for (int k2 = 0; k2 < 2; ++k2) sum += (lane + 64 * k2 < V) ? expf(v[k2] - mx) : 0.f;
+    const float lse = logf(wave_sum(sum));
+    if (lane == 0) {
+      const int lb = lab[r];
+      const float lp = (ff[r * V + min(max(lb, 0), V - 1)] - mx) - lse;
+      nllrow[r] = lb == TF_IGNORE ? 0.f : (lb == TF_BAD ? __builtin_nanf("") : -lp);
+    }
+  }
+  __syncthreads();
+  if (nll_out)
+    for (int r = tid; r < rows; r += TG_THREADS) nll_out[u0 * Ld + r] = nllrow[r];
+  if (tid < nu) {
+    double s = 0.0;
+    int n = 0;
+    for (int t = 0; t < Ld; ++t)
+      if (lab[tid * Ld + t] != TF_IGNORE) {
+        s += (double)nllrow[tid * Ld + t];
+        ++n;
+      }
+    pairs[2 * (u0 + tid)] = s;
+    pairs[2 * (u0 + tid) + 1] = (double)n;
+  }
+}
+
+// loss = sum of the users' NLL sums / sum of their counts (NaN when nothing is counted, as torch's mean over
+// no element): thread i adds users i, i + 256, ... in order, then a fixed tree over the threads.
+__global__ __launch_bounds__(TF_LOSS_THREADS) void tiger_loss_kernel(const double* __restrict__ pairs, int64_t B,
+                                                                     float* __restrict__ loss) {
+  __shared__ double ssum[TF_LOSS_THREADS], scnt[TF_LOSS_THREADS];
+  const int tid = threadIdx.x;
+  double s = 0.0, n = 0.0;
+  for (int64_t u = tid; u < B; u += TF_LOSS_THREADS) {
+    s += pairs[2 * u];
+    n += pairs[2 * u + 1];
+  }
+  ssum[tid] = s;
+  scnt[tid] = n;
+  __syncthreads();
+  for (int o = TF_LOSS_THREADS / 2; o > 0; o >>= 1) {
+    if (tid < o) {
+      ssum[tid] += ssum[tid + o];
+      scnt[tid] += scnt[tid + o];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) *loss = (float)(ssum[0] / scnt[0]);
+}
+
+int tiger_raise_lds(const std::string& who) {
+  static std::atomic<uint64_t> lds_raised{0};
+  int devid = 0;
+  if (hipGetDevice(&devid) != hipSuccess) return fail(GR_ERR_HIP, who + "no current device");
+  const uint64_t bit = 1ull << (devid & 63);
+  if (lds_raised.load() & bit) return GR_OK;
+  for (const void* kernel : {reinterpret_cast<const void*>(tiger_encoder_kernel<false>),
+                             reinterpret_cast<const void*>(tiger_encoder_kernel<true>),
+                             reinterpret_cast<const void*>(tiger_search_kernel),
+                             reinterpret_cast<const void*>(tiger_teacher_kernel)})
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTigerLdsMax) != hipSuccess)
+      return fail(GR_ERR_HIP, who + "cannot raise the dynamic LDS limit");
+  lds_raised.fetch_or(bit);
+  return GR_OK;
+}
+
+size_t tiger_pairs_bytes(int64_t B) { return align_up((size_t)B * 2 * sizeof(double), 16); }
+
+// cross K/V | per-user (sum, count) pairs [| the [B, S + 3] mask | the prefix tokens]
+size_t tiger_forward_plain_bytes(const gr_tiger_params* p, int64_t B, int S) {
+  return align_up(tiger_cross_floats(p, B, S) * sizeof(float), 16) + tiger_pairs_bytes(B) + 16;
+}
+
+const char* tiger_forward_check(const gr_tiger_params* p, int64_t B, int St, int Ld) {
+  if (p && p->vocab < 2) return "vocab_size must be at least 2";
+  if (const char* why = tiger_check(p, B, St, 1, 2)) return why;   // the envelope, without a beam or a length
+  if (Ld < 1 || Ld > TG_MAX_T) return "labels must hold 1..8 positions (Ld)";
+  return nullptr;
+}
+
+// Both forward entries, as tiger_generate: pp == nullptr is gr_tiger_forward_f32.
+int tiger_forward(const char* fn, const gr_tiger_params* p, const gr_tiger_prefix_params* pp, const int64_t* input_ids,
+                  const int64_t* attention_mask, const float* const* prof, const int64_t* labels, int64_t B, int32_t S,
+                  int32_t Ld, float* loss, float* logits, float* nll, float* enc_out, void* workspace,
+                  size_t workspace_bytes, void* stream, bool prefixed) {
+  clear_error();
+  const std::string who = std::string(fn) + ": ";
+  if (prefixed) {
+    if (const char* why = tiger_prefix_check(p, pp, S)) return fail(!p || !pp ? GR_ERR_ARG : GR_ERR_UNSUPPORTED, who + why);
+  }
+  const int St = prefixed ? S + TG_PREFIX : S;   // encoder positions
+  if (const char* why = tiger_forward_check(p, B, St, Ld)) {
+    const bool arg = !p || B < 0;
+    return fail(arg ? GR_ERR_ARG : GR_ERR_UNSUPPORTED, who + why);
+  }
+  if (int rc = tiger_check_ids_and_prefix(who, p, pp, prof, prefixed)) return rc;
+  const size_t plain = tiger_forward_plain_bytes(p, B, St);
+  const size_t need = prefixed ? plain + tiger_mask_bytes(B, S) + tiger_prefix_bytes(p, B) : plain;
+  if (!workspace || workspace_bytes < need || !aligned16(workspace))
+    return fail(GR_ERR_WORKSPACE, who + "workspace missing, misaligned or smaller than " +
+                                      (prefixed ? "gr_tiger_forward_prefix_workspace_bytes"
+                                                : "gr_tiger_forward_workspace_bytes"));
+  if (!input_ids || !labels || !loss) return fail(GR_ERR_ARG, who + "null pointer");
+  if (!tiger_weights_ok(p)) return fail(GR_ERR_ARG, who + "a weight pointer is null or not 16-byte aligned");
+  if (B == 0) return GR_OK;
+  const size_t enc_lds = tiger_enc_lds(p, St), tf_lds = (size_t)TF_TOTAL * sizeof(float);
+  static_assert((size_t)TF_TOTAL * sizeof(float) <= kTigerLdsMax, "teacher layout");
+  if (enc_lds > kTigerLdsMax) return fail(GR_ERR_UNSUPPORTED, who + "the per-user state does not fit in LDS");
+  if (int rc = tiger_raise_lds(who)) return rc;
+  float* cross = static_cast<float*>(workspace);
+  char* after = static_cast<char*>(workspace) + align_up(tiger_cross_floats(p, B, St) * sizeof(float), 16);
+  double* pairs = reinterpret_cast<double*>(after);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (prefixed) {
+    int64_t* ext_mask = reinterpret_cast<int64_t*>(static_cast<char*>(workspace) + plain);
+    float* prefix = reinterpret_cast<float*>(static_cast<char*>(workspace) + plain + tiger_mask_bytes(B, S));
+    tiger_adapter_kernel<<<dim3((unsigned)B, TG_PREFIX), dim3(AD_THREADS), 0, st>>>(
+        *pp, p->shared, p->vocab, p->d_model, input_ids, attention_mask, prof[0], prof[1], prof[2], S, ext_mask, prefix,
+        nullptr);
+    if (int rc = check_launch("tiger_adapter_kernel")) return rc;
+    tiger_encoder_kernel<true><<<dim3((unsigned)B), dim3(TG_ENC_THREADS), enc_lds, st>>>(*p, input_ids, ext_mask, St,
+                                                                                     cross, enc_out, prefix);
+    if (int rc = check_launch("tiger_encoder_kernel<true>")) return rc;
+    attention_mask = ext_mask;
+  } else {
+    tiger_encoder_kernel<false><<<dim3((unsigned)B), dim3(TG_ENC_THREADS), enc_lds, st>>>(*p, input_ids, attention_mask, S,
+                                                                                     cross, enc_out, nullptr);
+    if (int rc = check_launch("tiger_encoder_kernel")) return rc;
+  }
+  tiger_teacher_kernel<<<dim3((unsigned)((B + TF_USERS - 1) / TF_USERS)), dim3(TG_SRCH_THREADS), tf_lds, st>>>(
+      *p, attention_mask, labels, B, St, Ld, cross, logits, nll, pairs);
+  if (int rc = check_launch("tiger_teacher_kernel")) return rc;
+  tiger_loss_kernel<<<dim3(1), dim3(TF_LOSS_THREADS), 0, st>>>(pairs, B, loss);
+  return check_launch("tiger_loss_kernel");
+}
+
+}  // namespace
+}  // namespace gr
+
+extern "C" size_t gr_tiger_forward_workspace_bytes(const gr_tiger_params* p, int64_t B, int32_t S, int32_t Ld) {
+  if (gr::tiger_forward_check(p, B, S, Ld)) return 0;
+  return gr::tiger_forward_plain_bytes(p, B, S);
+}
+
+extern "C" int gr_tiger_forward_f32(const gr_tiger_params* p, const int64_t* input_ids, const int64_t* attention_mask,
+                                    const int64_t* labels, int64_t B, int32_t S, int32_t Ld, float* loss, float* logits,
+                                    float* nll, float* enc_out, void* workspace, size_t workspace_bytes, void* stream) {
+  return gr::tiger_forward("gr_tiger_forward_f32", p, nullptr, input_ids, attention_mask, nullptr, labels, B, S, Ld, loss,
+                           logits, nll, enc_out, workspace, workspace_bytes, stream, false);
+}
+
+extern "C" size_t gr_tiger_forward_prefix_workspace_bytes(const gr_tiger_params* p, const gr_tiger_prefix_params* pp,
+                                                          int64_t B, int32_t S, int32_t Ld) {
+  using namespace gr;
+  if (tiger_prefix_check(p, pp, S) || tiger_forward_check(p, B, S + TG_PREFIX, Ld)) return 0;
+  return tiger_forward_plain_bytes(p, B, S + TG_PREFIX) + tiger_mask_bytes(B, S) + tiger_prefix_bytes(p, B);
+}
+
+extern "C" int gr_tiger_forward_prefix_f32(const gr_tiger_params* p, const gr_tiger_prefix_params* pp,
+                                           const int64_t* input_ids, const int64_t* attention_mask, const float* prof1,
+                                           const float* prof2, const float* prof3, const int64_t* labels, int64_t B,
+                                           int32_t S, int32_t Ld, float* loss, float* logits, float* nll, float* enc_out,
+                                           void* workspace, size_t workspace_bytes, void* stream) {
+  const float* prof[3] = {prof1, prof2, prof3};
+  return gr::tiger_forward("gr_tiger_forward_prefix_f32", p, pp, input_ids, attention_mask, prof, labels, B, S, Ld, loss,
+                           logits, nll, enc_out, workspace, workspace_bytes, stream, true);
+}
 
 extern "C" size_t gr_tiger_workspace_bytes(const gr_tiger_params* p, int64_t B, int32_t S, int32_t num_beams,
                                            int32_t max_length) {

@@ -1717,6 +1717,13 @@ class TigerBinding:
             n = self._ws[key] = L.lib().gr_tiger_workspace_bytes(self.ref, B, S, num_beams, max_length)
         return n
 
+    def forward_workspace_bytes(self, B, S, Ld):
+        key = ("forward", B, S, Ld)
+        n = self._ws.get(key)
+        if n is None:
+            n = self._ws[key] = L.lib().gr_tiger_forward_workspace_bytes(self.ref, B, S, Ld)
+        return n
+
 
 def tiger_generate(binding, input_ids, attention_mask=None, num_beams=20, max_length=5, with_encoder=False,
                    with_logits=False):
@@ -1822,6 +1829,13 @@ class TigerPrefixBinding:
                                                                         max_length)
         return n
 
+    def forward_workspace_bytes(self, n_vec, B, S, Ld):
+        key = ("forward", n_vec, B, S, Ld)
+        n = self._ws.get(key)
+        if n is None:
+            n = self._ws[key] = L.lib().gr_tiger_forward_prefix_workspace_bytes(self.t5.ref, self.ref(n_vec), B, S, Ld)
+        return n
+
 
 def tiger_generate_prefix(binding, input_ids, attention_mask, prof_lvl1, prof_lvl2, prof_lvl3, num_beams=20,
                           max_length=5, with_prefix=False, with_encoder=False, with_logits=False):
@@ -1872,6 +1886,92 @@ def tiger_generate_prefix(binding, input_ids, attention_mask, prof_lvl1, prof_lv
         if on:
             out += (t,)
     return out
+
+
+def _tiger_forward_args(what, input_ids, attention_mask, labels):
+    """The shape and dtype checks both forward calls share -> (ids, mask, labels, B, S, Ld), contiguous."""
+    L.require_gpu(input_ids, labels)
+    if input_ids.dim() != 2 or input_ids.dtype != torch.int64:
+        raise RuntimeError(f"{what} takes [B, S] int64 token ids, got {tuple(input_ids.shape)} {input_ids.dtype}")
+    B, S = input_ids.shape
+    if labels.dim() != 2 or labels.shape[0] != B or labels.dtype != torch.int64:
+        raise RuntimeError(f"{what} takes [{B}, Ld] int64 labels, got {tuple(labels.shape)} {labels.dtype}")
+    Ld = int(labels.shape[1])
+    if not 1 <= Ld <= 8:
+        raise NotImplementedError(f"TIGER: labels of {Ld} positions; 1..8 are supported (the gfx950 kernels cover: "
+                                  f"{TIGER_ENVELOPE}); there is no CPU fallback")
+    if attention_mask is not None:
+        L.require_gpu(attention_mask)
+        if tuple(attention_mask.shape) != (B, S):
+            raise RuntimeError(f"attention_mask must be [{B}, {S}], got {tuple(attention_mask.shape)}")
+        if attention_mask.dtype != torch.int64:
+            attention_mask = attention_mask.to(torch.int64)
+        attention_mask = attention_mask.contiguous()
+    return input_ids.contiguous(), attention_mask, labels.contiguous(), B, S, Ld
+
+
+def _tiger_forward_outputs(B, S_enc, Ld, V, D, dev, with_logits, with_nll, with_encoder):
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    logits = torch.empty((B, Ld, V), dtype=torch.float32, device=dev) if with_logits else None
+    nll = torch.empty((B, Ld), dtype=torch.float32, device=dev) if with_nll else None
+    enc = torch.empty((B, S_enc, D), dtype=torch.float32, device=dev) if with_encoder else None
+    return loss, logits, nll, enc
+
+
+def _tiger_forward_result(loss, logits, nll, enc):
+    return (loss,) + tuple(t for t in (logits, nll, enc) if t is not None)
+
+
+def tiger_forward(binding, input_ids, attention_mask, labels, with_logits=True, with_nll=False, with_encoder=False):
+    """``gr_tiger_forward_f32``: T5ForConditionalGeneration.forward with ``labels`` in eval mode (the call of
+    the reference's ``eval_loss``) as one C call, nothing synchronises.  labels [B, Ld] int64, -100 = not counted.
+    -> (loss 0-dim fp32[, logits [B, Ld, vocab]][, per-position NLL [B, Ld], 0 where not counted][, encoder
+    output [B, S, d_model]])."""
+    input_ids, attention_mask, labels, B, S, Ld = _tiger_forward_args("tiger_forward", input_ids, attention_mask, labels)
+    tiger_check_config(binding.cfg, None, S, None)
+    dev = input_ids.device
+    loss, logits, nll, enc = _tiger_forward_outputs(B, S, Ld, binding.params.vocab, binding.params.d_model, dev,
+                                                    with_logits, with_nll, with_encoder)
+    if B == 0:          # an empty tensor has no address to pass: torch's mean over no element
+        return _tiger_forward_result(loss.fill_(float("nan")), logits, nll, enc)
+    nbytes = binding.forward_workspace_bytes(B, S, Ld)
+    wsp = L.workspace(nbytes, dev)
+    with L.on(dev):
+        L.check(L.lib().gr_tiger_forward_f32(binding.ref, L.ptr(input_ids), L.ptr(attention_mask), L.ptr(labels), B, S,
+                                             Ld, L.ptr(loss), L.ptr(logits), L.ptr(nll), L.ptr(enc), L.ptr(wsp), nbytes,
+                                             L.stream_of(dev)), "gr_tiger_forward_f32")
+    return _tiger_forward_result(loss, logits, nll, enc)
+
+
+def tiger_forward_prefix(binding, input_ids, attention_mask, prof_lvl1, prof_lvl2, prof_lvl3, labels, with_logits=True,
+                         with_nll=False, with_encoder=False):
+    """``gr_tiger_forward_prefix_f32``: ``tiger_forward`` on the S + 3 encoder positions of ``tiger_generate_prefix``
+    (the adapter launch first); the encoder output then is [B, S + 3, d_model]."""
+    prof = [prof_lvl1, prof_lvl2, prof_lvl3]
+    L.require_gpu(*prof)
+    input_ids, attention_mask, labels, B, S, Ld = _tiger_forward_args("tiger_forward_prefix", input_ids, attention_mask,
+                                                                      labels)
+    n_vec = int(prof[0].shape[1]) if prof[0].dim() == 3 else -1
+    for i, t in enumerate(prof):
+        if t.dtype != torch.float32 or tuple(t.shape) != (B, n_vec, binding.bert_dim):
+            raise RuntimeError(f"prof_lvl{i + 1} must be float32 [{B}, n_vec, {binding.bert_dim}], got {t.dtype} "
+                               f"{tuple(t.shape)}")
+    tiger_prefix_check(binding.cfg, binding.bert_dim, n_vec, S)
+    tiger_check_config(binding.cfg, None, S + 3, None)
+    prof = [t.contiguous() for t in prof]
+    dev = input_ids.device
+    loss, logits, nll, enc = _tiger_forward_outputs(B, S + 3, Ld, binding.t5.params.vocab, binding.t5.params.d_model,
+                                                    dev, with_logits, with_nll, with_encoder)
+    if B == 0:
+        return _tiger_forward_result(loss.fill_(float("nan")), logits, nll, enc)
+    nbytes = binding.forward_workspace_bytes(n_vec, B, S, Ld)
+    wsp = L.workspace(nbytes, dev)
+    with L.on(dev):
+        L.check(L.lib().gr_tiger_forward_prefix_f32(
+            binding.t5.ref, binding.ref(n_vec), L.ptr(input_ids), L.ptr(attention_mask), L.ptr(prof[0]), L.ptr(prof[1]),
+            L.ptr(prof[2]), L.ptr(labels), B, S, Ld, L.ptr(loss), L.ptr(logits), L.ptr(nll), L.ptr(enc), L.ptr(wsp),
+            nbytes, L.stream_of(dev)), "gr_tiger_forward_prefix_f32")
+    return _tiger_forward_result(loss, logits, nll, enc)
 
 
 def beam_hits(preds, labels, skip=0):

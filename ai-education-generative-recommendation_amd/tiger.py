@@ -5,7 +5,10 @@ searched by beam search -- inference only, on the gfx950 kernels of csrc/tiger.h
 reference's names (``model.shared.weight``, ``model.encoder.block.0.layer.0.SelfAttention.q.weight``,
 ..., tied entries included), so a reference checkpoint loads unchanged; it does not import
 ``transformers``.  ``generate`` is the reference's call (``max_length=5``, ``num_return_sequences =
-num_beams``) as one C call with no host round trip; the training loss is not built.
+num_beams``) as one C call with no host round trip.  ``forward(input_ids, attention_mask, labels)`` under
+``.eval()`` and ``torch.no_grad()`` is the reference's evaluation call: the teacher-forced logits and the mean
+cross-entropy over the labels that are not -100 (``eval_loss`` restates RQVAE-T5/train.py:40-51 on it); the
+backward and the optimiser step are not built, so the same call in training mode raises.
 
 ``codes_to_tokens`` and ``collate`` reproduce the token map and ``GenRecDataLoader.collate_fn`` on
 arrays, so the output of ``RQVAE.generate_codes`` feeds ``TIGER`` directly; ``evaluate_model`` restates
@@ -128,9 +131,20 @@ class TIGER(nn.Module):
             self._binding_key = key
         return self._binding
 
+    def _forward_guard(self, labels):
+        if self.training or torch.is_grad_enabled():
+            raise NotImplementedError("TIGER.forward in training mode or with gradients enabled is not built: training "
+                                      "of the T5 model (backward and the optimiser step) is out of scope here; call it "
+                                      "under .eval() and torch.no_grad() for the evaluation loss, or use generate()")
+        if labels is None:
+            raise ValueError("TIGER.forward needs labels: it is the teacher-forced evaluation call (loss, logits); "
+                             "decoder_input_ids and the library's other keyword arguments are not built")
+
     def forward(self, input_ids, attention_mask=None, labels=None):
-        raise NotImplementedError("TIGER.forward (the training loss and teacher-forced logits) is not built: "
-                                  "training of the T5 model is out of scope here; use generate()")
+        """The reference's evaluation call (``eval_loss``): -> (loss 0-dim fp32, logits [B, Ld, vocab] fp32), the
+        mean NLL over the labels that are not -100, as one C call with no host round trip."""
+        self._forward_guard(labels)
+        return ops.tiger_forward(self.binding(), input_ids, attention_mask, labels)
 
     @torch.no_grad()
     def generate_scored(self, input_ids, attention_mask=None, num_beams=20, max_length=MAX_LENGTH):
@@ -195,6 +209,22 @@ def crop_like_library(seqs, eos_id):
     length = torch.where(is_eos, pos, torch.full_like(pos, T - 1)).amin(-1)      # generated tokens per hypothesis
     width = 1 + length.max()
     return torch.where(torch.arange(T, device=seqs.device) < width, seqs, torch.zeros_like(seqs))
+
+
+def eval_loss(model, test_loader, device):
+    """RQVAE-T5/train.py:40-51 (and RQVAE-T5-prefix/train.py:55-76: a batch that carries ``prof_lvl1..3`` passes
+    them to the model): eval mode, one teacher-forced forward and one ``loss.item()`` per batch under
+    ``torch.no_grad()``, training mode again at the end; the mean over the batches."""
+    model.eval()
+    total_loss = 0.0
+    with torch.no_grad():
+        for batch in test_loader:
+            args = {k: batch[k].to(device) for k in ("prof_lvl1", "prof_lvl2", "prof_lvl3") if k in batch}
+            loss, _ = model(input_ids=batch["history"].to(device), attention_mask=batch["attention_mask"].to(device),
+                            labels=batch["target"].to(device), **args)
+            total_loss += loss.item()
+    model.train()
+    return total_loss / len(test_loader)
 
 
 @torch.no_grad()

@@ -770,6 +770,42 @@ int gr_tiger_generate_prefix_f32(const gr_tiger_params* p, const gr_tiger_prefix
                                  float* enc_out, float* step_logits, void* workspace, size_t workspace_bytes,
                                  void* stream);
 
+/* TIGER teacher-forced forward: the evaluation-time call model(input_ids, attention_mask, labels) of
+ * eval_loss (RQVAE-T5/train.py:40-51), i.e. T5ForConditionalGeneration.forward with labels under
+ * model.eval() and torch.no_grad() -- gr_tiger_forward_f32; gr_tiger_forward_prefix_f32 is the same call
+ * of RQVAE-T5-prefix/train.py's eval_loss with prof_lvl1..3 (RQVAE-T5-prefix/model.py TIGER.forward).
+ * Forward only: no dropout, no gradient.
+ *
+ * The decoder input row is [pad_id, labels[:, :-1]] with every -100 replaced by pad_id (_shift_right).
+ * The decoder runs over all Ld positions at once: causal self-attention with the decoder's relative
+ * bias, cross-attention over the user's encoder keys (padding masked, no position bias), the ReLU
+ * feed-forward, the final norm times lm_scale, lm_head.
+ *   labels[B, Ld] int64; -100 marks a position that is not counted (anywhere in a row)
+ *   loss: one fp32, the mean over the counted positions of -log_softmax(logits)[label]; NaN when no
+ *   position of the batch is counted (torch's mean over nothing).  A label outside [0, vocab) that is
+ *   not -100 never faults (every read uses a clamped index); its NLL, and so the loss, is NaN.
+ *   logits[B, Ld, vocab] (optional); nll[B, Ld] (optional): the per-position NLL, 0 where not counted
+ *   enc_out (optional) and the other arguments as in the generate entries
+ * Launches, never synchronising: generate's encoder kernel (after generate's adapter kernel in the
+ * prefix entry), a teacher kernel (one workgroup per four users; log-softmax and NLL per row, a
+ * (sum, count) pair per user) and a one-workgroup loss kernel that adds the pairs in a fixed order in
+ * double and rounds once: a call is bitwise repeatable, and a user's logits and NLLs do not depend on
+ * the rest of the batch.
+ * Envelope: the generate entries' without num_beams and max_length (vocab >= 2); 1 <= Ld <= 8.
+ * workspace: gr_tiger_forward_workspace_bytes / gr_tiger_forward_prefix_workspace_bytes (cross K/V,
+ * the pairs, and for the prefix entry the mask and the prefix tokens; 0 outside the envelope). */
+size_t gr_tiger_forward_workspace_bytes(const gr_tiger_params* p, int64_t B, int32_t S, int32_t Ld);
+int gr_tiger_forward_f32(const gr_tiger_params* p, const int64_t* input_ids, const int64_t* attention_mask,
+                         const int64_t* labels, int64_t B, int32_t S, int32_t Ld, float* loss, float* logits,
+                         float* nll, float* enc_out, void* workspace, size_t workspace_bytes, void* stream);
+size_t gr_tiger_forward_prefix_workspace_bytes(const gr_tiger_params* p, const gr_tiger_prefix_params* pp,
+                                               int64_t B, int32_t S, int32_t Ld);
+int gr_tiger_forward_prefix_f32(const gr_tiger_params* p, const gr_tiger_prefix_params* pp,
+                                const int64_t* input_ids, const int64_t* attention_mask, const float* prof1,
+                                const float* prof2, const float* prof3, const int64_t* labels, int64_t B,
+                                int32_t S, int32_t Ld, float* loss, float* logits, float* nll, float* enc_out,
+                                void* workspace, size_t workspace_bytes, void* stream);
+
 /* calculate_pos_index of RQVAE-T5/utils.py:6-32: hits[b, j] = 1 for the first beam j whose tokens
  * equal labels[b, :], 0 elsewhere.  preds: beam j of user b starts at preds + (b * k + j) * ld_pred
  * and holds pred_len tokens; positions past pred_len compare as 0 (evaluate_model's zero padding) and
