@@ -211,6 +211,9 @@ SIGNATURES = {
     "gr_bert_embed_workspace_bytes": (_sz, [ctypes.POINTER(BertParams), _i64, _i32]),
     "gr_bert_embed_f32": (ctypes.c_int, [ctypes.POINTER(BertParams), _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp,
                                          _sz, _vp]),
+    "gr_bert_embed_ragged_workspace_bytes": (_sz, [ctypes.POINTER(BertParams), _i64, _i32, _i64]),
+    "gr_bert_embed_ragged_f32": (ctypes.c_int, [ctypes.POINTER(BertParams), _vp, _vp, _vp, _i64, _i32, _i64, _i32, _vp,
+                                                _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

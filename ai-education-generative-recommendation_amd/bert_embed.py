@@ -143,57 +143,93 @@ class BertEncoder(nn.Module):
         with torch.no_grad():
             return BertOutput(ops.bert_embed(self.binding(), input_ids, attention_mask, token_type_ids, pooling=None))
 
-    def embed(self, input_ids, attention_mask=None, token_type_ids=None, pooling="mean_no_cls"):
+    def embed(self, input_ids, attention_mask=None, token_type_ids=None, pooling="mean_no_cls", ragged=False,
+              rows_bound=None):
         """-> [B, H] in one C call.  ``"mean_no_cls"``: ``(hidden * mask)[:, 1:].sum(1) / mask[:, 1:].sum(-1)
         .clamp(min=1e-9)`` (major-encode/bert_emb.py:160-165), which is T5/item_encode.py:74-75 for every sequence
         with a live token after position 0; a sequence with none returns 0 where item_encode.py's unclamped division
         gives NaN.  ``"cls"``: row 0 of the last hidden state (item_encode.py:28).  A mask entry other than 0
-        counts as 1."""
+        counts as 1.
+
+        ``ragged=True``: the same bits from the ragged entry, which computes only the rows up to each sequence's last
+        live position.  ``rows_bound`` is an upper bound on their count (``row_bound(mask)`` of a host-side mask
+        gives it exactly); None means B * S, which is always safe.  Neither form synchronises."""
         self._refuse_training()
         if pooling not in ("mean_no_cls", "cls"):
             raise ValueError(f"pooling={pooling!r} must be 'mean_no_cls' or 'cls'")
         with torch.no_grad():
+            if ragged:
+                return ops.bert_embed_ragged(self.binding(), input_ids, attention_mask, token_type_ids, pooling=pooling,
+                                             rows_bound=rows_bound)
             return ops.bert_embed(self.binding(), input_ids, attention_mask, token_type_ids, pooling=pooling)
 
 
+def row_bound(attention_mask, S=None):
+    """The packed row count of the ragged entry for ``attention_mask`` [B, S]: the sum over the sequences of one past
+    the last live position (0 for a sequence with no live key) -- exact for a mask on the host.  A mask on a device
+    is not read (that would synchronise): the answer is B * S, the bound that is always safe.  None (all live) gives
+    None, which ``embed`` and ``ops.bert_embed_ragged`` read as B * S.  ``S``: the padded width when it is not the
+    mask's own (a mask wider than the ids)."""
+    if attention_mask is None:
+        return None
+    B, width = attention_mask.shape
+    S = width if S is None else int(S)
+    if attention_mask.is_cuda:
+        return B * S
+    live = attention_mask[:, :S] != 0
+    last = torch.arange(1, live.shape[1] + 1)[None, :] * live
+    return int(last.max(dim=1).values.sum()) if live.numel() else 0
+
+
 def _tokenize(tokenizer, texts, max_length, device):
+    """-> (the encoded batch on ``device``, the ragged entry's row bound taken from the mask where the tokenizer left
+    it: exact on the host, B * S on a device)."""
     encoded = tokenizer(list(texts), padding=True, truncation=True, max_length=max_length, return_tensors="pt")
+    mask = encoded.get("attention_mask")
+    B, S = encoded["input_ids"].shape
+    bound = B * S if mask is None else row_bound(mask, S)
     if hasattr(encoded, "to"):
-        return encoded.to(device)
-    return {k: v.to(device) for k, v in encoded.items()}
+        return encoded.to(device), bound
+    return {k: v.to(device) for k, v in encoded.items()}, bound
 
 
-def _embed_encoded(model, encoded, pooling):
-    return model.embed(encoded["input_ids"], encoded.get("attention_mask"), encoded.get("token_type_ids"), pooling=pooling)
+def _embed_encoded(model, encoded, pooling, bound, ragged):
+    """The ragged entry when it has rows to leave out, the padded one otherwise: the same bits from both."""
+    ids = encoded["input_ids"]
+    ragged = ragged and bound < ids.shape[0] * ids.shape[1]
+    return model.embed(ids, encoded.get("attention_mask"), encoded.get("token_type_ids"), pooling=pooling,
+                       ragged=ragged, rows_bound=bound if ragged else None)
 
 
 @torch.no_grad()
-def encode_texts(texts, tokenizer, model, device, batch_size, max_length):
+def encode_texts(texts, tokenizer, model, device, batch_size, max_length, *, ragged=True):
     """The item pass (T5/item_encode.py:59-78, major-encode/bert_emb.py:131-168): batches of ``batch_size`` texts,
     tokenized with padding to the batch's longest and truncation at ``max_length``, mean-pooled without [CLS] ->
-    float32 array [len(texts), H].  A text with no live token after position 0 gives a zero row."""
+    float32 array [len(texts), H].  A text with no live token after position 0 gives a zero row.  ``ragged``: batches
+    with padding go through the ragged entry with the row count taken from the tokenizer's host-side mask (the same
+    bits, less work); False keeps every batch on the padded entry."""
     model.eval()
     device = torch.device(device)
     embs = []
     for start in range(0, len(texts), batch_size):
-        encoded = _tokenize(tokenizer, texts[start:start + batch_size], max_length, device)
-        embs.append(_embed_encoded(model, encoded, "mean_no_cls"))
+        encoded, bound = _tokenize(tokenizer, texts[start:start + batch_size], max_length, device)
+        embs.append(_embed_encoded(model, encoded, "mean_no_cls", bound, ragged))
     if not embs:
         return np.zeros((0, model.config["hidden_size"]), np.float32)
     return torch.cat(embs, dim=0).cpu().numpy().astype(np.float32)
 
 
 @torch.no_grad()
-def generate_user_profile_embedding(user_profile_map, tokenizer, model):
+def generate_user_profile_embedding(user_profile_map, tokenizer, model, *, ragged=True):
     """The profile pass (T5/item_encode.py:11-34): users in sorted order, batches of 32, 64 tokens at most, the
-    [CLS] row -> {user id: float32 vector [H]}.  Runs on the model's device."""
+    [CLS] row -> {user id: float32 vector [H]}.  Runs on the model's device.  ``ragged``: as in ``encode_texts``."""
     device = next(model.parameters()).device
     users = sorted(user_profile_map.items(), key=lambda kv: kv[0])
     out = {}
     for start in range(0, len(users), 32):
         batch = users[start:start + 32]
-        encoded = _tokenize(tokenizer, [name for _, name in batch], 64, device)
-        vecs = _embed_encoded(model, encoded, "cls").cpu().numpy()
+        encoded, bound = _tokenize(tokenizer, [name for _, name in batch], 64, device)
+        vecs = _embed_encoded(model, encoded, "cls", bound, ragged).cpu().numpy()
         for (uid, _), v in zip(batch, vecs):
             out[uid] = v
     return out

@@ -31,6 +31,14 @@
 // LayerNorm is two-pass (mean, then centred squares), biased variance, eps inside the square root.
 // Every output element has one summation order that depends on neither B nor the row's tile position,
 // and nothing uses atomics, so a call is bitwise repeatable and batch-invariant.
+//
+// gr_bert_embed_ragged_f32 runs the same kernels in their RAGGED instantiation over rows [0, len_b) of each sequence
+// only (len_b: one past the last live position), packed at off[b] + s:
+//   be_len_kernel        a wave per sequence: len_b by a ballot per 64 positions.
+//   be_offsets_kernel    one workgroup: off = exclusive prefix sum of len, the total, the overflow flag.
+// The caller's row bound sizes the workspace and the grids; the total is read on the device, and a tile, wave or
+// query tile past it exits.  The sums' orders are the padded call's, so the kept rows and the pooled vectors have
+// its bits.  The padded instantiations take the row map (BeRows) and never read it.
 #include "gr_common.h"
 
 namespace gr {
@@ -43,17 +51,33 @@ constexpr int BE_KFLUSH = 8;               // 32-deep stages per fma chain: 256 
 constexpr int BE_QT = 128, BE_KT = 32;     // queries per workgroup, keys per streamed tile
 enum { BE_EPI_BIAS = 0, BE_EPI_GELU = 1, BE_EPI_RESID = 2 };
 
+// The ragged call's row map, in the workspace: len[b] kept rows of sequence b (one past its last live position),
+// off[b] their first packed row, total = off[B], flag != 0 when the mask held more rows than the caller's bound
+// (then every len is 0 and total is 0).  The padded kernels take it and never read it.
+struct BeRows {
+  const int32_t* len;
+  const int64_t* off;
+  const int64_t* total;
+  const int32_t* flag;
+};
+
 struct BeSeg {   // up to three [seg_n, K] weight matrices side by side, and their biases
   const float* w[3];
   const float* b[3];
 };
 
 // WM waves down the tile's rows (4 / WM across its columns), each owning TM x TN blocks of 32 x 32 outputs.
-template <int WM, int TM, int TN, int EPI>
+// RAGGED: the grid covers the caller's row bound (M_), the row count is rg.total[0]; a tile at or past it exits.
+template <int WM, int TM, int TN, int EPI, bool RAGGED>
 __global__ __launch_bounds__(BE_NT, 2) void be_gemm_kernel(const float* __restrict__ x, BeSeg sg, int seg_n,
                                                            const float* __restrict__ residual, float* __restrict__ y,
-                                                           int64_t M, int N, int K, int tiles_n) {
+                                                           int64_t M_, int N, int K, int tiles_n, BeRows rg) {
   constexpr int WN = 4 / WM, BM = 32 * WM * TM, BN = 32 * WN * TN;
+  int64_t M = M_;
+  if constexpr (RAGGED) {
+    M = rg.total[0];
+    if ((int64_t)(blockIdx.x / tiles_n) * BM >= M) return;
+  }
   __shared__ __attribute__((aligned(16))) float lds[2][(BM + BN) * BE_PITCH];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN, r = lane & 31, h = lane >> 5;
@@ -186,15 +210,26 @@ __device__ __forceinline__ void be_ln_row(float (&xv)[BE_MAX_H / 64], int lane, 
   }
 }
 
+// RAGGED: grid (sequence, four positions); position s < len[b] of sequence b is written at packed row off[b] + s.
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void be_embed_ln_kernel(const int64_t* __restrict__ ids,
                                                           const int64_t* __restrict__ type_ids,
                                                           const float* __restrict__ word, const float* __restrict__ pos,
                                                           const float* __restrict__ type, const float* __restrict__ lnw,
                                                           const float* __restrict__ lnb, float eps, int vocab,
-                                                          int type_vocab, int S, int H, int64_t M, float* __restrict__ out) {
+                                                          int type_vocab, int S, int H, int64_t M, float* __restrict__ out,
+                                                          BeRows rg) {
   const int lane = threadIdx.x & 63;
-  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= M) return;
+  int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);   // of ids
+  int64_t orow = row;                                           // of out
+  if constexpr (RAGGED) {
+    const int sp = (int)blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (sp >= rg.len[blockIdx.x]) return;
+    row = (int64_t)blockIdx.x * S + sp;
+    orow = rg.off[blockIdx.x] + sp;
+  } else if (row >= M) {
+    return;
+  }
   int64_t id = ids[row];
   id = id < 0 ? 0 : id >= vocab ? vocab - 1 : id;
   int64_t tt = type_ids != nullptr ? type_ids[row] : 0;
@@ -209,14 +244,17 @@ __global__ __launch_bounds__(256) void be_embed_ln_kernel(const int64_t* __restr
     const int c = lane + 64 * t;
     xv[t] = c < H ? (wr[c] + tr[c]) + pr[c] : 0.f;
   }
-  be_ln_row(xv, lane, H, lnw, lnb, eps, out + row * H);
+  be_ln_row(xv, lane, H, lnw, lnb, eps, out + orow * H);
 }
 
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void be_ln_kernel(const float* __restrict__ in, const float* __restrict__ lnw,
-                                                    const float* __restrict__ lnb, float eps, int H, int64_t M,
-                                                    float* __restrict__ out) {
+                                                    const float* __restrict__ lnb, float eps, int H, int64_t M_,
+                                                    float* __restrict__ out, BeRows rg) {
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  int64_t M = M_;
+  if constexpr (RAGGED) M = rg.total[0];
   if (row >= M) return;
   float xv[BE_MAX_H / 64];
 #pragma unroll
@@ -227,9 +265,13 @@ __global__ __launch_bounds__(256) void be_ln_kernel(const float* __restrict__ in
   be_ln_row(xv, lane, H, lnw, lnb, eps, out + row * H);
 }
 
-template <int HD>
+// RAGGED: the sequence's rows are the packed rows off[b] .. off[b] + len[b]; SL = len[b] takes S's place in the row
+// and key clamps and in the store guard, and a query tile at or past it exits.  The mask, the key tiles and their
+// order stay the padded call's (positions from len[b] on are dead), so the live rows get the padded call's bits.
+template <int HD, bool RAGGED>
 __global__ __launch_bounds__(256) void be_attn_kernel(const float* __restrict__ qkv, const int64_t* __restrict__ mask,
-                                                      float* __restrict__ ctx, int S, int NH, int nqt, float scale) {
+                                                      float* __restrict__ ctx, int S, int NH, int nqt, float scale,
+                                                      BeRows rg) {
   constexpr int P = HD + 4, NKC = HD / 8, NDB = HD / 32, LV = 2 * BE_KT * HD / 4 / 256;
   __shared__ __attribute__((aligned(16))) float kv[2][2 * BE_KT * P];
   __shared__ uint32_t livebits[BE_MAX_S / BE_KT];
@@ -240,7 +282,14 @@ __global__ __launch_bounds__(256) void be_attn_kernel(const float* __restrict__ 
   const int qt = blockIdx.x % nqt, head = (blockIdx.x / nqt) % NH;
   const int64_t b = blockIdx.x / (nqt * NH);
   const int Hd = NH * HD, ld = 3 * Hd;
-  const float* base = qkv + b * S * ld + head * HD;
+  int SL = S;                 // rows of this sequence
+  int64_t row0 = b * S;       // its first row in qkv and ctx
+  if constexpr (RAGGED) {
+    SL = rg.len[b];
+    row0 = rg.off[b];
+    if (qt * BE_QT >= SL) return;   // uniform over the workgroup, before any barrier
+  }
+  const float* base = qkv + row0 * ld + head * HD;
   const int nt = (S + BE_KT - 1) / BE_KT;
 
   // bit j of livebits[t]: position 32 t + j is a key; tiles[]: the tiles that hold one, ascending
@@ -261,8 +310,8 @@ __global__ __launch_bounds__(256) void be_attn_kernel(const float* __restrict__ 
   const int ntl = ntl_s;
 
   const int q0 = qt * BE_QT + 32 * wave;
-  const bool active = q0 < S;             // wave-uniform
-  const int qrow = q0 + r < S ? q0 + r : S - 1;   // rows past S read row S - 1, never stored
+  const bool active = q0 < SL;            // wave-uniform
+  const int qrow = q0 + r < SL ? q0 + r : SL - 1;   // rows past SL read row SL - 1, never stored
   f32x4 q[NKC];
 #pragma unroll
   for (int kc = 0; kc < NKC; ++kc) q[kc] = *reinterpret_cast<const f32x4*>(base + (int64_t)qrow * ld + 8 * kc + 4 * h);
@@ -273,7 +322,7 @@ __global__ __launch_bounds__(256) void be_attn_kernel(const float* __restrict__ 
     for (int i = 0; i < LV; ++i) {
       const int f = tid + 256 * i, mat = f / (BE_KT * HD / 4), rem = f % (BE_KT * HD / 4);
       const int row = rem / (HD / 4), c4 = rem % (HD / 4);
-      const int key = BE_KT * t + row < S ? BE_KT * t + row : S - 1;   // past S: finite, weighted 0
+      const int key = BE_KT * t + row < SL ? BE_KT * t + row : SL - 1;   // past SL: finite, weighted 0
       rk[i] = *reinterpret_cast<const f32x4*>(base + (int64_t)key * ld + (1 + mat) * Hd + 4 * c4);
     }
   };
@@ -360,28 +409,43 @@ __global__ __launch_bounds__(256) void be_attn_kernel(const float* __restrict__ 
 #pragma unroll
       for (int v = 0; v < 16; ++v) {
         const int qi = q0 + mfma32_row(v, h);
-        if (qi < S) ctx[(b * S + qi) * Hd + head * HD + 32 * d + r] = lv[v] > 0.f ? o[d][v] / lv[v] : 0.f;
+        if (qi < SL) ctx[(row0 + qi) * Hd + head * HD + 32 * d + r] = lv[v] > 0.f ? o[d][v] / lv[v] : 0.f;
       }
   }
 }
 
 // mode 0: no pooling; 1: mean over the live rows after position 0; 2: row 0.  A sequence with no live
 // key gets zeros in pooled and in hidden_out.  hid: the last hidden state (hidden_out itself when given).
+// RAGGED: hid holds packed rows (row i of the sequence at off[b] + i, i < len[b]; hidden_out is not used); NaN in
+// pooled when the flag is set.
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void be_pool_kernel(const float* hid, const int64_t* __restrict__ mask, int S, int H,
-                                                      int mode, float* __restrict__ pooled, float* hidden_out) {
+                                                      int mode, float* __restrict__ pooled, float* hidden_out, BeRows rg) {
   const int c = blockIdx.y * 256 + threadIdx.x;
   const int64_t b = blockIdx.x;
   const bool col = c < H;
+  int SL = S;
+  int64_t row0 = 0;   // the sequence's first packed row
+  if constexpr (RAGGED) {
+    if (rg.flag[0] != 0) {
+      if (col && mode != 0) pooled[b * H + c] = __builtin_nanf("");
+      return;
+    }
+    SL = rg.len[b];
+    row0 = rg.off[b];
+  }
   bool any = false;
   int cnt = 0;
   float acc = 0.f, lost = 0.f;   // compensated (Kahan) sum in position order: up to 511 rows
-  for (int i = 0; i < S; ++i) {
+  for (int i = 0; i < SL; ++i) {
     const bool lv = mask == nullptr || mask[b * S + i] != 0;
     any = any || lv;
     if (i >= 1 && lv) {
       ++cnt;
       if (mode == 1 && col) {
-        const float y = hid[(b * S + i) * H + c] - lost;
+        float y;
+        if constexpr (RAGGED) y = hid[(row0 + i) * H + c] - lost;
+        else y = hid[(b * S + i) * H + c] - lost;
         const float t = acc + y;
         lost = (t - acc) - y;
         acc = t;
@@ -390,9 +454,79 @@ __global__ __launch_bounds__(256) void be_pool_kernel(const float* hid, const in
   }
   if (!col) return;
   if (mode == 1) pooled[b * H + c] = acc / fmaxf((float)cnt, 1e-9f);
-  if (mode == 2) pooled[b * H + c] = any ? hid[b * S * H + c] : 0.f;
-  if (!any && hidden_out != nullptr)
-    for (int i = 0; i < S; ++i) hidden_out[(b * S + i) * H + c] = 0.f;
+  if constexpr (RAGGED) {
+    if (mode == 2) pooled[b * H + c] = any ? hid[row0 * H + c] : 0.f;
+  } else {
+    if (mode == 2) pooled[b * H + c] = any ? hid[b * S * H + c] : 0.f;
+    if (!any && hidden_out != nullptr)
+      for (int i = 0; i < S; ++i) hidden_out[(b * S + i) * H + c] = 0.f;
+  }
+}
+
+// len[b]: one past the last live position of sequence b (0: no live key; S with no mask).  A wave per sequence, a
+// ballot per 64 positions.
+__global__ __launch_bounds__(256) void be_len_kernel(const int64_t* __restrict__ mask, int64_t B, int S,
+                                                     int32_t* __restrict__ len) {
+  const int lane = threadIdx.x & 63;
+  const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= B) return;
+  int n = mask == nullptr ? S : 0;
+  if (mask != nullptr)
+    for (int s0 = 0; s0 < S; s0 += 64) {
+      const bool live = s0 + lane < S && mask[b * S + s0 + lane] != 0;
+      const uint64_t bits = __ballot(live);
+      if (bits != 0) n = s0 + 64 - __builtin_clzll(bits);
+    }
+  if (lane == 0) len[b] = n;
+}
+
+// One workgroup: off = exclusive prefix sum of len, off[B] = total = the packed row count.  When it exceeds
+// bound: every len and off 0, total 0, flag 1, and -1 in the caller's last offset.  No atomics.
+constexpr int BE_SCAN_NT = 1024;
+__global__ __launch_bounds__(BE_SCAN_NT) void be_offsets_kernel(int32_t* __restrict__ len, int64_t B, int64_t bound,
+                                                               int64_t* __restrict__ off, int64_t* __restrict__ total,
+                                                               int32_t* __restrict__ flag, int64_t* __restrict__ off_out) {
+  __shared__ int64_t part[BE_SCAN_NT];
+  __shared__ int64_t first[BE_SCAN_NT + 1];
+  const int tid = threadIdx.x;
+  const int64_t per = (B + BE_SCAN_NT - 1) / BE_SCAN_NT;
+  const int64_t lo = tid * per < B ? tid * per : B, hi = lo + per < B ? lo + per : B;
+  int64_t sum = 0;
+  for (int64_t b = lo; b < hi; ++b) sum += len[b];
+  part[tid] = sum;
+  __syncthreads();
+  if (tid < 64) {   // wave 0: sixteen parts per lane, a shuffle scan across the lanes
+    int64_t mine = 0;
+    for (int i = 0; i < BE_SCAN_NT / 64; ++i) mine += part[tid * (BE_SCAN_NT / 64) + i];
+    int64_t incl = mine;
+    for (int d = 1; d < 64; d <<= 1) {
+      const int64_t up = __shfl_up(incl, d, 64);
+      if (tid >= d) incl += up;
+    }
+    int64_t run = incl - mine;
+    for (int i = 0; i < BE_SCAN_NT / 64; ++i) {
+      first[tid * (BE_SCAN_NT / 64) + i] = run;
+      run += part[tid * (BE_SCAN_NT / 64) + i];
+    }
+    if (tid == 63) first[BE_SCAN_NT] = run;
+  }
+  __syncthreads();
+  const int64_t all = first[BE_SCAN_NT];
+  const bool over = all > bound;
+  int64_t run = first[tid];
+  for (int64_t b = lo; b < hi; ++b) {
+    const int32_t n = len[b];
+    const int64_t o = over ? 0 : run;
+    off[b] = o;
+    if (off_out != nullptr) off_out[b] = o;
+    if (over) len[b] = 0;
+    run += n;
+  }
+  if (tid == 0) {
+    off[B] = total[0] = over ? 0 : all;
+    flag[0] = over ? 1 : 0;
+    if (off_out != nullptr) off_out[B] = over ? -1 : all;
+  }
 }
 
 const char* be_check(const gr_bert_params* p, int64_t B, int S) {
@@ -421,8 +555,8 @@ struct BeLayout {   // float offsets into the workspace
   size_t x, t, qkv, ctx, ff, total;
 };
 
-BeLayout be_layout(const gr_bert_params* p, int64_t B, int S) {
-  const size_t M = (size_t)B * S, H = (size_t)p->hidden_size;
+BeLayout be_layout_rows(const gr_bert_params* p, size_t M) {
+  const size_t H = (size_t)p->hidden_size;
   BeLayout L;
   size_t o = 0;
   L.x = o;   o += align_up(M * H, 4);
@@ -434,11 +568,33 @@ BeLayout be_layout(const gr_bert_params* p, int64_t B, int S) {
   return L;
 }
 
+BeLayout be_layout(const gr_bert_params* p, int64_t B, int S) { return be_layout_rows(p, (size_t)B * S); }
+
+// The ragged call's workspace: be_layout_rows(rows), then off[B + 1] int64, total int64 + flag int32 (16 bytes),
+// len[B] int32, each on a 16-byte boundary.
+struct BeRagged {
+  int64_t rows;              // the caller's bound, at most B * S
+  size_t off, total, len;    // byte offsets
+  size_t bytes;
+};
+
+BeRagged be_ragged(const gr_bert_params* p, int64_t B, int S, int64_t rows_bound) {
+  BeRagged R;
+  R.rows = rows_bound < B * S ? (rows_bound > 0 ? rows_bound : 0) : B * S;
+  size_t o = be_layout_rows(p, (size_t)R.rows).total * sizeof(float);
+  R.off = o;   o += align_up((size_t)(B + 1) * sizeof(int64_t), 16);
+  R.total = o; o += 16;
+  R.len = o;   o += align_up((size_t)B * sizeof(int32_t), 16);
+  R.bytes = o + 16;
+  return R;
+}
+
 size_t be_bytes(const gr_bert_params* p, int64_t B, int S) { return be_layout(p, B, S).total * sizeof(float) + 16; }
 
-template <int EPI>
+// RAGGED: M is the caller's row bound (it sizes the grid and picks the tile), the row count is rg.total[0].
+template <int EPI, bool RAGGED>
 int be_gemm(const char* what, const float* x, const BeSeg& sg, int seg_n, const float* residual, float* y, int64_t M,
-            int N, int K, hipStream_t st) {
+            int N, int K, hipStream_t st, const BeRows& rg) {
   // Three tiles, the same bits from each.  A compute unit works through its workgroups at one MFMA rate
   // however many are resident, so a launch takes ceil(workgroups / compute units) rounds of one tile's
   // work: take the tile with the least rounds x tile area (bert-base at 4096 rows: q/k/v is 2.25 rounds of
@@ -458,10 +614,57 @@ int be_gemm(const char* what, const float* x, const BeSeg& sg, int seg_n, const 
   }
   const int tn = (N + tiles[pick].bn - 1) / tiles[pick].bn;
   const dim3 grid((unsigned)(((M + tiles[pick].bm - 1) / tiles[pick].bm) * tn));
-  if (pick == 0) be_gemm_kernel<2, 2, 2, EPI><<<grid, dim3(BE_NT), 0, st>>>(x, sg, seg_n, residual, y, M, N, K, tn);
-  else if (pick == 1) be_gemm_kernel<2, 1, 2, EPI><<<grid, dim3(BE_NT), 0, st>>>(x, sg, seg_n, residual, y, M, N, K, tn);
-  else be_gemm_kernel<4, 1, 3, EPI><<<grid, dim3(BE_NT), 0, st>>>(x, sg, seg_n, residual, y, M, N, K, tn);
+  if (pick == 0)
+    be_gemm_kernel<2, 2, 2, EPI, RAGGED><<<grid, dim3(BE_NT), 0, st>>>(x, sg, seg_n, residual, y, M, N, K, tn, rg);
+  else if (pick == 1)
+    be_gemm_kernel<2, 1, 2, EPI, RAGGED><<<grid, dim3(BE_NT), 0, st>>>(x, sg, seg_n, residual, y, M, N, K, tn, rg);
+  else
+    be_gemm_kernel<4, 1, 3, EPI, RAGGED><<<grid, dim3(BE_NT), 0, st>>>(x, sg, seg_n, residual, y, M, N, K, tn, rg);
   return check_launch(what);
+}
+
+// The encoder stack over M rows of X (RAGGED: M bounds the packed rows, rg.total[0] counts them), the last
+// LayerNorm into last: 7 launches per layer.
+template <bool RAGGED>
+int be_stack(const gr_bert_params* p, const int64_t* attention_mask, int64_t B, int S, int64_t M, float* ws,
+             const BeLayout& L, float* last, hipStream_t st, const BeRows& rg) {
+  const int H = p->hidden_size, I = p->intermediate_size, NH = p->num_heads, HD = p->head_dim;
+  float *X = ws + L.x, *T = ws + L.t, *QKV = ws + L.qkv, *CTX = ws + L.ctx, *FF = ws + L.ff;
+  const unsigned row_blocks = (unsigned)((M + 3) / 4);
+  const float scale = sas_scale(HD);
+  const int nqt = (S + BE_QT - 1) / BE_QT;
+  for (int l = 0; l < p->num_layers; ++l) {
+    const float* const* w = p->layer[l];
+    const BeSeg qkv_w = {{w[0], w[2], w[4]}, {w[1], w[3], w[5]}};
+    if (int rc = be_gemm<BE_EPI_BIAS, RAGGED>("bert q/k/v", X, qkv_w, H, nullptr, QKV, M, 3 * H, H, st, rg)) return rc;
+    const dim3 ag((unsigned)(B * NH * nqt));
+    if (HD == 64)
+      be_attn_kernel<64, RAGGED><<<ag, dim3(256), 0, st>>>(QKV, attention_mask, CTX, S, NH, nqt, scale, rg);
+    else
+      be_attn_kernel<32, RAGGED><<<ag, dim3(256), 0, st>>>(QKV, attention_mask, CTX, S, NH, nqt, scale, rg);
+    if (int rc = check_launch("be_attn_kernel")) return rc;
+    const BeSeg ao = {{w[6], nullptr, nullptr}, {w[7], nullptr, nullptr}};
+    if (int rc = be_gemm<BE_EPI_RESID, RAGGED>("bert attention output + residual", CTX, ao, H, X, T, M, H, H, st, rg))
+      return rc;
+    be_ln_kernel<RAGGED><<<dim3(row_blocks), dim3(256), 0, st>>>(T, w[8], w[9], p->eps, H, M, X, rg);
+    if (int rc = check_launch("be_ln_kernel")) return rc;
+    const BeSeg inter = {{w[10], nullptr, nullptr}, {w[11], nullptr, nullptr}};
+    if (int rc = be_gemm<BE_EPI_GELU, RAGGED>("bert intermediate + gelu", X, inter, I, nullptr, FF, M, I, H, st, rg))
+      return rc;
+    const BeSeg outw = {{w[12], nullptr, nullptr}, {w[13], nullptr, nullptr}};
+    if (int rc = be_gemm<BE_EPI_RESID, RAGGED>("bert output + residual", FF, outw, H, X, T, M, H, I, st, rg)) return rc;
+    be_ln_kernel<RAGGED><<<dim3(row_blocks), dim3(256), 0, st>>>(T, w[14], w[15], p->eps, H, M,
+                                                                 l + 1 == p->num_layers ? last : X, rg);
+    if (int rc = check_launch("be_ln_kernel")) return rc;
+  }
+  return GR_OK;
+}
+
+bool be_weights_ok(const gr_bert_params* p) {
+  bool ok = p->word && p->position && p->token_type && p->emb_ln_w && p->emb_ln_b;
+  for (int l = 0; ok && l < p->num_layers; ++l)
+    for (int i = 0; i < 16; ++i) ok = ok && p->layer[l][i] && aligned16(p->layer[l][i]);
+  return ok;
 }
 
 }  // namespace
@@ -490,47 +693,81 @@ extern "C" int gr_bert_embed_f32(const gr_bert_params* p, const int64_t* input_i
   if (pooling == GR_BERT_POOL_NONE && !hidden_out)
     return fail(GR_ERR_ARG, who + "hidden_out is null and pooling is GR_BERT_POOL_NONE: nothing to compute");
   if (hidden_out && !aligned16(hidden_out)) return fail(GR_ERR_ARG, who + "hidden_out must be 16-byte aligned");
-  bool ok = p->word && p->position && p->token_type && p->emb_ln_w && p->emb_ln_b;
-  for (int l = 0; ok && l < p->num_layers; ++l)
-    for (int i = 0; i < 16; ++i) ok = ok && p->layer[l][i] && aligned16(p->layer[l][i]);
-  if (!ok) return fail(GR_ERR_ARG, who + "a weight pointer is null or not 16-byte aligned");
+  if (!be_weights_ok(p)) return fail(GR_ERR_ARG, who + "a weight pointer is null or not 16-byte aligned");
 
-  const int H = p->hidden_size, I = p->intermediate_size, NH = p->num_heads, HD = p->head_dim;
+  const int H = p->hidden_size;
   const int64_t M = B * S;
   const BeLayout L = be_layout(p, B, S);
   float* ws = static_cast<float*>(workspace);
-  float *X = ws + L.x, *T = ws + L.t, *QKV = ws + L.qkv, *CTX = ws + L.ctx, *FF = ws + L.ff;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const unsigned row_blocks = (unsigned)((M + 3) / 4);
-  const float scale = sas_scale(HD);
-  const int nqt = (S + BE_QT - 1) / BE_QT;
+  const BeRows none = {nullptr, nullptr, nullptr, nullptr};
 
-  be_embed_ln_kernel<<<dim3(row_blocks), dim3(256), 0, st>>>(input_ids, token_type_ids, p->word, p->position,
-                                                              p->token_type, p->emb_ln_w, p->emb_ln_b, p->eps,
-                                                              p->vocab_size, p->type_vocab_size, S, H, M, X);
+  be_embed_ln_kernel<false><<<dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st>>>(
+      input_ids, token_type_ids, p->word, p->position, p->token_type, p->emb_ln_w, p->emb_ln_b, p->eps, p->vocab_size,
+      p->type_vocab_size, S, H, M, ws + L.x, none);
   if (int rc = check_launch("be_embed_ln_kernel")) return rc;
-  float* last = hidden_out ? hidden_out : X;
-  for (int l = 0; l < p->num_layers; ++l) {
-    const float* const* w = p->layer[l];
-    const BeSeg qkv_w = {{w[0], w[2], w[4]}, {w[1], w[3], w[5]}};
-    if (int rc = be_gemm<BE_EPI_BIAS>("bert q/k/v", X, qkv_w, H, nullptr, QKV, M, 3 * H, H, st)) return rc;
-    const dim3 ag((unsigned)(B * NH * nqt));
-    if (HD == 64) be_attn_kernel<64><<<ag, dim3(256), 0, st>>>(QKV, attention_mask, CTX, S, NH, nqt, scale);
-    else be_attn_kernel<32><<<ag, dim3(256), 0, st>>>(QKV, attention_mask, CTX, S, NH, nqt, scale);
-    if (int rc = check_launch("be_attn_kernel")) return rc;
-    const BeSeg ao = {{w[6], nullptr, nullptr}, {w[7], nullptr, nullptr}};
-    if (int rc = be_gemm<BE_EPI_RESID>("bert attention output + residual", CTX, ao, H, X, T, M, H, H, st)) return rc;
-    be_ln_kernel<<<dim3(row_blocks), dim3(256), 0, st>>>(T, w[8], w[9], p->eps, H, M, X);
-    if (int rc = check_launch("be_ln_kernel")) return rc;
-    const BeSeg inter = {{w[10], nullptr, nullptr}, {w[11], nullptr, nullptr}};
-    if (int rc = be_gemm<BE_EPI_GELU>("bert intermediate + gelu", X, inter, I, nullptr, FF, M, I, H, st)) return rc;
-    const BeSeg outw = {{w[12], nullptr, nullptr}, {w[13], nullptr, nullptr}};
-    if (int rc = be_gemm<BE_EPI_RESID>("bert output + residual", FF, outw, H, X, T, M, H, I, st)) return rc;
-    be_ln_kernel<<<dim3(row_blocks), dim3(256), 0, st>>>(T, w[14], w[15], p->eps, H, M,
-                                                         l + 1 == p->num_layers ? last : X);
-    if (int rc = check_launch("be_ln_kernel")) return rc;
-  }
-  be_pool_kernel<<<dim3((unsigned)B, (unsigned)((H + 255) / 256)), dim3(256), 0, st>>>(last, attention_mask, S, H, pooling,
-                                                                                       pooled_out, hidden_out);
+  float* last = hidden_out ? hidden_out : ws + L.x;
+  if (int rc = be_stack<false>(p, attention_mask, B, S, M, ws, L, last, st, none)) return rc;
+  be_pool_kernel<false><<<dim3((unsigned)B, (unsigned)((H + 255) / 256)), dim3(256), 0, st>>>(
+      last, attention_mask, S, H, pooling, pooled_out, hidden_out, none);
+  return check_launch("be_pool_kernel");
+}
+
+extern "C" size_t gr_bert_embed_ragged_workspace_bytes(const gr_bert_params* p, int64_t B, int32_t S,
+                                                       int64_t rows_bound) {
+  if (gr::be_check(p, B, S) || (B > 0 && rows_bound < 1)) return 0;
+  return gr::be_ragged(p, B, S, rows_bound).bytes;
+}
+
+extern "C" int gr_bert_embed_ragged_f32(const gr_bert_params* p, const int64_t* input_ids,
+                                        const int64_t* attention_mask, const int64_t* token_type_ids, int64_t B,
+                                        int32_t S, int64_t rows_bound, int32_t pooling, float* pooled_out,
+                                        float* hidden_rows_out, int64_t* row_offsets_out, void* workspace,
+                                        size_t workspace_bytes, void* stream) {
+  using namespace gr;
+  clear_error();
+  const std::string who = "gr_bert_embed_ragged_f32: ";
+  if (const char* why = be_check(p, B, S)) return fail(!p || B < 0 ? GR_ERR_ARG : GR_ERR_UNSUPPORTED, who + why);
+  if (B > 0 && rows_bound < 1) return fail(GR_ERR_ARG, who + "rows_bound must be at least 1");
+  if (pooling != GR_BERT_POOL_NONE && pooling != GR_BERT_POOL_MEAN_NO_CLS && pooling != GR_BERT_POOL_CLS)
+    return fail(GR_ERR_ARG, who + "pooling must be GR_BERT_POOL_NONE, _MEAN_NO_CLS or _CLS");
+  if (B == 0) return GR_OK;
+  const BeRagged R = be_ragged(p, B, S, rows_bound);
+  if (!workspace || workspace_bytes < R.bytes || !aligned16(workspace))
+    return fail(GR_ERR_WORKSPACE,
+                who + "workspace missing, misaligned or smaller than gr_bert_embed_ragged_workspace_bytes");
+  if (!input_ids) return fail(GR_ERR_ARG, who + "input_ids is null");
+  if (pooling != GR_BERT_POOL_NONE && !pooled_out) return fail(GR_ERR_ARG, who + "pooled_out is null");
+  if (pooling == GR_BERT_POOL_NONE && (!hidden_rows_out || !row_offsets_out))
+    return fail(GR_ERR_ARG, who + "hidden_rows_out or row_offsets_out is null and pooling is GR_BERT_POOL_NONE: "
+                                  "nothing to compute");
+  if (hidden_rows_out && !aligned16(hidden_rows_out))
+    return fail(GR_ERR_ARG, who + "hidden_rows_out must be 16-byte aligned");
+  if (!be_weights_ok(p)) return fail(GR_ERR_ARG, who + "a weight pointer is null or not 16-byte aligned");
+
+  const int H = p->hidden_size;
+  const BeLayout L = be_layout_rows(p, (size_t)R.rows);
+  float* ws = static_cast<float*>(workspace);
+  char* wb = static_cast<char*>(workspace);
+  int64_t* off = reinterpret_cast<int64_t*>(wb + R.off);
+  int64_t* total = reinterpret_cast<int64_t*>(wb + R.total);
+  int32_t* flag = reinterpret_cast<int32_t*>(wb + R.total + sizeof(int64_t));
+  int32_t* len = reinterpret_cast<int32_t*>(wb + R.len);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const BeRows rg = {len, off, total, flag};
+
+  be_len_kernel<<<dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st>>>(attention_mask, B, S, len);
+  if (int rc = check_launch("be_len_kernel")) return rc;
+  be_offsets_kernel<<<dim3(1), dim3(BE_SCAN_NT), 0, st>>>(len, B, R.rows, off, total, flag, row_offsets_out);
+  if (int rc = check_launch("be_offsets_kernel")) return rc;
+  // B x ceil(S / 4) <= 65536 x 128 workgroups
+  be_embed_ln_kernel<true><<<dim3((unsigned)B, (unsigned)((S + 3) / 4)), dim3(256), 0, st>>>(
+      input_ids, token_type_ids, p->word, p->position, p->token_type, p->emb_ln_w, p->emb_ln_b, p->eps, p->vocab_size,
+      p->type_vocab_size, S, H, R.rows, ws + L.x, rg);
+  if (int rc = check_launch("be_embed_ln_kernel")) return rc;
+  float* last = hidden_rows_out ? hidden_rows_out : ws + L.x;
+  if (int rc = be_stack<true>(p, attention_mask, B, S, R.rows, ws, L, last, st, rg)) return rc;
+  be_pool_kernel<true><<<dim3((unsigned)B, (unsigned)((H + 255) / 256)), dim3(256), 0, st>>>(
+      last, attention_mask, S, H, pooling, pooled_out, nullptr, rg);
   return check_launch("be_pool_kernel");
 }

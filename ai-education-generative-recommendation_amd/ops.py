@@ -2203,6 +2203,12 @@ class BertBinding:
             n = self._ws[(B, S)] = L.lib().gr_bert_embed_workspace_bytes(self.ref, B, S)
         return n
 
+    def ragged_workspace_bytes(self, B, S, rows_bound):
+        n = self._ws.get((B, S, rows_bound))
+        if n is None:
+            n = self._ws[(B, S, rows_bound)] = L.lib().gr_bert_embed_ragged_workspace_bytes(self.ref, B, S, rows_bound)
+        return n
+
 
 def _bert_ids(name, t, B, S):
     L.require_gpu(t)
@@ -2246,3 +2252,47 @@ def bert_embed(binding, input_ids, attention_mask=None, token_type_ids=None, poo
     if pooled is None:
         return hidden
     return (pooled, hidden) if with_hidden else pooled
+
+
+def bert_embed_ragged(binding, input_ids, attention_mask=None, token_type_ids=None, pooling="mean_no_cls", rows_bound=None,
+                      with_hidden=False):
+    """``gr_bert_embed_ragged_f32``: ``bert_embed`` over rows ``[0, len_b)`` of each sequence only (``len_b``: one past
+    its last live position), packed; the pooled vectors and the kept rows have ``bert_embed``'s bits.  ``rows_bound``:
+    an upper bound on the packed row count ``sum(len_b)`` -- ``bert_embed.row_bound`` gives it for a host-side mask;
+    None means B * S, which is always safe; 0 (no sequence has a live key) is passed on as 1.  Nothing synchronises: the row count stays on the device, and a bound
+    below it shows as NaN in every pooled element and -1 in the last offset.
+    -> pooled [B, H], or with ``with_hidden`` (pooled, hidden_rows [rows_bound, H], row_offsets [B + 1] int64):
+    ``hidden_rows[row_offsets[b] + s]`` is position s of sequence b, rows from ``row_offsets[B]`` on are unset.
+    ``pooling=None`` returns (hidden_rows, row_offsets)."""
+    if pooling not in BERT_POOLINGS:
+        raise ValueError(f"pooling={pooling!r} must be 'mean_no_cls', 'cls' or None")
+    mode = BERT_POOLINGS[pooling]
+    if input_ids.dim() != 2:
+        raise RuntimeError(f"bert_embed_ragged takes [B, S] token ids, got {tuple(input_ids.shape)}")
+    B, S = input_ids.shape
+    input_ids = _bert_ids("input_ids", input_ids, B, S)
+    bert_check(binding.cfg, S, B)
+    if attention_mask is not None:
+        attention_mask = _bert_ids("attention_mask", attention_mask, B, S)
+    if token_type_ids is not None:
+        token_type_ids = _bert_ids("token_type_ids", token_type_ids, B, S)
+    if rows_bound is not None and int(rows_bound) < 0:
+        raise ValueError(f"rows_bound={rows_bound} must not be negative")
+    rows = B * S if rows_bound is None else max(min(int(rows_bound), B * S), min(B, 1))   # the C entry takes >= 1
+    dev = input_ids.device
+    H = binding.params.hidden_size
+    want_hidden = with_hidden or mode == L.GR_BERT_POOL_NONE
+    pooled = torch.empty((B, H), dtype=torch.float32, device=dev) if mode != L.GR_BERT_POOL_NONE else None
+    hidden = torch.empty((rows, H), dtype=torch.float32, device=dev) if want_hidden else None
+    offsets = torch.zeros((B + 1,), dtype=torch.int64, device=dev) if want_hidden else None
+    if B > 0:
+        nbytes = binding.ragged_workspace_bytes(B, S, rows)
+        wsp = L.workspace(nbytes, dev)
+        with L.on(dev):
+            L.check(L.lib().gr_bert_embed_ragged_f32(binding.ref, L.ptr(input_ids), L.ptr(attention_mask),
+                                                     L.ptr(token_type_ids), B, S, rows, mode, L.ptr(pooled),
+                                                     L.ptr(hidden), L.ptr(offsets), L.ptr(wsp), nbytes,
+                                                     L.stream_of(dev)), "gr_bert_embed_ragged_f32")
+    if pooled is None:
+        return hidden, offsets
+    return (pooled, hidden, offsets) if with_hidden else pooled

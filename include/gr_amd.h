@@ -927,6 +927,38 @@ int gr_bert_embed_f32(const gr_bert_params* p, const int64_t* input_ids, const i
                       const int64_t* token_type_ids, int64_t B, int32_t S, int32_t pooling, float* pooled_out,
                       float* hidden_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same encoder over the rows that matter: gr_bert_embed_ragged_f32 keeps rows [0, len_b) of each
+ * sequence, len_b = 1 + its last live position (0 for a sequence with no live key), packed one sequence
+ * after the other: row s of sequence b is packed row off[b] + s, off = the exclusive prefix sum of len.
+ * Holes inside [0, len_b) stay in as masked rows, position 0 is kept whenever a key is live.  The inputs
+ * are gr_bert_embed_f32's [B, S] arrays (same envelope, same clamping, NULL mask = all live), the math
+ * is the math above, and every kept row and every pooled vector has the bits gr_bert_embed_f32 gives
+ * for the same inputs: a GEMM row's bits do not depend on where the row sits, the attention visits the
+ * same key tiles in the same order, and the pooling adds the same rows in position order.
+ *
+ * rows_bound is the caller's upper bound on off[B] (a host-side mask gives it exactly; B * S is always
+ * safe; above B * S counts as B * S; below 1 with B > 0 is GR_ERR_ARG).  It sizes the workspace and every
+ * grid; the true count is computed on the device and read there, a workgroup or wave whose rows lie
+ * past it exits, and the call never synchronises or reads anything back.  If the mask holds more rows
+ * than rows_bound the host cannot know, so the call still returns GR_OK: the offsets kernel sets every
+ * length to 0 and a flag, no later kernel touches a row, every element of pooled_out is NaN and
+ * row_offsets_out is all zeros with -1 in its last slot.
+ *
+ * Launches: 2 (lengths: a wave per sequence; offsets: one workgroup, no atomics) + 2 + 7 num_layers.
+ *   pooled_out[B, H] (NULL only with GR_BERT_POOL_NONE; zeros for a sequence with no live key)
+ *   hidden_rows_out[rows_bound, H] 16-byte aligned or NULL: packed rows of the last hidden state, rows
+ *   from off[B] on are left as they were; row_offsets_out[B + 1] = off, or NULL.  GR_BERT_POOL_NONE needs both.
+ * Argument checks, error codes and their order are gr_bert_embed_f32's; messages start with
+ * "gr_bert_embed_ragged_f32: ".  B = 0: GR_OK, no launch.
+ * workspace: gr_bert_embed_ragged_workspace_bytes(p, B, S, rows_bound) bytes, 16-byte aligned (0 outside
+ * the envelope or with rows_bound < 1 and B > 0), with R = min(rows_bound, B * S):
+ *   4 R (6 H + intermediate_size) + up16(8 (B + 1)) + 16 + up16(4 B) + 16,  up16 = rounded up to 16. */
+size_t gr_bert_embed_ragged_workspace_bytes(const gr_bert_params* p, int64_t B, int32_t S, int64_t rows_bound);
+int gr_bert_embed_ragged_f32(const gr_bert_params* p, const int64_t* input_ids, const int64_t* attention_mask,
+                             const int64_t* token_type_ids, int64_t B, int32_t S, int64_t rows_bound,
+                             int32_t pooling, float* pooled_out, float* hidden_rows_out,
+                             int64_t* row_offsets_out, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,6 +5,13 @@ torch on the same GPU in the same process with the same weights.
 
     python scripts/time_bert_embed.py [--out profiles/r21/bert_embed.txt]
     rocprofv3 --kernel-trace --stats ... -- python scripts/time_bert_embed.py --only-kernels   (per-kernel shares)
+    python scripts/time_bert_embed.py --ragged [--out profiles/r23/bert_embed_ragged.txt]
+    python scripts/time_bert_embed.py --padded-only       (the padded call alone: for a build of another commit)
+
+``--ragged``: the ragged entry (``embed(..., ragged=True)``: only the rows up to each sequence's last live position)
+next to the padded call on the same inputs in the same process, for two length distributions -- one sequence of S
+and the rest uniform on S/2..S, or on 8..S -- with the exact row bound (a host-side mask) and with the bound B * S
+(a device-side mask: oversized grids that exit on the device's row count).
 
 Each call is timed by its own pair of events after a warm-up; the figure is the median over ``--reps`` calls with
 the minimum, the quartiles and the maximum beside it.  The fp32 floor is the multiply-adds the shapes need (every
@@ -29,13 +36,14 @@ CONFIG = dict(vocab_size=30522, hidden_size=768, num_hidden_layers=12, num_atten
 FP32_MATRIX_FLOPS = 157e12
 
 
-def inputs(B, S, dev):
-    """Right-padded sequences, the first of full length, the others uniform on S/2..S."""
+def inputs(B, S, dev, low=None):
+    """Right-padded sequences, the first of full length, the others uniform on low..S (S/2..S by default)."""
     rng = np.random.default_rng(0)
     ids = np.zeros((B, S), np.int64)
     mask = np.zeros((B, S), np.int64)
+    low = S // 2 if low is None else low
     for b in range(B):
-        n = S if b == 0 else int(rng.integers(S // 2, S + 1))
+        n = S if b == 0 else int(rng.integers(low, S + 1))
         ids[b, :n] = rng.integers(1, CONFIG["vocab_size"], n)
         mask[b, :n] = 1
     return torch.from_numpy(ids).to(dev), torch.from_numpy(mask).to(dev)
@@ -80,12 +88,42 @@ def seeded_model(dev):
     return model.to(dev).eval()
 
 
+def ragged_report(model, a, dev):
+    """The padded call, the ragged call with the exact bound and the ragged call with the bound B * S, per shape and
+    length distribution, interleaved in one process on the same weights."""
+    res = {"config": {k: CONFIG[k] for k in ("hidden_size", "num_hidden_layers", "num_attention_heads", "intermediate_size")},
+           "device": torch.cuda.get_device_name(0), "timing": f"one pair of events per call, median of {a.reps} calls "
+           "after 5 warm-up calls, quartiles beside it", "points": []}
+    for S in a.positions:
+        for name, low in (("one of S, the others uniform on S/2..S", None), ("one of S, the others uniform on 8..S", 8)):
+            ids, mask = inputs(a.batch, S, dev, low)
+            lens = mask.sum(1).cpu().numpy().astype(np.int64)              # right padding: the length is the live count
+            exact = gr_amd.bert_embed.row_bound(mask.cpu())
+            assert exact == int(lens.sum())
+            row = {"B": a.batch, "S": S, "lengths": name, "kept_rows": exact,
+                   "kept_row_share": exact / (a.batch * S), "attention_share": float((lens ** 2).sum()) / (a.batch * S * S)}
+            padded = lambda: model.embed(ids, mask)
+            ragged = lambda: model.embed(ids, mask, ragged=True, rows_bound=exact)
+            loose = lambda: model.embed(ids, mask, ragged=True)
+            row["same_bits"] = bool(torch.equal(padded(), ragged()) and torch.equal(padded(), loose()))
+            row["padded"] = timed(padded, a.reps, 5)
+            row["ragged_exact_bound"] = timed(ragged, a.reps, 5)
+            row["ragged_bound_B_S"] = timed(loose, a.reps, 5)
+            row["padded_again"] = timed(padded, a.reps, 5)                  # the drift of the run itself
+            row["ragged_over_padded"] = row["ragged_exact_bound"]["median_ms"] / row["padded"]["median_ms"]
+            row["ragged_bound_B_S_over_padded"] = row["ragged_bound_B_S"]["median_ms"] / row["padded"]["median_ms"]
+            res["points"].append(row)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--positions", type=int, nargs="+", default=[128, 512])
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--only-kernels", action="store_true", help="a few calls of the kernels alone (for a kernel trace)")
+    ap.add_argument("--ragged", action="store_true", help="the ragged entry next to the padded call")
+    ap.add_argument("--padded-only", action="store_true", help="the padded call alone")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -93,9 +131,25 @@ def main():
     if a.only_kernels:
         for S in a.positions:
             ids, mask = inputs(a.batch, S, dev)
+            exact = gr_amd.bert_embed.row_bound(mask.cpu()) if a.ragged else None
             for _ in range(5):
-                model.embed(ids, mask)
+                model.embed(ids, mask, ragged=True, rows_bound=exact) if a.ragged else model.embed(ids, mask)
         torch.cuda.synchronize()
+        return
+    if a.ragged or a.padded_only:
+        if a.ragged:
+            res = ragged_report(model, a, dev)
+        else:
+            res = {"device": torch.cuda.get_device_name(0), "shapes": []}
+            for S in a.positions:
+                ids, mask = inputs(a.batch, S, dev)
+                res["shapes"].append({"B": a.batch, "S": S, "padded": timed(lambda: model.embed(ids, mask), a.reps, 5)})
+        line = json.dumps(res, indent=1)
+        print(line)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
         return
     sd = {k: v.detach() for k, v in model.state_dict().items()}
     res = {"config": {k: CONFIG[k] for k in ("hidden_size", "num_hidden_layers", "num_attention_heads", "intermediate_size")},
