@@ -94,6 +94,12 @@ class BertParams(ctypes.Structure):
                [("layer", (_vp * 16) * GR_BERT_MAX_LAYERS)]
 
 
+class BertBf16Params(ctypes.Structure):
+    """Mirror of ``gr_bert_bf16_params`` (include/gr_amd.h): ``matrix`` bf16, everything else fp32."""
+    _fields_ = BertParams._fields_[:-1] + [("matrix", (_vp * 6) * GR_BERT_MAX_LAYERS),
+                                           ("vector", (_vp * 10) * GR_BERT_MAX_LAYERS)]
+
+
 # (name, restype, argtypes) for every entry point of include/gr_amd.h
 SIGNATURES = {
     "gr_version": (ctypes.c_char_p, []),
@@ -214,6 +220,12 @@ SIGNATURES = {
     "gr_bert_embed_ragged_workspace_bytes": (_sz, [ctypes.POINTER(BertParams), _i64, _i32, _i64]),
     "gr_bert_embed_ragged_f32": (ctypes.c_int, [ctypes.POINTER(BertParams), _vp, _vp, _vp, _i64, _i32, _i64, _i32, _vp,
                                                 _vp, _vp, _vp, _sz, _vp]),
+    "gr_bert_embed_bf16_workspace_bytes": (_sz, [ctypes.POINTER(BertBf16Params), _i64, _i32]),
+    "gr_bert_embed_bf16": (ctypes.c_int, [ctypes.POINTER(BertBf16Params), _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp,
+                                          _sz, _vp]),
+    "gr_bert_embed_ragged_bf16_workspace_bytes": (_sz, [ctypes.POINTER(BertBf16Params), _i64, _i32, _i64]),
+    "gr_bert_embed_ragged_bf16": (ctypes.c_int, [ctypes.POINTER(BertBf16Params), _vp, _vp, _vp, _i64, _i32, _i64, _i32,
+                                                 _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -1,6 +1,7 @@
 """BERT text encoder (the ``AutoModel.from_pretrained(...)`` pass of T5/item_encode.py, major-encode/bert_emb.py and
 Baseline/Rec.py): embeddings, the post-LN encoder stack and the reference's two poolings -- inference only, fp32,
-on the gfx950 kernels of csrc/bert_embed.hip.
+on the gfx950 kernels of csrc/bert_embed.hip; ``embed(..., precision="bf16")`` opts into bf16 GEMM operands with
+fp32 accumulation (float32 results; the contract is in include/gr_amd.h).
 
 ``BertEncoder(config)`` takes a dict or any object with HF's ``BertConfig`` field names and holds ``BertModel``'s
 parameter tree under ``BertModel``'s names (``embeddings.word_embeddings.weight``,
@@ -113,6 +114,8 @@ class BertEncoder(nn.Module):
         self.pooler = _Dense(cfg["hidden_size"], cfg["hidden_size"])
         self._binding = None
         self._binding_key = None
+        self._binding_bf16 = None
+        self._binding_bf16_key = None
 
     def load_state_dict(self, state_dict, strict=True, **kw):
         """``BertModel``'s state dict, strictly; the ``position_ids`` / ``token_type_ids`` buffers that older
@@ -129,6 +132,26 @@ class BertEncoder(nn.Module):
             self._binding_key = key
         return self._binding
 
+    def binding_bf16(self):
+        """The bf16 precision's binding (``ops.BertBf16Binding``: a snapshot of the six matrices per layer rounded to
+        bf16), rebuilt when a parameter's storage pointer or its ``_version`` changes -- so after an in-place update
+        or a ``load_state_dict`` the next call rounds the new weights."""
+        tensors = self.state_dict(keep_vars=True)
+        key = tuple((t.data_ptr(), t._version) for t in tensors.values())
+        if self._binding_bf16 is None or key != self._binding_bf16_key:
+            self._binding_bf16 = ops.BertBf16Binding(self.config, {k: v.detach() for k, v in tensors.items()})
+            self._binding_bf16_key = key
+        return self._binding_bf16
+
+    def _binding_for(self, precision):
+        if precision == "fp32":
+            return self.binding()
+        if precision == "bf16":
+            return self.binding_bf16()
+        if precision == "fp16":
+            raise ValueError("precision='fp16' is not built: 'fp32' or 'bf16'")
+        raise ValueError(f"precision={precision!r} must be 'fp32' or 'bf16'")
+
     def _refuse_training(self):
         if self.training and torch.is_grad_enabled():
             raise NotImplementedError("the BERT encoder's training (its backward) is not built: call it under "
@@ -144,7 +167,7 @@ class BertEncoder(nn.Module):
             return BertOutput(ops.bert_embed(self.binding(), input_ids, attention_mask, token_type_ids, pooling=None))
 
     def embed(self, input_ids, attention_mask=None, token_type_ids=None, pooling="mean_no_cls", ragged=False,
-              rows_bound=None):
+              rows_bound=None, precision="fp32"):
         """-> [B, H] in one C call.  ``"mean_no_cls"``: ``(hidden * mask)[:, 1:].sum(1) / mask[:, 1:].sum(-1)
         .clamp(min=1e-9)`` (major-encode/bert_emb.py:160-165), which is T5/item_encode.py:74-75 for every sequence
         with a live token after position 0; a sequence with none returns 0 where item_encode.py's unclamped division
@@ -153,15 +176,20 @@ class BertEncoder(nn.Module):
 
         ``ragged=True``: the same bits from the ragged entry, which computes only the rows up to each sequence's last
         live position.  ``rows_bound`` is an upper bound on their count (``row_bound(mask)`` of a host-side mask
-        gives it exactly); None means B * S, which is always safe.  Neither form synchronises."""
+        gives it exactly); None means B * S, which is always safe.  Neither form synchronises.
+
+        ``precision="bf16"``: the opt-in bf16 precision -- bf16 GEMM operands with fp32 accumulation, fp32 epilogues,
+        LayerNorms, softmax and pooling, a float32 result (the contract is in include/gr_amd.h); ``"fp32"``, the
+        default, is the call as it always was.  ``forward`` is fp32 only."""
         self._refuse_training()
         if pooling not in ("mean_no_cls", "cls"):
             raise ValueError(f"pooling={pooling!r} must be 'mean_no_cls' or 'cls'")
         with torch.no_grad():
+            binding = self._binding_for(precision)             # ValueError, naming the argument, for any other string
             if ragged:
-                return ops.bert_embed_ragged(self.binding(), input_ids, attention_mask, token_type_ids, pooling=pooling,
+                return ops.bert_embed_ragged(binding, input_ids, attention_mask, token_type_ids, pooling=pooling,
                                              rows_bound=rows_bound)
-            return ops.bert_embed(self.binding(), input_ids, attention_mask, token_type_ids, pooling=pooling)
+            return ops.bert_embed(binding, input_ids, attention_mask, token_type_ids, pooling=pooling)
 
 
 def row_bound(attention_mask, S=None):
@@ -193,43 +221,44 @@ def _tokenize(tokenizer, texts, max_length, device):
     return {k: v.to(device) for k, v in encoded.items()}, bound
 
 
-def _embed_encoded(model, encoded, pooling, bound, ragged):
+def _embed_encoded(model, encoded, pooling, bound, ragged, precision="fp32"):
     """The ragged entry when it has rows to leave out, the padded one otherwise: the same bits from both."""
     ids = encoded["input_ids"]
     ragged = ragged and bound < ids.shape[0] * ids.shape[1]
     return model.embed(ids, encoded.get("attention_mask"), encoded.get("token_type_ids"), pooling=pooling,
-                       ragged=ragged, rows_bound=bound if ragged else None)
+                       ragged=ragged, rows_bound=bound if ragged else None, precision=precision)
 
 
 @torch.no_grad()
-def encode_texts(texts, tokenizer, model, device, batch_size, max_length, *, ragged=True):
+def encode_texts(texts, tokenizer, model, device, batch_size, max_length, *, ragged=True, precision="fp32"):
     """The item pass (T5/item_encode.py:59-78, major-encode/bert_emb.py:131-168): batches of ``batch_size`` texts,
     tokenized with padding to the batch's longest and truncation at ``max_length``, mean-pooled without [CLS] ->
     float32 array [len(texts), H].  A text with no live token after position 0 gives a zero row.  ``ragged``: batches
     with padding go through the ragged entry with the row count taken from the tokenizer's host-side mask (the same
-    bits, less work); False keeps every batch on the padded entry."""
+    bits, less work); False keeps every batch on the padded entry.  ``precision``: ``embed``'s."""
     model.eval()
     device = torch.device(device)
     embs = []
     for start in range(0, len(texts), batch_size):
         encoded, bound = _tokenize(tokenizer, texts[start:start + batch_size], max_length, device)
-        embs.append(_embed_encoded(model, encoded, "mean_no_cls", bound, ragged))
+        embs.append(_embed_encoded(model, encoded, "mean_no_cls", bound, ragged, precision))
     if not embs:
         return np.zeros((0, model.config["hidden_size"]), np.float32)
     return torch.cat(embs, dim=0).cpu().numpy().astype(np.float32)
 
 
 @torch.no_grad()
-def generate_user_profile_embedding(user_profile_map, tokenizer, model, *, ragged=True):
+def generate_user_profile_embedding(user_profile_map, tokenizer, model, *, ragged=True, precision="fp32"):
     """The profile pass (T5/item_encode.py:11-34): users in sorted order, batches of 32, 64 tokens at most, the
-    [CLS] row -> {user id: float32 vector [H]}.  Runs on the model's device.  ``ragged``: as in ``encode_texts``."""
+    [CLS] row -> {user id: float32 vector [H]}.  Runs on the model's device.  ``ragged``, ``precision``: as in
+    ``encode_texts``."""
     device = next(model.parameters()).device
     users = sorted(user_profile_map.items(), key=lambda kv: kv[0])
     out = {}
     for start in range(0, len(users), 32):
         batch = users[start:start + 32]
         encoded, bound = _tokenize(tokenizer, [name for _, name in batch], 64, device)
-        vecs = _embed_encoded(model, encoded, "cls", bound, ragged).cpu().numpy()
+        vecs = _embed_encoded(model, encoded, "cls", bound, ragged, precision).cpu().numpy()
         for (uid, _), v in zip(batch, vecs):
             out[uid] = v
     return out

@@ -39,7 +39,41 @@
 // The caller's row bound sizes the workspace and the grids; the total is read on the device, and a tile, wave or
 // query tile past it exits.  The sums' orders are the padded call's, so the kept rows and the pooled vectors have
 // its bits.  The padded instantiations take the row map (BeRows) and never read it.
+//
+// gr_bert_embed_bf16 / gr_bert_embed_ragged_bf16: the same encoder with bf16 GEMM operands (opt-in; the fp32 entries
+// keep their kernels and their bits).  bf16 = the upper 16 bits of the RNE-rounded fp32.  The contract:
+//   GEMM operands   A and W of the four projections per layer (fused q/k/v, attention output, intermediate, output)
+//                   are bf16, accumulated in fp32 in the MFMA accumulator (v_mfma_f32_32x32x16_bf16).
+//   epilogues       bias, exact-erf GELU, residual add (be_epilogue, the fp32 kernel's own expressions), both
+//                   LayerNorms (two-pass), the softmax's max / exp / sum and the pooling are fp32.
+//   residual        the residual stream and the last hidden state stay fp32.
+//   q, k, v         rounded to bf16 once, in the q/k/v GEMM's epilogue.
+//   scores          fp32 from a bf16 MFMA, the 1 / sqrt(head_dim) scale applied in fp32.
+//   probabilities   the un-normalised exp(s - running max) is rounded to bf16 where it becomes the P . v operand; the
+//                   row sum adds, in fp32, those same rounded values, so a row's weights sum to 1 within fp32.
+//   masking         as the fp32 call: a masked key has probability exactly 0, tiles with no live key are skipped, a
+//                   sequence with no live key gives zeros, holes are legal.
+//   context, GELU   written as bf16 (they are only ever GEMM A operands); each LayerNorm writes its fp32 row for
+//                   the residual and a bf16 copy for the next GEMM.
+//   weights         the six [out, in] matrices per layer are bf16; tables, biases and LayerNorm parameters fp32.
+//   determinism     one summation order per output element (k ascending in steps of 16, the order inside a step is
+//                   the instruction's), whatever B, the row's place in a tile or the tile; no atomics: bitwise
+//                   repeatable, batch-invariant, and the ragged form returns the padded form's bits.
+//   be_gemm_bf16_kernel<WM, TM, TN, EPI>   be_gemm_kernel's tiles and epilogues; K staged 64 deep through a
+//       double-buffered LDS image of 128-byte rows on a 144-byte pitch (16-byte loads, conflict-free 16-byte fragment
+//       reads); K is a multiple of 32, so the last stage may be half zeros, never read from memory.  One fp32 chain per
+//       element: bf16 products are exact in fp32 and K <= 4096, so the fp32 kernel's 256-deep blocking buys nothing
+//       next to the operands' 2^-9.  Output bf16 (bias, GELU) or fp32 (residual).
+//   be_attn_bf16_kernel<HD>   be_attn_kernel's grid and tile order on bf16 q/k/v.  Scores transposed (A rows are keys,
+//       B columns are queries); the probability registers, rounded pairwise, are the B operand of
+//       O^T = V^T . P^T, so a query's running max, sum and output column all sit in its own lane; v is staged
+//       transposed, its keys in the order the accumulator's registers hold them.
+#include <type_traits>
+
 #include "gr_common.h"
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 namespace gr {
 namespace {
@@ -50,6 +84,22 @@ constexpr int BE_BK = 32, BE_PITCH = BE_BK + 4, BE_NT = 256;
 constexpr int BE_KFLUSH = 8;               // 32-deep stages per fma chain: 256 deep
 constexpr int BE_QT = 128, BE_KT = 32;     // queries per workgroup, keys per streamed tile
 enum { BE_EPI_BIAS = 0, BE_EPI_GELU = 1, BE_EPI_RESID = 2 };
+constexpr int BH_BK = 64, BH_PITCH = BH_BK + 8;   // bf16 elements per staged row and its pitch: 128 of 144 bytes
+
+// What follows a GEMM's sum, in the fp32 and in the bf16 kernel: the bias, then exact-erf GELU or the residual add.
+template <int EPI>
+__device__ __forceinline__ float be_epilogue(float sum, float bias, const float* __restrict__ residual, int64_t at) {
+  float o = sum + bias;
+  if constexpr (EPI == BE_EPI_GELU) o = 0.5f * o * (1.0f + erff(o * 0.70710678118654752440f));
+  if constexpr (EPI == BE_EPI_RESID) o = residual[at] + o;
+  return o;
+}
+
+// bf16 = the upper 16 bits of the RNE-rounded fp32 (v_cvt_pk_bf16_f32)
+__device__ __forceinline__ uint16_t be_bf16(float x) { return __builtin_bit_cast(uint16_t, (__bf16)x); }
+__device__ __forceinline__ f32x16 mfma32_bf16(u32x4 a, u32x4 b, f32x16 c) {
+  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+}
 
 // The ragged call's row map, in the workspace: len[b] kept rows of sequence b (one past its last live position),
 // off[b] their first packed row, total = off[B], flag != 0 when the mask held more rows than the caller's bound
@@ -179,19 +229,138 @@ __global__ __launch_bounds__(BE_NT, 2) void be_gemm_kernel(const float* __restri
       for (int v = 0; v < 16; ++v) {
         const int64_t row = m0 + wm * 32 * TM + i * 32 + mfma32_row(v, h);
         if (row < M) {
-          float o = tot[i][j][v] + bv;
-          if constexpr (EPI == BE_EPI_GELU) o = 0.5f * o * (1.0f + erff(o * 0.70710678118654752440f));
-          if constexpr (EPI == BE_EPI_RESID) o = residual[row * N + col] + o;
-          y[row * N + col] = o;
+          y[row * N + col] = be_epilogue<EPI>(tot[i][j][v], bv, residual, row * N + col);
         }
       }
     }
   }
 }
 
-// LayerNorm of the row a wave holds as xv[t] = x[lane + 64 t] (0 past H), written to out.
+struct BeSeg16 {   // BeSeg with bf16 matrices
+  const uint16_t* w[3];
+  const float* b[3];
+};
+
+// be_gemm_kernel on bf16 operands: x [M, K] and the weights [seg_n, K] bf16, fp32 accumulation, be_epilogue, y
+// fp32 (EPI_RESID) or bf16 (the others).  Lane (r, h) of a wave takes, per 16-deep step, the 16 bytes k = 8 h .. 8 h + 7
+// of row r of each operand from the LDS image.
+template <int WM, int TM, int TN, int EPI, bool RAGGED>
+__global__ __launch_bounds__(BE_NT, 2) void be_gemm_bf16_kernel(const uint16_t* __restrict__ x, BeSeg16 sg, int seg_n,
+                                                                const float* __restrict__ residual,
+                                                                void* __restrict__ y_, int64_t M_, int N, int K,
+                                                                int tiles_n, BeRows rg) {
+  constexpr int WN = 4 / WM, BM = 32 * WM * TM, BN = 32 * WN * TN;
+  using OT = std::conditional_t<EPI == BE_EPI_RESID, float, uint16_t>;
+  OT* __restrict__ y = static_cast<OT*>(y_);
+  int64_t M = M_;
+  if constexpr (RAGGED) {
+    M = rg.total[0];
+    if ((int64_t)(blockIdx.x / tiles_n) * BM >= M) return;
+  }
+  __shared__ __attribute__((aligned(16))) uint16_t lds[2][(BM + BN) * BH_PITCH];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave / WN, wn = wave % WN, r = lane & 31, h = lane >> 5;
+  const int tni = blockIdx.x % tiles_n;
+  const int64_t m0 = (int64_t)(blockIdx.x / tiles_n) * BM;
+  const int n0 = tni * BN;
+
+  constexpr int AV = BM * BH_BK / 8 / BE_NT, BV = BN * BH_BK / 8 / BE_NT;
+  u32x4 ra[AV], rb[BV];
+  // K is a multiple of 32 and kk of 8: a 16-byte piece lies inside the row or wholly past it (then zeros)
+  auto gload = [&](int k0) {
+#pragma unroll
+    for (int i = 0; i < AV; ++i) {
+      const int f = tid + BE_NT * i, row = f >> 3, kk = k0 + (f & 7) * 8;
+      const int64_t g = m0 + row;
+      ra[i] = (g < M && kk < K) ? *reinterpret_cast<const u32x4*>(x + g * K + kk) : u32x4{0u, 0u, 0u, 0u};
+    }
+#pragma unroll
+    for (int i = 0; i < BV; ++i) {
+      const int f = tid + BE_NT * i, row = f >> 3, kk = k0 + (f & 7) * 8;
+      const int gn = n0 + row;
+      u32x4 v = {0u, 0u, 0u, 0u};
+      if (gn < N && kk < K) {
+        const int seg = gn / seg_n, wr = gn - seg * seg_n;
+        const uint16_t* wp = seg == 0 ? sg.w[0] : seg == 1 ? sg.w[1] : sg.w[2];
+        v = *reinterpret_cast<const u32x4*>(wp + (int64_t)wr * K + kk);
+      }
+      rb[i] = v;
+    }
+  };
+  auto swrite = [&](int buf) {
+    uint16_t* s = lds[buf];
+#pragma unroll
+    for (int i = 0; i < AV; ++i) {
+      const int f = tid + BE_NT * i;
+      *reinterpret_cast<u32x4*>(s + (f >> 3) * BH_PITCH + (f & 7) * 8) = ra[i];
+    }
+#pragma unroll
+    for (int i = 0; i < BV; ++i) {
+      const int f = tid + BE_NT * i;
+      *reinterpret_cast<u32x4*>(s + (BM + (f >> 3)) * BH_PITCH + (f & 7) * 8) = rb[i];
+    }
+  };
+
+  f32x16 acc[TM][TN];
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int v = 0; v < 16; ++v) acc[i][j][v] = 0.f;
+
+  const int nk = (K + BH_BK - 1) / BH_BK;
+  gload(0);
+  swrite(0);
+  __syncthreads();
+  for (int kt = 0; kt < nk; ++kt) {
+    const int cur = kt & 1;
+    if (kt + 1 < nk) gload((kt + 1) * BH_BK);
+    const uint16_t* As = lds[cur] + (wm * 32 * TM + r) * BH_PITCH + 8 * h;
+    const uint16_t* Bs = lds[cur] + (BM + wn * 32 * TN + r) * BH_PITCH + 8 * h;
+#pragma unroll
+    for (int kc = 0; kc < BH_BK / 16; ++kc) {
+      u32x4 a[TM], b[TN];
+#pragma unroll
+      for (int i = 0; i < TM; ++i) a[i] = *reinterpret_cast<const u32x4*>(As + i * 32 * BH_PITCH + kc * 16);
+#pragma unroll
+      for (int j = 0; j < TN; ++j) b[j] = *reinterpret_cast<const u32x4*>(Bs + j * 32 * BH_PITCH + kc * 16);
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) acc[i][j] = mfma32_bf16(a[i], b[j], acc[i][j]);
+    }
+    if (kt + 1 < nk) swrite(cur ^ 1);
+    __syncthreads();
+  }
+
+#pragma unroll
+  for (int j = 0; j < TN; ++j) {
+    const int col = n0 + wn * 32 * TN + j * 32 + r;
+    if (col >= N) continue;
+    const int seg = col / seg_n;
+    const float* bp = seg == 0 ? sg.b[0] : seg == 1 ? sg.b[1] : sg.b[2];
+    const float bv = bp[col - seg * seg_n];
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+#pragma unroll
+      for (int v = 0; v < 16; ++v) {
+        const int64_t row = m0 + wm * 32 * TM + i * 32 + mfma32_row(v, h);
+        if (row < M) {
+          const float o = be_epilogue<EPI>(acc[i][j][v], bv, residual, row * N + col);
+          if constexpr (EPI == BE_EPI_RESID) y[row * N + col] = o;
+          else y[row * N + col] = be_bf16(o);
+        }
+      }
+    }
+  }
+}
+
+// LayerNorm of the row a wave holds as xv[t] = x[lane + 64 t] (0 past H), written to out and, BF16, rounded to out16.
+template <bool BF16>
 __device__ __forceinline__ void be_ln_row(float (&xv)[BE_MAX_H / 64], int lane, int H, const float* __restrict__ w,
-                                          const float* __restrict__ b, float eps, float* __restrict__ out) {
+                                          const float* __restrict__ b, float eps, float* __restrict__ out,
+                                          uint16_t* __restrict__ out16) {
   float s = 0.f;
 #pragma unroll
   for (int t = 0; t < BE_MAX_H / 64; ++t) s += xv[t];
@@ -206,19 +375,24 @@ __device__ __forceinline__ void be_ln_row(float (&xv)[BE_MAX_H / 64], int lane, 
 #pragma unroll
   for (int t = 0; t < BE_MAX_H / 64; ++t) {
     const int c = lane + 64 * t;
-    if (c < H) out[c] = (xv[t] * rstd) * w[c] + b[c];
+    if (c < H) {
+      const float o = (xv[t] * rstd) * w[c] + b[c];
+      out[c] = o;
+      if constexpr (BF16) out16[c] = be_bf16(o);
+    }
   }
 }
 
 // RAGGED: grid (sequence, four positions); position s < len[b] of sequence b is written at packed row off[b] + s.
-template <bool RAGGED>
+// BF16: the row is also written, rounded, to out16 (the next GEMM's operand); out16 is not read otherwise.
+template <bool RAGGED, bool BF16>
 __global__ __launch_bounds__(256) void be_embed_ln_kernel(const int64_t* __restrict__ ids,
                                                           const int64_t* __restrict__ type_ids,
                                                           const float* __restrict__ word, const float* __restrict__ pos,
                                                           const float* __restrict__ type, const float* __restrict__ lnw,
                                                           const float* __restrict__ lnb, float eps, int vocab,
                                                           int type_vocab, int S, int H, int64_t M, float* __restrict__ out,
-                                                          BeRows rg) {
+                                                          uint16_t* __restrict__ out16, BeRows rg) {
   const int lane = threadIdx.x & 63;
   int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);   // of ids
   int64_t orow = row;                                           // of out
@@ -244,13 +418,13 @@ __global__ __launch_bounds__(256) void be_embed_ln_kernel(const int64_t* __restr
     const int c = lane + 64 * t;
     xv[t] = c < H ? (wr[c] + tr[c]) + pr[c] : 0.f;
   }
-  be_ln_row(xv, lane, H, lnw, lnb, eps, out + orow * H);
+  be_ln_row<BF16>(xv, lane, H, lnw, lnb, eps, out + orow * H, BF16 ? out16 + orow * H : nullptr);
 }
 
-template <bool RAGGED>
+template <bool RAGGED, bool BF16>
 __global__ __launch_bounds__(256) void be_ln_kernel(const float* __restrict__ in, const float* __restrict__ lnw,
                                                     const float* __restrict__ lnb, float eps, int H, int64_t M_,
-                                                    float* __restrict__ out, BeRows rg) {
+                                                    float* __restrict__ out, uint16_t* __restrict__ out16, BeRows rg) {
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   int64_t M = M_;
@@ -262,7 +436,7 @@ __global__ __launch_bounds__(256) void be_ln_kernel(const float* __restrict__ in
     const int c = lane + 64 * t;
     xv[t] = c < H ? in[row * H + c] : 0.f;
   }
-  be_ln_row(xv, lane, H, lnw, lnb, eps, out + row * H);
+  be_ln_row<BF16>(xv, lane, H, lnw, lnb, eps, out + row * H, BF16 ? out16 + row * H : nullptr);
 }
 
 // RAGGED: the sequence's rows are the packed rows off[b] .. off[b] + len[b]; SL = len[b] takes S's place in the row
@@ -414,6 +588,161 @@ __global__ __launch_bounds__(256) void be_attn_kernel(const float* __restrict__ 
   }
 }
 
+// be_attn_kernel on bf16 q/k/v (rows of 3 Hd bf16), bf16 context.  Per visited tile: S^T = K . Q^T (D register v of
+// lane (r, h): key mfma32_row(v, h) against query r), the fp32 softmax step, then O^T += V^T . P^T with the rounded
+// probabilities as the B operand: registers 8 s .. 8 s + 7 are k-step s, so element j of lane half h is key
+// 16 s + 8 (j >> 2) + 4 h + (j & 3), and v is staged as vt[d][16 s + 8 h + j] = v[that key][d] to match.  O^T has
+// query r on the lane and d = mfma32_row(v, h) in the registers: alpha and the row sum are the lane's own.
+template <int HD, bool RAGGED>
+__global__ __launch_bounds__(256) void be_attn_bf16_kernel(const uint16_t* __restrict__ qkv,
+                                                           const int64_t* __restrict__ mask, uint16_t* __restrict__ ctx,
+                                                           int S, int NH, int nqt, float scale, BeRows rg) {
+  constexpr int PK = HD + 8, PV = BE_KT + 8, NKS = HD / 16, NDB = HD / 32, LV = 2 * BE_KT * HD / 8 / 256;
+  constexpr int PER = BE_KT * HD / 8;   // 16-byte pieces per matrix per tile
+  __shared__ __attribute__((aligned(16))) uint16_t ks[2][BE_KT * PK];
+  __shared__ __attribute__((aligned(16))) uint16_t vt[2][HD * PV];
+  __shared__ uint32_t livebits[BE_MAX_S / BE_KT];
+  __shared__ int tiles[BE_MAX_S / BE_KT];
+  __shared__ int ntl_s;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r = lane & 31, h = lane >> 5;
+  const int qt = blockIdx.x % nqt, head = (blockIdx.x / nqt) % NH;
+  const int64_t b = blockIdx.x / (nqt * NH);
+  const int Hd = NH * HD, ld = 3 * Hd;
+  int SL = S;                 // rows of this sequence
+  int64_t row0 = b * S;       // its first row in qkv and ctx
+  if constexpr (RAGGED) {
+    SL = rg.len[b];
+    row0 = rg.off[b];
+    if (qt * BE_QT >= SL) return;   // uniform over the workgroup, before any barrier
+  }
+  const uint16_t* base = qkv + row0 * ld + head * HD;
+  const int nt = (S + BE_KT - 1) / BE_KT;
+
+  for (int t = wave; t < nt; t += 4) {
+    const int j = BE_KT * t + lane;
+    const bool live = lane < BE_KT && j < S && (mask == nullptr || mask[b * S + j] != 0);
+    const uint32_t bits = (uint32_t)__ballot(live);
+    if (lane == 0) livebits[t] = bits;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int n = 0;
+    for (int t = 0; t < nt; ++t)
+      if (livebits[t] != 0u) tiles[n++] = t;
+    ntl_s = n;
+  }
+  __syncthreads();
+  const int ntl = ntl_s;
+
+  const int q0 = qt * BE_QT + 32 * wave;
+  const bool active = q0 < SL;            // wave-uniform
+  const int qrow = q0 + r < SL ? q0 + r : SL - 1;   // rows past SL read row SL - 1, never stored
+  u32x4 q[NKS];
+#pragma unroll
+  for (int kc = 0; kc < NKS; ++kc) q[kc] = *reinterpret_cast<const u32x4*>(base + (int64_t)qrow * ld + 16 * kc + 8 * h);
+
+  u32x4 rk[LV];
+  auto gload = [&](int t) {
+#pragma unroll
+    for (int i = 0; i < LV; ++i) {
+      const int f = tid + 256 * i, mat = f / PER, rem = f % PER;
+      const int row = rem / (HD / 8), c8 = rem % (HD / 8);
+      const int key = BE_KT * t + row < SL ? BE_KT * t + row : SL - 1;   // past SL: finite, weighted 0
+      rk[i] = *reinterpret_cast<const u32x4*>(base + (int64_t)key * ld + (1 + mat) * Hd + 8 * c8);
+    }
+  };
+  auto swrite = [&](int buf) {
+#pragma unroll
+    for (int i = 0; i < LV; ++i) {
+      const int f = tid + 256 * i, mat = f / PER, rem = f % PER;
+      const int row = rem / (HD / 8), c8 = rem % (HD / 8);
+      if (mat == 0) {
+        *reinterpret_cast<u32x4*>(&ks[buf][row * PK + 8 * c8]) = rk[i];
+      } else {
+        const int at = (row & 16) | (((row >> 2) & 1) << 3) | (((row >> 3) & 1) << 2) | (row & 3);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) vt[buf][(8 * c8 + e) * PV + at] = (uint16_t)(rk[i][e >> 1] >> (16 * (e & 1)));
+      }
+    }
+  };
+
+  f32x16 o[NDB];
+#pragma unroll
+  for (int d = 0; d < NDB; ++d)
+#pragma unroll
+    for (int v = 0; v < 16; ++v) o[d][v] = 0.f;
+  float m = -INFINITY, l = 0.f;   // of query r, the same in both lanes of the pair
+
+  if (ntl > 0) {
+    gload(tiles[0]);
+    swrite(0);
+  }
+  __syncthreads();
+  for (int it = 0; it < ntl; ++it) {
+    const int cur = it & 1;
+    if (it + 1 < ntl) gload(tiles[it + 1]);
+    if (active) {
+      const uint32_t bits = livebits[tiles[it]];
+      const uint16_t* Ks = ks[cur] + r * PK + 8 * h;
+      const uint16_t* Vs = vt[cur] + r * PV + 8 * h;
+      f32x16 sc;
+#pragma unroll
+      for (int v = 0; v < 16; ++v) sc[v] = 0.f;
+#pragma unroll
+      for (int kc = 0; kc < NKS; ++kc) sc = mfma32_bf16(*reinterpret_cast<const u32x4*>(Ks + 16 * kc), q[kc], sc);
+      float mt = -INFINITY;
+#pragma unroll
+      for (int v = 0; v < 16; ++v) {
+        const float a = ((bits >> mfma32_row(v, h)) & 1u) ? sc[v] * scale : -INFINITY;
+        sc[v] = a;
+        mt = fmaxf(mt, a);
+      }
+      mt = xmax<32>(mt);                       // the other sixteen keys of this query; finite: the tile has a live key
+      const float mn = fmaxf(m, mt);
+      const float alpha = expf(m - mn);        // 0 on the first visited tile (m = -inf)
+      float sum = 0.f;
+      bf16x8 pf[2];                            // the rounded weights: P . v's operand and the row sum's terms
+#pragma unroll
+      for (int v = 0; v < 16; ++v) {
+        const __bf16 pb = (__bf16)expf(sc[v] - mn);   // exactly 0 for a masked key
+        pf[v >> 3][v & 7] = pb;
+        sum += (float)pb;
+      }
+      sum = xsum<32>(sum);
+      l = fmaf(l, alpha, sum);
+      m = mn;
+#pragma unroll
+      for (int d = 0; d < NDB; ++d) {
+#pragma unroll
+        for (int v = 0; v < 16; ++v) o[d][v] = o[d][v] * alpha;
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+          o[d] = mfma32_bf16(*reinterpret_cast<const u32x4*>(Vs + 32 * d * PV + 16 * s),
+                             __builtin_bit_cast(u32x4, pf[s]), o[d]);
+      }
+    }
+    if (it + 1 < ntl) swrite(cur ^ 1);
+    __syncthreads();
+  }
+
+  if (active && q0 + r < SL) {
+    uint16_t* out = ctx + (row0 + q0 + r) * Hd + head * HD + 4 * h;
+#pragma unroll
+    for (int d = 0; d < NDB; ++d)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {   // registers 4 g .. 4 g + 3: d = 32 d + 8 g + 4 h + 0 .. 3
+        uint32_t w2[2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+          const float lo = l > 0.f ? o[d][4 * g + 2 * e] / l : 0.f, hi = l > 0.f ? o[d][4 * g + 2 * e + 1] / l : 0.f;
+          w2[e] = (uint32_t)be_bf16(lo) | ((uint32_t)be_bf16(hi) << 16);
+        }
+        *reinterpret_cast<uint2*>(out + 32 * d + 8 * g) = make_uint2(w2[0], w2[1]);
+      }
+  }
+}
+
 // mode 0: no pooling; 1: mean over the live rows after position 0; 2: row 0.  A sequence with no live
 // key gets zeros in pooled and in hidden_out.  hid: the last hidden state (hidden_out itself when given).
 // RAGGED: hid holds packed rows (row i of the sequence at off[b] + i, i < len[b]; hidden_out is not used); NaN in
@@ -529,7 +858,9 @@ __global__ __launch_bounds__(BE_SCAN_NT) void be_offsets_kernel(int32_t* __restr
   }
 }
 
-const char* be_check(const gr_bert_params* p, int64_t B, int S) {
+// P: gr_bert_params or gr_bert_bf16_params (the same dimension fields): one envelope for the four entries.
+template <typename P>
+const char* be_check(const P* p, int64_t B, int S) {
   if (!p) return "null params";
   if (B < 0) return "negative batch size";
   if (p->hidden_size < 32 || p->hidden_size > BE_MAX_H || p->hidden_size % 32)
@@ -568,20 +899,43 @@ BeLayout be_layout_rows(const gr_bert_params* p, size_t M) {
   return L;
 }
 
-BeLayout be_layout(const gr_bert_params* p, int64_t B, int S) { return be_layout_rows(p, (size_t)B * S); }
+size_t be_rows_bytes(const gr_bert_params* p, size_t M) { return be_layout_rows(p, M).total * sizeof(float); }
 
-// The ragged call's workspace: be_layout_rows(rows), then off[B + 1] int64, total int64 + flag int32 (16 bytes),
-// len[B] int32, each on a 16-byte boundary.
+// The bf16 calls' workspace, byte offsets: the fp32 residual stream x and the pre-LN sum t, then the bf16 GEMM
+// operands (x's copy, q/k/v, the context, the GELU output); no fp32 qkv, ctx or ff.
+struct BeLayout16 {
+  size_t x, t, x16, qkv, ctx, ff, total;
+};
+
+BeLayout16 be_layout16_rows(const gr_bert_bf16_params* p, size_t M) {
+  const size_t H = (size_t)p->hidden_size;
+  BeLayout16 L;
+  size_t o = 0;
+  L.x = o;   o += align_up(M * H * 4, 16);
+  L.t = o;   o += align_up(M * H * 4, 16);
+  L.x16 = o; o += align_up(M * H * 2, 16);
+  L.qkv = o; o += align_up(M * 3 * H * 2, 16);
+  L.ctx = o; o += align_up(M * H * 2, 16);
+  L.ff = o;  o += align_up(M * (size_t)p->intermediate_size * 2, 16);
+  L.total = o;
+  return L;
+}
+
+size_t be_rows_bytes(const gr_bert_bf16_params* p, size_t M) { return be_layout16_rows(p, M).total; }
+
+// The ragged call's workspace: the rows' part (be_rows_bytes(rows)), then off[B + 1] int64, total int64 + flag int32
+// (16 bytes), len[B] int32, each on a 16-byte boundary.
 struct BeRagged {
   int64_t rows;              // the caller's bound, at most B * S
   size_t off, total, len;    // byte offsets
   size_t bytes;
 };
 
-BeRagged be_ragged(const gr_bert_params* p, int64_t B, int S, int64_t rows_bound) {
+template <typename P>
+BeRagged be_ragged(const P* p, int64_t B, int S, int64_t rows_bound) {
   BeRagged R;
   R.rows = rows_bound < B * S ? (rows_bound > 0 ? rows_bound : 0) : B * S;
-  size_t o = be_layout_rows(p, (size_t)R.rows).total * sizeof(float);
+  size_t o = be_rows_bytes(p, (size_t)R.rows);
   R.off = o;   o += align_up((size_t)(B + 1) * sizeof(int64_t), 16);
   R.total = o; o += 16;
   R.len = o;   o += align_up((size_t)B * sizeof(int32_t), 16);
@@ -589,31 +943,54 @@ BeRagged be_ragged(const gr_bert_params* p, int64_t B, int S, int64_t rows_bound
   return R;
 }
 
-size_t be_bytes(const gr_bert_params* p, int64_t B, int S) { return be_layout(p, B, S).total * sizeof(float) + 16; }
+template <typename P>
+size_t be_bytes(const P* p, int64_t B, int S) { return be_rows_bytes(p, (size_t)B * S) + 16; }
 
-// RAGGED: M is the caller's row bound (it sizes the grid and picks the tile), the row count is rg.total[0].
-template <int EPI, bool RAGGED>
-int be_gemm(const char* what, const float* x, const BeSeg& sg, int seg_n, const float* residual, float* y, int64_t M,
-            int N, int K, hipStream_t st, const BeRows& rg) {
-  // Three tiles, the same bits from each.  A compute unit works through its workgroups at one MFMA rate
-  // however many are resident, so a launch takes ceil(workgroups / compute units) rounds of one tile's
-  // work: take the tile with the least rounds x tile area (bert-base at 4096 rows: q/k/v is 2.25 rounds of
-  // 128 x 128 but exactly 3 of 128 x 96; the 768-wide outputs are 0.75 of 128 x 128 but exactly 1 of
-  // 128 x 96).  The factors charge the smaller tiles' extra operand traffic per multiply-add.
-  struct Tile { int bm, bn; double cost; };
-  const Tile tiles[3] = {{128, 128, 1.0}, {64, 128, 1.10}, {128, 96, 1.03}};
+// Three tiles, the same bits from each.  A compute unit works through its workgroups at one MFMA rate
+// however many are resident, so a launch takes ceil(workgroups / compute units) rounds of one tile's
+// work: take the tile with the least rounds x tile area (bert-base at 4096 rows: q/k/v is 2.25 rounds of
+// 128 x 128 but exactly 3 of 128 x 96; the 768-wide outputs are 0.75 of 128 x 128 but exactly 1 of
+// 128 x 96).  The factors charge the smaller tiles' extra operand traffic per multiply-add.
+struct BeTile { int bm, bn; double cost; };
+constexpr BeTile BE_TILES[3] = {{128, 128, 1.0}, {64, 128, 1.10}, {128, 96, 1.03}};
+
+int be_pick_tile(int64_t M, int N) {
   const int64_t cus = cu_count();
   int pick = (int)option("bert_tile") - 1;
   if (pick < 0) {
     double best = 0.0;
     for (int t = 0; t < 3; ++t) {
-      const int64_t wgs = ((M + tiles[t].bm - 1) / tiles[t].bm) * ((N + tiles[t].bn - 1) / tiles[t].bn);
-      const double c = (double)((wgs + cus - 1) / cus) * tiles[t].bm * tiles[t].bn * tiles[t].cost;
+      const int64_t wgs = ((M + BE_TILES[t].bm - 1) / BE_TILES[t].bm) * ((N + BE_TILES[t].bn - 1) / BE_TILES[t].bn);
+      const double c = (double)((wgs + cus - 1) / cus) * BE_TILES[t].bm * BE_TILES[t].bn * BE_TILES[t].cost;
       if (pick < 0 || c < best) pick = t, best = c;
     }
   }
-  const int tn = (N + tiles[pick].bn - 1) / tiles[pick].bn;
-  const dim3 grid((unsigned)(((M + tiles[pick].bm - 1) / tiles[pick].bm) * tn));
+  return pick;
+}
+
+// The bf16 GEMM: be_gemm's tiles, picked the same way.  y: fp32 with EPI_RESID, bf16 otherwise.
+template <int EPI, bool RAGGED>
+int be_gemm_bf16(const char* what, const uint16_t* x, const BeSeg16& sg, int seg_n, const float* residual, void* y,
+                 int64_t M, int N, int K, hipStream_t st, const BeRows& rg) {
+  const int pick = be_pick_tile(M, N);
+  const int tn = (N + BE_TILES[pick].bn - 1) / BE_TILES[pick].bn;
+  const dim3 grid((unsigned)(((M + BE_TILES[pick].bm - 1) / BE_TILES[pick].bm) * tn));
+  if (pick == 0)
+    be_gemm_bf16_kernel<2, 2, 2, EPI, RAGGED><<<grid, dim3(BE_NT), 0, st>>>(x, sg, seg_n, residual, y, M, N, K, tn, rg);
+  else if (pick == 1)
+    be_gemm_bf16_kernel<2, 1, 2, EPI, RAGGED><<<grid, dim3(BE_NT), 0, st>>>(x, sg, seg_n, residual, y, M, N, K, tn, rg);
+  else
+    be_gemm_bf16_kernel<4, 1, 3, EPI, RAGGED><<<grid, dim3(BE_NT), 0, st>>>(x, sg, seg_n, residual, y, M, N, K, tn, rg);
+  return check_launch(what);
+}
+
+// RAGGED: M is the caller's row bound (it sizes the grid and picks the tile), the row count is rg.total[0].
+template <int EPI, bool RAGGED>
+int be_gemm(const char* what, const float* x, const BeSeg& sg, int seg_n, const float* residual, float* y, int64_t M,
+            int N, int K, hipStream_t st, const BeRows& rg) {
+  const int pick = be_pick_tile(M, N);
+  const int tn = (N + BE_TILES[pick].bn - 1) / BE_TILES[pick].bn;
+  const dim3 grid((unsigned)(((M + BE_TILES[pick].bm - 1) / BE_TILES[pick].bm) * tn));
   if (pick == 0)
     be_gemm_kernel<2, 2, 2, EPI, RAGGED><<<grid, dim3(BE_NT), 0, st>>>(x, sg, seg_n, residual, y, M, N, K, tn, rg);
   else if (pick == 1)
@@ -646,15 +1023,15 @@ int be_stack(const gr_bert_params* p, const int64_t* attention_mask, int64_t B, 
     const BeSeg ao = {{w[6], nullptr, nullptr}, {w[7], nullptr, nullptr}};
     if (int rc = be_gemm<BE_EPI_RESID, RAGGED>("bert attention output + residual", CTX, ao, H, X, T, M, H, H, st, rg))
       return rc;
-    be_ln_kernel<RAGGED><<<dim3(row_blocks), dim3(256), 0, st>>>(T, w[8], w[9], p->eps, H, M, X, rg);
+    be_ln_kernel<RAGGED, false><<<dim3(row_blocks), dim3(256), 0, st>>>(T, w[8], w[9], p->eps, H, M, X, nullptr, rg);
     if (int rc = check_launch("be_ln_kernel")) return rc;
     const BeSeg inter = {{w[10], nullptr, nullptr}, {w[11], nullptr, nullptr}};
     if (int rc = be_gemm<BE_EPI_GELU, RAGGED>("bert intermediate + gelu", X, inter, I, nullptr, FF, M, I, H, st, rg))
       return rc;
     const BeSeg outw = {{w[12], nullptr, nullptr}, {w[13], nullptr, nullptr}};
     if (int rc = be_gemm<BE_EPI_RESID, RAGGED>("bert output + residual", FF, outw, H, X, T, M, H, I, st, rg)) return rc;
-    be_ln_kernel<RAGGED><<<dim3(row_blocks), dim3(256), 0, st>>>(T, w[14], w[15], p->eps, H, M,
-                                                                 l + 1 == p->num_layers ? last : X, rg);
+    be_ln_kernel<RAGGED, false><<<dim3(row_blocks), dim3(256), 0, st>>>(T, w[14], w[15], p->eps, H, M,
+                                                                        l + 1 == p->num_layers ? last : X, nullptr, rg);
     if (int rc = check_launch("be_ln_kernel")) return rc;
   }
   return GR_OK;
@@ -665,6 +1042,169 @@ bool be_weights_ok(const gr_bert_params* p) {
   for (int l = 0; ok && l < p->num_layers; ++l)
     for (int i = 0; i < 16; ++i) ok = ok && p->layer[l][i] && aligned16(p->layer[l][i]);
   return ok;
+}
+
+bool be_weights_ok(const gr_bert_bf16_params* p) {
+  bool ok = p->word && p->position && p->token_type && p->emb_ln_w && p->emb_ln_b;
+  for (int l = 0; ok && l < p->num_layers; ++l) {
+    for (int i = 0; i < 6; ++i) ok = ok && p->matrix[l][i] && aligned16(p->matrix[l][i]);
+    for (int i = 0; i < 10; ++i) ok = ok && p->vector[l][i] && aligned16(p->vector[l][i]);
+  }
+  return ok;
+}
+
+// Embeddings + LayerNorm into the workspace's x, then the stack with the last LayerNorm into last (the workspace's x
+// when null); returns through *last_out where the last hidden state lies.
+template <bool RAGGED>
+int be_forward(const gr_bert_params* p, const int64_t* input_ids, const int64_t* attention_mask,
+               const int64_t* token_type_ids, int64_t B, int S, int64_t M, void* workspace, float* last,
+               const float** last_out, hipStream_t st, const BeRows& rg) {
+  const int H = p->hidden_size;
+  const BeLayout L = be_layout_rows(p, (size_t)M);
+  float* ws = static_cast<float*>(workspace);
+  const dim3 eg = RAGGED ? dim3((unsigned)B, (unsigned)((S + 3) / 4)) : dim3((unsigned)((M + 3) / 4));
+  // RAGGED: B x ceil(S / 4) <= 65536 x 128 workgroups
+  be_embed_ln_kernel<RAGGED, false><<<eg, dim3(256), 0, st>>>(
+      input_ids, token_type_ids, p->word, p->position, p->token_type, p->emb_ln_w, p->emb_ln_b, p->eps, p->vocab_size,
+      p->type_vocab_size, S, H, M, ws + L.x, nullptr, rg);
+  if (int rc = check_launch("be_embed_ln_kernel")) return rc;
+  if (!last) last = ws + L.x;
+  *last_out = last;
+  return be_stack<RAGGED>(p, attention_mask, B, S, M, ws, L, last, st, rg);
+}
+
+// The same on bf16 GEMM operands (the contract at the head of this file): 2 + 7 num_layers launches as well.
+// matrix[l] = {query, key, value, attention.output.dense, intermediate.dense, output.dense}.weight,
+// vector[l] = {query, key, value, attention.output.dense}.bias, attention.output.LayerNorm.{weight, bias},
+//             {intermediate.dense, output.dense}.bias, output.LayerNorm.{weight, bias}.
+template <bool RAGGED>
+int be_forward(const gr_bert_bf16_params* p, const int64_t* input_ids, const int64_t* attention_mask,
+               const int64_t* token_type_ids, int64_t B, int S, int64_t M, void* workspace, float* last,
+               const float** last_out, hipStream_t st, const BeRows& rg) {
+  const int H = p->hidden_size, I = p->intermediate_size, NH = p->num_heads, HD = p->head_dim;
+  const BeLayout16 L = be_layout16_rows(p, (size_t)M);
+  char* wb = static_cast<char*>(workspace);
+  float *X = reinterpret_cast<float*>(wb + L.x), *T = reinterpret_cast<float*>(wb + L.t);
+  uint16_t *X16 = reinterpret_cast<uint16_t*>(wb + L.x16), *QKV = reinterpret_cast<uint16_t*>(wb + L.qkv);
+  uint16_t *CTX = reinterpret_cast<uint16_t*>(wb + L.ctx), *FF = reinterpret_cast<uint16_t*>(wb + L.ff);
+  const dim3 eg = RAGGED ? dim3((unsigned)B, (unsigned)((S + 3) / 4)) : dim3((unsigned)((M + 3) / 4));
+  be_embed_ln_kernel<RAGGED, true><<<eg, dim3(256), 0, st>>>(
+      input_ids, token_type_ids, p->word, p->position, p->token_type, p->emb_ln_w, p->emb_ln_b, p->eps, p->vocab_size,
+      p->type_vocab_size, S, H, M, X, X16, rg);
+  if (int rc = check_launch("be_embed_ln_kernel")) return rc;
+  if (!last) last = X;
+  *last_out = last;
+  const unsigned row_blocks = (unsigned)((M + 3) / 4);
+  const float scale = sas_scale(HD);
+  const int nqt = (S + BE_QT - 1) / BE_QT;
+  for (int l = 0; l < p->num_layers; ++l) {
+    const uint16_t* const* w = p->matrix[l];
+    const float* const* v = p->vector[l];
+    const BeSeg16 qkv_w = {{w[0], w[1], w[2]}, {v[0], v[1], v[2]}};
+    if (int rc = be_gemm_bf16<BE_EPI_BIAS, RAGGED>("bert bf16 q/k/v", X16, qkv_w, H, nullptr, QKV, M, 3 * H, H, st, rg))
+      return rc;
+    const dim3 ag((unsigned)(B * NH * nqt));
+    if (HD == 64)
+      be_attn_bf16_kernel<64, RAGGED><<<ag, dim3(256), 0, st>>>(QKV, attention_mask, CTX, S, NH, nqt, scale, rg);
+    else
+      be_attn_bf16_kernel<32, RAGGED><<<ag, dim3(256), 0, st>>>(QKV, attention_mask, CTX, S, NH, nqt, scale, rg);
+    if (int rc = check_launch("be_attn_bf16_kernel")) return rc;
+    const BeSeg16 ao = {{w[3], nullptr, nullptr}, {v[3], nullptr, nullptr}};
+    if (int rc = be_gemm_bf16<BE_EPI_RESID, RAGGED>("bert bf16 attention output + residual", CTX, ao, H, X, T, M, H, H,
+                                                    st, rg))
+      return rc;
+    be_ln_kernel<RAGGED, true><<<dim3(row_blocks), dim3(256), 0, st>>>(T, v[4], v[5], p->eps, H, M, X, X16, rg);
+    if (int rc = check_launch("be_ln_kernel")) return rc;
+    const BeSeg16 inter = {{w[4], nullptr, nullptr}, {v[6], nullptr, nullptr}};
+    if (int rc = be_gemm_bf16<BE_EPI_GELU, RAGGED>("bert bf16 intermediate + gelu", X16, inter, I, nullptr, FF, M, I, H,
+                                                   st, rg))
+      return rc;
+    const BeSeg16 outw = {{w[5], nullptr, nullptr}, {v[7], nullptr, nullptr}};
+    if (int rc = be_gemm_bf16<BE_EPI_RESID, RAGGED>("bert bf16 output + residual", FF, outw, H, X, T, M, H, I, st, rg))
+      return rc;
+    be_ln_kernel<RAGGED, true><<<dim3(row_blocks), dim3(256), 0, st>>>(T, v[8], v[9], p->eps, H, M,
+                                                                       l + 1 == p->num_layers ? last : X, X16, rg);
+    if (int rc = check_launch("be_ln_kernel")) return rc;
+  }
+  return GR_OK;
+}
+
+// The padded entries' body: the checks in gr_bert_embed_f32's order, then the launches.  who: "<entry>: ";
+// ws_query: the entry's workspace query, named in the workspace message.
+template <typename P>
+int be_embed(const std::string& who, const char* ws_query, const P* p, const int64_t* input_ids,
+             const int64_t* attention_mask, const int64_t* token_type_ids, int64_t B, int32_t S, int32_t pooling,
+             float* pooled_out, float* hidden_out, void* workspace, size_t workspace_bytes, void* stream) {
+  clear_error();
+  if (const char* why = be_check(p, B, S)) return fail(!p || B < 0 ? GR_ERR_ARG : GR_ERR_UNSUPPORTED, who + why);
+  if (pooling != GR_BERT_POOL_NONE && pooling != GR_BERT_POOL_MEAN_NO_CLS && pooling != GR_BERT_POOL_CLS)
+    return fail(GR_ERR_ARG, who + "pooling must be GR_BERT_POOL_NONE, _MEAN_NO_CLS or _CLS");
+  if (B == 0) return GR_OK;
+  if (!workspace || workspace_bytes < be_bytes(p, B, S) || !aligned16(workspace))
+    return fail(GR_ERR_WORKSPACE, who + "workspace missing, misaligned or smaller than " + ws_query);
+  if (!input_ids) return fail(GR_ERR_ARG, who + "input_ids is null");
+  if (pooling != GR_BERT_POOL_NONE && !pooled_out) return fail(GR_ERR_ARG, who + "pooled_out is null");
+  if (pooling == GR_BERT_POOL_NONE && !hidden_out)
+    return fail(GR_ERR_ARG, who + "hidden_out is null and pooling is GR_BERT_POOL_NONE: nothing to compute");
+  if (hidden_out && !aligned16(hidden_out)) return fail(GR_ERR_ARG, who + "hidden_out must be 16-byte aligned");
+  if (!be_weights_ok(p)) return fail(GR_ERR_ARG, who + "a weight pointer is null or not 16-byte aligned");
+
+  const int H = p->hidden_size;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const BeRows none = {nullptr, nullptr, nullptr, nullptr};
+  const float* last = nullptr;
+  if (int rc = be_forward<false>(p, input_ids, attention_mask, token_type_ids, B, S, B * S, workspace, hidden_out, &last,
+                                 st, none))
+    return rc;
+  be_pool_kernel<false><<<dim3((unsigned)B, (unsigned)((H + 255) / 256)), dim3(256), 0, st>>>(
+      last, attention_mask, S, H, pooling, pooled_out, hidden_out, none);
+  return check_launch("be_pool_kernel");
+}
+
+// The ragged entries' body, likewise.
+template <typename P>
+int be_embed_ragged(const std::string& who, const char* ws_query, const P* p, const int64_t* input_ids,
+                    const int64_t* attention_mask, const int64_t* token_type_ids, int64_t B, int32_t S,
+                    int64_t rows_bound, int32_t pooling, float* pooled_out, float* hidden_rows_out,
+                    int64_t* row_offsets_out, void* workspace, size_t workspace_bytes, void* stream) {
+  clear_error();
+  if (const char* why = be_check(p, B, S)) return fail(!p || B < 0 ? GR_ERR_ARG : GR_ERR_UNSUPPORTED, who + why);
+  if (B > 0 && rows_bound < 1) return fail(GR_ERR_ARG, who + "rows_bound must be at least 1");
+  if (pooling != GR_BERT_POOL_NONE && pooling != GR_BERT_POOL_MEAN_NO_CLS && pooling != GR_BERT_POOL_CLS)
+    return fail(GR_ERR_ARG, who + "pooling must be GR_BERT_POOL_NONE, _MEAN_NO_CLS or _CLS");
+  if (B == 0) return GR_OK;
+  const BeRagged R = be_ragged(p, B, S, rows_bound);
+  if (!workspace || workspace_bytes < R.bytes || !aligned16(workspace))
+    return fail(GR_ERR_WORKSPACE, who + "workspace missing, misaligned or smaller than " + ws_query);
+  if (!input_ids) return fail(GR_ERR_ARG, who + "input_ids is null");
+  if (pooling != GR_BERT_POOL_NONE && !pooled_out) return fail(GR_ERR_ARG, who + "pooled_out is null");
+  if (pooling == GR_BERT_POOL_NONE && (!hidden_rows_out || !row_offsets_out))
+    return fail(GR_ERR_ARG, who + "hidden_rows_out or row_offsets_out is null and pooling is GR_BERT_POOL_NONE: "
+                                  "nothing to compute");
+  if (hidden_rows_out && !aligned16(hidden_rows_out))
+    return fail(GR_ERR_ARG, who + "hidden_rows_out must be 16-byte aligned");
+  if (!be_weights_ok(p)) return fail(GR_ERR_ARG, who + "a weight pointer is null or not 16-byte aligned");
+
+  const int H = p->hidden_size;
+  char* wb = static_cast<char*>(workspace);
+  int64_t* off = reinterpret_cast<int64_t*>(wb + R.off);
+  int64_t* total = reinterpret_cast<int64_t*>(wb + R.total);
+  int32_t* flag = reinterpret_cast<int32_t*>(wb + R.total + sizeof(int64_t));
+  int32_t* len = reinterpret_cast<int32_t*>(wb + R.len);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const BeRows rg = {len, off, total, flag};
+
+  be_len_kernel<<<dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st>>>(attention_mask, B, S, len);
+  if (int rc = check_launch("be_len_kernel")) return rc;
+  be_offsets_kernel<<<dim3(1), dim3(BE_SCAN_NT), 0, st>>>(len, B, R.rows, off, total, flag, row_offsets_out);
+  if (int rc = check_launch("be_offsets_kernel")) return rc;
+  const float* last = nullptr;
+  if (int rc = be_forward<true>(p, input_ids, attention_mask, token_type_ids, B, S, R.rows, workspace, hidden_rows_out,
+                                &last, st, rg))
+    return rc;
+  be_pool_kernel<true><<<dim3((unsigned)B, (unsigned)((H + 255) / 256)), dim3(256), 0, st>>>(
+      last, attention_mask, S, H, pooling, pooled_out, nullptr, rg);
+  return check_launch("be_pool_kernel");
 }
 
 }  // namespace
@@ -679,38 +1219,8 @@ extern "C" int gr_bert_embed_f32(const gr_bert_params* p, const int64_t* input_i
                                  const int64_t* token_type_ids, int64_t B, int32_t S, int32_t pooling,
                                  float* pooled_out, float* hidden_out, void* workspace, size_t workspace_bytes,
                                  void* stream) {
-  using namespace gr;
-  clear_error();
-  const std::string who = "gr_bert_embed_f32: ";
-  if (const char* why = be_check(p, B, S)) return fail(!p || B < 0 ? GR_ERR_ARG : GR_ERR_UNSUPPORTED, who + why);
-  if (pooling != GR_BERT_POOL_NONE && pooling != GR_BERT_POOL_MEAN_NO_CLS && pooling != GR_BERT_POOL_CLS)
-    return fail(GR_ERR_ARG, who + "pooling must be GR_BERT_POOL_NONE, _MEAN_NO_CLS or _CLS");
-  if (B == 0) return GR_OK;
-  if (!workspace || workspace_bytes < be_bytes(p, B, S) || !aligned16(workspace))
-    return fail(GR_ERR_WORKSPACE, who + "workspace missing, misaligned or smaller than gr_bert_embed_workspace_bytes");
-  if (!input_ids) return fail(GR_ERR_ARG, who + "input_ids is null");
-  if (pooling != GR_BERT_POOL_NONE && !pooled_out) return fail(GR_ERR_ARG, who + "pooled_out is null");
-  if (pooling == GR_BERT_POOL_NONE && !hidden_out)
-    return fail(GR_ERR_ARG, who + "hidden_out is null and pooling is GR_BERT_POOL_NONE: nothing to compute");
-  if (hidden_out && !aligned16(hidden_out)) return fail(GR_ERR_ARG, who + "hidden_out must be 16-byte aligned");
-  if (!be_weights_ok(p)) return fail(GR_ERR_ARG, who + "a weight pointer is null or not 16-byte aligned");
-
-  const int H = p->hidden_size;
-  const int64_t M = B * S;
-  const BeLayout L = be_layout(p, B, S);
-  float* ws = static_cast<float*>(workspace);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const BeRows none = {nullptr, nullptr, nullptr, nullptr};
-
-  be_embed_ln_kernel<false><<<dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st>>>(
-      input_ids, token_type_ids, p->word, p->position, p->token_type, p->emb_ln_w, p->emb_ln_b, p->eps, p->vocab_size,
-      p->type_vocab_size, S, H, M, ws + L.x, none);
-  if (int rc = check_launch("be_embed_ln_kernel")) return rc;
-  float* last = hidden_out ? hidden_out : ws + L.x;
-  if (int rc = be_stack<false>(p, attention_mask, B, S, M, ws, L, last, st, none)) return rc;
-  be_pool_kernel<false><<<dim3((unsigned)B, (unsigned)((H + 255) / 256)), dim3(256), 0, st>>>(
-      last, attention_mask, S, H, pooling, pooled_out, hidden_out, none);
-  return check_launch("be_pool_kernel");
+  return gr::be_embed("gr_bert_embed_f32: ", "gr_bert_embed_workspace_bytes", p, input_ids, attention_mask,
+                      token_type_ids, B, S, pooling, pooled_out, hidden_out, workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t gr_bert_embed_ragged_workspace_bytes(const gr_bert_params* p, int64_t B, int32_t S,
@@ -724,50 +1234,37 @@ extern "C" int gr_bert_embed_ragged_f32(const gr_bert_params* p, const int64_t* 
                                         int32_t S, int64_t rows_bound, int32_t pooling, float* pooled_out,
                                         float* hidden_rows_out, int64_t* row_offsets_out, void* workspace,
                                         size_t workspace_bytes, void* stream) {
-  using namespace gr;
-  clear_error();
-  const std::string who = "gr_bert_embed_ragged_f32: ";
-  if (const char* why = be_check(p, B, S)) return fail(!p || B < 0 ? GR_ERR_ARG : GR_ERR_UNSUPPORTED, who + why);
-  if (B > 0 && rows_bound < 1) return fail(GR_ERR_ARG, who + "rows_bound must be at least 1");
-  if (pooling != GR_BERT_POOL_NONE && pooling != GR_BERT_POOL_MEAN_NO_CLS && pooling != GR_BERT_POOL_CLS)
-    return fail(GR_ERR_ARG, who + "pooling must be GR_BERT_POOL_NONE, _MEAN_NO_CLS or _CLS");
-  if (B == 0) return GR_OK;
-  const BeRagged R = be_ragged(p, B, S, rows_bound);
-  if (!workspace || workspace_bytes < R.bytes || !aligned16(workspace))
-    return fail(GR_ERR_WORKSPACE,
-                who + "workspace missing, misaligned or smaller than gr_bert_embed_ragged_workspace_bytes");
-  if (!input_ids) return fail(GR_ERR_ARG, who + "input_ids is null");
-  if (pooling != GR_BERT_POOL_NONE && !pooled_out) return fail(GR_ERR_ARG, who + "pooled_out is null");
-  if (pooling == GR_BERT_POOL_NONE && (!hidden_rows_out || !row_offsets_out))
-    return fail(GR_ERR_ARG, who + "hidden_rows_out or row_offsets_out is null and pooling is GR_BERT_POOL_NONE: "
-                                  "nothing to compute");
-  if (hidden_rows_out && !aligned16(hidden_rows_out))
-    return fail(GR_ERR_ARG, who + "hidden_rows_out must be 16-byte aligned");
-  if (!be_weights_ok(p)) return fail(GR_ERR_ARG, who + "a weight pointer is null or not 16-byte aligned");
-
-  const int H = p->hidden_size;
-  const BeLayout L = be_layout_rows(p, (size_t)R.rows);
-  float* ws = static_cast<float*>(workspace);
-  char* wb = static_cast<char*>(workspace);
-  int64_t* off = reinterpret_cast<int64_t*>(wb + R.off);
-  int64_t* total = reinterpret_cast<int64_t*>(wb + R.total);
-  int32_t* flag = reinterpret_cast<int32_t*>(wb + R.total + sizeof(int64_t));
-  int32_t* len = reinterpret_cast<int32_t*>(wb + R.len);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const BeRows rg = {len, off, total, flag};
-
-  be_len_kernel<<<dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st>>>(attention_mask, B, S, len);
-  if (int rc = check_launch("be_len_kernel")) return rc;
-  be_offsets_kernel<<<dim3(1), dim3(BE_SCAN_NT), 0, st>>>(len, B, R.rows, off, total, flag, row_offsets_out);
-  if (int rc = check_launch("be_offsets_kernel")) return rc;
-  // B x ceil(S / 4) <= 65536 x 128 workgroups
-  be_embed_ln_kernel<true><<<dim3((unsigned)B, (unsigned)((S + 3) / 4)), dim3(256), 0, st>>>(
-      input_ids, token_type_ids, p->word, p->position, p->token_type, p->emb_ln_w, p->emb_ln_b, p->eps, p->vocab_size,
-      p->type_vocab_size, S, H, R.rows, ws + L.x, rg);
-  if (int rc = check_launch("be_embed_ln_kernel")) return rc;
-  float* last = hidden_rows_out ? hidden_rows_out : ws + L.x;
-  if (int rc = be_stack<true>(p, attention_mask, B, S, R.rows, ws, L, last, st, rg)) return rc;
-  be_pool_kernel<true><<<dim3((unsigned)B, (unsigned)((H + 255) / 256)), dim3(256), 0, st>>>(
-      last, attention_mask, S, H, pooling, pooled_out, nullptr, rg);
-  return check_launch("be_pool_kernel");
+  return gr::be_embed_ragged("gr_bert_embed_ragged_f32: ", "gr_bert_embed_ragged_workspace_bytes", p, input_ids,
+                             attention_mask, token_type_ids, B, S, rows_bound, pooling, pooled_out, hidden_rows_out,
+                             row_offsets_out, workspace, workspace_bytes, stream);
 }
+
+extern "C" size_t gr_bert_embed_bf16_workspace_bytes(const gr_bert_bf16_params* p, int64_t B, int32_t S) {
+  if (gr::be_check(p, B, S)) return 0;
+  return gr::be_bytes(p, B, S);
+}
+
+extern "C" int gr_bert_embed_bf16(const gr_bert_bf16_params* p, const int64_t* input_ids,
+                                  const int64_t* attention_mask, const int64_t* token_type_ids, int64_t B, int32_t S,
+                                  int32_t pooling, float* pooled_out, float* hidden_out, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+  return gr::be_embed("gr_bert_embed_bf16: ", "gr_bert_embed_bf16_workspace_bytes", p, input_ids, attention_mask,
+                      token_type_ids, B, S, pooling, pooled_out, hidden_out, workspace, workspace_bytes, stream);
+}
+
+extern "C" size_t gr_bert_embed_ragged_bf16_workspace_bytes(const gr_bert_bf16_params* p, int64_t B, int32_t S,
+                                                            int64_t rows_bound) {
+  if (gr::be_check(p, B, S) || (B > 0 && rows_bound < 1)) return 0;
+  return gr::be_ragged(p, B, S, rows_bound).bytes;
+}
+
+extern "C" int gr_bert_embed_ragged_bf16(const gr_bert_bf16_params* p, const int64_t* input_ids,
+                                         const int64_t* attention_mask, const int64_t* token_type_ids, int64_t B,
+                                         int32_t S, int64_t rows_bound, int32_t pooling, float* pooled_out,
+                                         float* hidden_rows_out, int64_t* row_offsets_out, void* workspace,
+                                         size_t workspace_bytes, void* stream) {
+  return gr::be_embed_ragged("gr_bert_embed_ragged_bf16: ", "gr_bert_embed_ragged_bf16_workspace_bytes", p, input_ids,
+                             attention_mask, token_type_ids, B, S, rows_bound, pooling, pooled_out, hidden_rows_out,
+                             row_offsets_out, workspace, workspace_bytes, stream);
+}
+

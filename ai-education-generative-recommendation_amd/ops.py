@@ -2157,6 +2157,8 @@ class BertBinding:
     ``BertModel``'s names (``embeddings.word_embeddings.weight``, ``encoder.layer.0.attention.self.query.weight``,
     ...; the pooler is not read).  The pointers are the tensors' own storage, so in-place weight updates are
     seen by the next call."""
+    ENTRY, WS_QUERY = "gr_bert_embed_f32", "gr_bert_embed_workspace_bytes"
+    RAGGED_ENTRY, RAGGED_WS_QUERY = "gr_bert_embed_ragged_f32", "gr_bert_embed_ragged_workspace_bytes"
 
     def __init__(self, cfg, tensors):
         bert_check(cfg)
@@ -2200,14 +2202,44 @@ class BertBinding:
     def workspace_bytes(self, B, S):
         n = self._ws.get((B, S))
         if n is None:
-            n = self._ws[(B, S)] = L.lib().gr_bert_embed_workspace_bytes(self.ref, B, S)
+            n = self._ws[(B, S)] = getattr(L.lib(), self.WS_QUERY)(self.ref, B, S)
         return n
 
     def ragged_workspace_bytes(self, B, S, rows_bound):
         n = self._ws.get((B, S, rows_bound))
         if n is None:
-            n = self._ws[(B, S, rows_bound)] = L.lib().gr_bert_embed_ragged_workspace_bytes(self.ref, B, S, rows_bound)
+            n = self._ws[(B, S, rows_bound)] = getattr(L.lib(), self.RAGGED_WS_QUERY)(self.ref, B, S, rows_bound)
         return n
+
+
+class BertBf16Binding(BertBinding):
+    """``gr_bert_bf16_params``: the bf16 precision of the same encoder (bf16 GEMM operands, fp32 accumulation and
+    epilogues; the contract is in include/gr_amd.h).  ``tensors``: the float32 tensors ``BertBinding`` takes.  The six
+    matrices per layer are rounded once, here, with ``tensor.to(torch.bfloat16)`` (round-to-nearest-even) and kept
+    alive by the binding: it is a SNAPSHOT of them, so a later in-place change to a matrix is not seen until a new
+    binding is made (``BertEncoder.binding_bf16`` does that).  Tables, biases and LayerNorm parameters stay the
+    tensors' own float32 storage.  ``ops.bert_embed`` and ``ops.bert_embed_ragged`` take it in ``BertBinding``'s
+    place and call ``gr_bert_embed_bf16`` / ``gr_bert_embed_ragged_bf16``."""
+    ENTRY, WS_QUERY = "gr_bert_embed_bf16", "gr_bert_embed_bf16_workspace_bytes"
+    RAGGED_ENTRY, RAGGED_WS_QUERY = "gr_bert_embed_ragged_bf16", "gr_bert_embed_ragged_bf16_workspace_bytes"
+    MATRICES = tuple(i for i, k in enumerate(BERT_LAYER_KEYS) if k.endswith(".weight") and "LayerNorm" not in k)
+
+    def __init__(self, cfg, tensors):
+        super().__init__(cfg, tensors)
+        f32 = self.params
+        p = L.BertBf16Params()
+        for name, _ in L.BertParams._fields_[:-1]:
+            setattr(p, name, getattr(f32, name))
+        vectors = [i for i in range(len(BERT_LAYER_KEYS)) if i not in self.MATRICES]
+        for l in range(p.num_layers):
+            for j, i in enumerate(self.MATRICES):
+                m = tensors[f"encoder.layer.{l}.{BERT_LAYER_KEYS[i]}"].to(torch.bfloat16).contiguous()
+                self.keep.append(m)
+                p.matrix[l][j] = m.data_ptr()
+            for j, i in enumerate(vectors):
+                p.vector[l][j] = f32.layer[l][i]
+        self.params = p
+        self.ref = ctypes.byref(p)
 
 
 def _bert_ids(name, t, B, S):
@@ -2221,6 +2253,8 @@ def _bert_ids(name, t, B, S):
 
 def bert_embed(binding, input_ids, attention_mask=None, token_type_ids=None, pooling="mean_no_cls", with_hidden=False):
     """``gr_bert_embed_f32``: embeddings, the encoder stack and the pooling in one C call, nothing synchronises.
+    The binding's type picks the precision: a ``BertBf16Binding`` calls ``gr_bert_embed_bf16`` (the outputs are
+    float32 either way).
     input_ids [B, S]; attention_mask [B, S] (0 = not a key, not pooled; None: all live); token_type_ids [B, S] or
     None (zeros).  pooling "mean_no_cls" (the live rows after position 0, 0 when there is none), "cls" (row 0) or
     None -> pooled [B, H][, hidden [B, S, H] with ``with_hidden``], or hidden alone when pooling is None.  A
@@ -2246,9 +2280,9 @@ def bert_embed(binding, input_ids, attention_mask=None, token_type_ids=None, poo
         nbytes = binding.workspace_bytes(B, S)
         wsp = L.workspace(nbytes, dev)
         with L.on(dev):
-            L.check(L.lib().gr_bert_embed_f32(binding.ref, L.ptr(input_ids), L.ptr(attention_mask),
-                                              L.ptr(token_type_ids), B, S, mode, L.ptr(pooled), L.ptr(hidden),
-                                              L.ptr(wsp), nbytes, L.stream_of(dev)), "gr_bert_embed_f32")
+            L.check(getattr(L.lib(), binding.ENTRY)(binding.ref, L.ptr(input_ids), L.ptr(attention_mask),
+                                                    L.ptr(token_type_ids), B, S, mode, L.ptr(pooled), L.ptr(hidden),
+                                                    L.ptr(wsp), nbytes, L.stream_of(dev)), binding.ENTRY)
     if pooled is None:
         return hidden
     return (pooled, hidden) if with_hidden else pooled
@@ -2257,7 +2291,8 @@ def bert_embed(binding, input_ids, attention_mask=None, token_type_ids=None, poo
 def bert_embed_ragged(binding, input_ids, attention_mask=None, token_type_ids=None, pooling="mean_no_cls", rows_bound=None,
                       with_hidden=False):
     """``gr_bert_embed_ragged_f32``: ``bert_embed`` over rows ``[0, len_b)`` of each sequence only (``len_b``: one past
-    its last live position), packed; the pooled vectors and the kept rows have ``bert_embed``'s bits.  ``rows_bound``:
+    its last live position), packed; the pooled vectors and the kept rows have ``bert_embed``'s bits (a
+    ``BertBf16Binding`` calls ``gr_bert_embed_ragged_bf16``: the bits of ``bert_embed`` on that binding).  ``rows_bound``:
     an upper bound on the packed row count ``sum(len_b)`` -- ``bert_embed.row_bound`` gives it for a host-side mask;
     None means B * S, which is always safe; 0 (no sequence has a live key) is passed on as 1.  Nothing synchronises: the row count stays on the device, and a bound
     below it shows as NaN in every pooled element and -1 in the last offset.
@@ -2289,10 +2324,10 @@ def bert_embed_ragged(binding, input_ids, attention_mask=None, token_type_ids=No
         nbytes = binding.ragged_workspace_bytes(B, S, rows)
         wsp = L.workspace(nbytes, dev)
         with L.on(dev):
-            L.check(L.lib().gr_bert_embed_ragged_f32(binding.ref, L.ptr(input_ids), L.ptr(attention_mask),
-                                                     L.ptr(token_type_ids), B, S, rows, mode, L.ptr(pooled),
-                                                     L.ptr(hidden), L.ptr(offsets), L.ptr(wsp), nbytes,
-                                                     L.stream_of(dev)), "gr_bert_embed_ragged_f32")
+            L.check(getattr(L.lib(), binding.RAGGED_ENTRY)(binding.ref, L.ptr(input_ids), L.ptr(attention_mask),
+                                                           L.ptr(token_type_ids), B, S, rows, mode, L.ptr(pooled),
+                                                           L.ptr(hidden), L.ptr(offsets), L.ptr(wsp), nbytes,
+                                                           L.stream_of(dev)), binding.RAGGED_ENTRY)
     if pooled is None:
         return hidden, offsets
     return (pooled, hidden, offsets) if with_hidden else pooled

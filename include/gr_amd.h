@@ -92,7 +92,7 @@ const char* gr_last_error(void);
  *   "bert_tile"     0 (default): each GEMM of gr_bert_embed_f32 takes, of 128 x 128, 64 x 128 and
  *                   128 x 96 outputs per workgroup, the tile that leaves the fewest compute units idle at
  *                   its shape; 1 / 2 / 3: that tile on every GEMM.  One summation order: bitwise the
- *                   same results.
+ *                   same results.  The bf16 entries' GEMMs take the same tiles the same way.
  * The final block of a last-position forward (predict, last_hidden; gr_sasrec_plan reports the
  * choice): the H form when the tail kernel takes the shape (d / 4, head width / 4 and mlp / 4 powers
  * of two, at most 8 heads, d and mlp <= 256, 16-byte aligned weights); otherwise the pruned final
@@ -958,6 +958,71 @@ int gr_bert_embed_ragged_f32(const gr_bert_params* p, const int64_t* input_ids, 
                              const int64_t* token_type_ids, int64_t B, int32_t S, int64_t rows_bound,
                              int32_t pooling, float* pooled_out, float* hidden_rows_out,
                              int64_t* row_offsets_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The same encoder with bf16 GEMM operands and fp32 accumulation: an opt-in second precision.  The fp32
+ * entries above keep their kernels and their bits.  bf16 = the upper 16 bits of the RNE-rounded fp32.
+ *
+ * Numerics contract:
+ *   GEMM operands: the A and B operands of the four projections per layer (the fused q/k/v, the attention
+ *     output, the intermediate and the output projection) are bf16, round-to-nearest-even from fp32;
+ *     accumulation is fp32 in the MFMA accumulator.
+ *   Epilogues: bias, exact-erf GELU, residual add, both LayerNorms (two-pass), the softmax's max / exp / sum
+ *     and the pooling are fp32.
+ *   Residual stream: it and the last hidden state stay fp32; pooled_out and hidden_out are float arrays
+ *     exactly as above.
+ *   q, k, v: rounded to bf16 once, in the q/k/v GEMM's epilogue, and stored as bf16.
+ *   Scores: fp32 from a bf16 MFMA; the 1 / sqrt(head_dim) scale is applied in fp32.
+ *   Probabilities: rounded to bf16 where they become the P . v operand: the online softmax rounds the
+ *     un-normalised exp(s - running max), and the row sum is taken in fp32 from the same rounded values, so
+ *     a row's weights sum to 1 within fp32.
+ *   Masking: unchanged: a masked key has probability exactly 0, key tiles with no live key are skipped, a
+ *     sequence with no live key gives zeros, masks with holes are legal.
+ *   Context and GELU outputs: written as bf16 (they are only ever GEMM A operands).  Each LayerNorm writes
+ *     its fp32 row for the residual and a bf16 copy for the next GEMM.
+ *   Weights: the six [out, in] matrices per layer are bf16; embedding tables, biases and LayerNorm
+ *     parameters stay fp32.
+ *   Determinism: every output element has one summation order, which depends on neither B nor the row's
+ *     position in a tile nor the tile chosen; no atomics.  A call is bitwise repeatable and batch-invariant,
+ *     and the ragged form returns the padded form's bits.
+ * Not built: fp16, fp8, a bf16 last hidden state, bf16 embedding tables, training.
+ *
+ * gr_bert_bf16_params: gr_bert_params' dimensions and fp32 tables;
+ *   matrix[l] = {query, key, value, attention.output.dense, intermediate.dense, output.dense}.weight, bf16
+ *     [out, in] row-major;
+ *   vector[l] = {query.bias, key.bias, value.bias, attention.output.dense.bias, attention.output.LayerNorm.weight,
+ *     .bias, intermediate.dense.bias, output.dense.bias, output.LayerNorm.weight, .bias}, fp32;
+ *   each 16-byte aligned.
+ * gr_bert_embed_bf16 and gr_bert_embed_ragged_bf16 take gr_bert_embed_f32's and gr_bert_embed_ragged_f32's
+ * arguments.  The envelope, the clamping, the argument checks, the error codes and their order are those
+ * entries'; messages start with the bf16 entry's name; a rows_bound below the mask's count shows the same
+ * way (NaN in pooled_out, -1 in the last offset).  Launches: as the fp32 entries.
+ * workspace (16-byte aligned; 0 from the query outside the envelope), R rows (B * S, or min(rows_bound, B * S)):
+ *   R (18 H + 2 intermediate_size) bytes, each of its six parts rounded up to 16, + 16: the fp32 residual
+ *   stream and pre-LayerNorm sum, and the bf16 copies of x, q/k/v, the context and the GELU output; the
+ *   ragged query adds up16(8 (B + 1)) + 16 + up16(4 B). */
+typedef struct gr_bert_bf16_params {
+  int32_t vocab_size, hidden_size, num_heads, head_dim, intermediate_size, num_layers, max_position,
+      type_vocab_size, hidden_act, position_type;
+  float eps, reserved;
+  const float* word;
+  const float* position;
+  const float* token_type;
+  const float* emb_ln_w;
+  const float* emb_ln_b;
+  const uint16_t* matrix[GR_BERT_MAX_LAYERS][6];
+  const float* vector[GR_BERT_MAX_LAYERS][10];
+} gr_bert_bf16_params;
+
+size_t gr_bert_embed_bf16_workspace_bytes(const gr_bert_bf16_params* p, int64_t B, int32_t S);
+int gr_bert_embed_bf16(const gr_bert_bf16_params* p, const int64_t* input_ids, const int64_t* attention_mask,
+                       const int64_t* token_type_ids, int64_t B, int32_t S, int32_t pooling, float* pooled_out,
+                       float* hidden_out, void* workspace, size_t workspace_bytes, void* stream);
+size_t gr_bert_embed_ragged_bf16_workspace_bytes(const gr_bert_bf16_params* p, int64_t B, int32_t S,
+                                                 int64_t rows_bound);
+int gr_bert_embed_ragged_bf16(const gr_bert_bf16_params* p, const int64_t* input_ids, const int64_t* attention_mask,
+                              const int64_t* token_type_ids, int64_t B, int32_t S, int64_t rows_bound,
+                              int32_t pooling, float* pooled_out, float* hidden_rows_out,
+                              int64_t* row_offsets_out, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -7,6 +7,11 @@ torch on the same GPU in the same process with the same weights.
     rocprofv3 --kernel-trace --stats ... -- python scripts/time_bert_embed.py --only-kernels   (per-kernel shares)
     python scripts/time_bert_embed.py --ragged [--out profiles/r23/bert_embed_ragged.txt]
     python scripts/time_bert_embed.py --padded-only       (the padded call alone: for a build of another commit)
+    python scripts/time_bert_embed.py --bf16 [--ragged] [--out profiles/r24/bert_embed_bf16.txt]
+    rocprofv3 --kernel-trace --stats ... -- python scripts/time_bert_embed.py --only-kernels --bf16
+
+``--bf16``: the bf16 precision (``embed(..., precision="bf16")``: bf16 GEMM operands, fp32 accumulation) next to the fp32
+call on the same inputs in the same process; with ``--ragged`` the ragged entry of both precisions as well.
 
 ``--ragged``: the ragged entry (``embed(..., ragged=True)``: only the rows up to each sequence's last live position)
 next to the padded call on the same inputs in the same process, for two length distributions -- one sequence of S
@@ -116,6 +121,41 @@ def ragged_report(model, a, dev):
     return res
 
 
+def bf16_report(model, a, dev):
+    """The bf16 precision next to the fp32 call on the same inputs in the same process, interleaved: the padded calls,
+    and with ``--ragged`` the ragged calls with the exact row bound as well."""
+    res = {"config": {k: CONFIG[k] for k in ("hidden_size", "num_hidden_layers", "num_attention_heads", "intermediate_size")},
+           "device": torch.cuda.get_device_name(0), "timing": f"one pair of events per call, median of {a.reps} calls "
+           "after 5 warm-up calls, quartiles beside it", "shapes": []}
+    for S in a.positions:
+        ids, mask = inputs(a.batch, S, dev)
+        total, proj, attn = macs(a.batch, S)
+        exact = gr_amd.bert_embed.row_bound(mask.cpu())
+        row = {"B": a.batch, "S": S, "lengths": "one of S, the others uniform on S/2..S", "multiply_adds_per_call": total,
+               "projection_multiply_adds": proj, "attention_multiply_adds": attn, "kept_rows": exact}
+        fp32 = lambda: model.embed(ids, mask)
+        bf16 = lambda: model.embed(ids, mask, precision="bf16")
+        a32, a16 = fp32(), bf16()
+        row["bf16_max_difference_from_fp32_over_max"] = float((a16 - a32).abs().max()) / float(a32.abs().max())
+        row["fp32_padded"] = timed(fp32, a.reps, 5)
+        row["bf16_padded"] = timed(bf16, a.reps, 5)
+        row["fp32_padded_again"] = timed(fp32, a.reps, 5)                  # the drift of the run itself
+        row["bf16_over_fp32_padded"] = row["bf16_padded"]["median_ms"] / row["fp32_padded"]["median_ms"]
+        row["fp32_over_bf16_padded"] = row["fp32_padded"]["median_ms"] / row["bf16_padded"]["median_ms"]
+        row["bf16_padded_tflops"] = 2 * total / (row["bf16_padded"]["median_ms"] * 1e-3) / 1e12
+        row["fp32_padded_tflops"] = 2 * total / (row["fp32_padded"]["median_ms"] * 1e-3) / 1e12
+        if a.ragged:
+            r32 = lambda: model.embed(ids, mask, ragged=True, rows_bound=exact)
+            r16 = lambda: model.embed(ids, mask, ragged=True, rows_bound=exact, precision="bf16")
+            row["ragged_same_bits"] = bool(torch.equal(r32(), a32) and torch.equal(r16(), a16))
+            row["fp32_ragged"] = timed(r32, a.reps, 5)
+            row["bf16_ragged"] = timed(r16, a.reps, 5)
+            row["bf16_over_fp32_ragged"] = row["bf16_ragged"]["median_ms"] / row["fp32_ragged"]["median_ms"]
+            row["bf16_ragged_over_bf16_padded"] = row["bf16_ragged"]["median_ms"] / row["bf16_padded"]["median_ms"]
+        res["shapes"].append(row)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
@@ -124,6 +164,7 @@ def main():
     ap.add_argument("--only-kernels", action="store_true", help="a few calls of the kernels alone (for a kernel trace)")
     ap.add_argument("--ragged", action="store_true", help="the ragged entry next to the padded call")
     ap.add_argument("--padded-only", action="store_true", help="the padded call alone")
+    ap.add_argument("--bf16", action="store_true", help="the bf16 precision next to the fp32 call (with --ragged: both entries)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -132,12 +173,18 @@ def main():
         for S in a.positions:
             ids, mask = inputs(a.batch, S, dev)
             exact = gr_amd.bert_embed.row_bound(mask.cpu()) if a.ragged else None
+            precision = "bf16" if a.bf16 else "fp32"
             for _ in range(5):
-                model.embed(ids, mask, ragged=True, rows_bound=exact) if a.ragged else model.embed(ids, mask)
+                if a.ragged:
+                    model.embed(ids, mask, ragged=True, rows_bound=exact, precision=precision)
+                else:
+                    model.embed(ids, mask, precision=precision)
         torch.cuda.synchronize()
         return
-    if a.ragged or a.padded_only:
-        if a.ragged:
+    if a.bf16 or a.ragged or a.padded_only:
+        if a.bf16:
+            res = bf16_report(model, a, dev)
+        elif a.ragged:
             res = ragged_report(model, a, dev)
         else:
             res = {"device": torch.cuda.get_device_name(0), "shapes": []}
