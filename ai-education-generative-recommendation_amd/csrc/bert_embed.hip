@@ -68,6 +68,13 @@
 //       B columns are queries); the probability registers, rounded pairwise, are the B operand of
 //       O^T = V^T . P^T, so a query's running max, sum and output column all sit in its own lane; v is staged
 //       transposed, its keys in the order the accumulator's registers hold them.
+//   workspace on return   what a test may read after the call; not an interface for callers.  The six parts of
+//       BeLayout16, in order, each rounded up to 16 bytes, hold the LAST layer's intermediates over R rows (B * S, or
+//       the packed rows): x fp32 [R, H] the post-attention LayerNorm output (the final hidden state instead when
+//       hidden_out is NULL); t fp32 [R, H] x + output.dense(ff) + bias, the final LayerNorm's input; x16 bf16 [R, H]
+//       the RNE copy of the final LayerNorm's fp32 rows (be_pool_kernel zeroes hidden_out alone for a sequence with no
+//       live key); qkv bf16 [R, 3H] q | k | v; ctx bf16 [R, H] the attention context; ff bf16 [R, I] the GELU output.
+//       tests/bert_bf16_stages.py checks each stage in float64 on these operands.
 #include <type_traits>
 
 #include "gr_common.h"

@@ -999,7 +999,19 @@ int gr_bert_embed_ragged_f32(const gr_bert_params* p, const int64_t* input_ids, 
  * workspace (16-byte aligned; 0 from the query outside the envelope), R rows (B * S, or min(rows_bound, B * S)):
  *   R (18 H + 2 intermediate_size) bytes, each of its six parts rounded up to 16, + 16: the fp32 residual
  *   stream and pre-LayerNorm sum, and the bf16 copies of x, q/k/v, the context and the GELU output; the
- *   ragged query adds up16(8 (B + 1)) + 16 + up16(4 B). */
+ *   ragged query adds up16(8 (B + 1)) + 16 + up16(4 B).
+ *   What a test may read after the call; not an interface for callers.  The six parts lie in this order from the
+ *   workspace's start, each rounded up to 16 bytes, and on return hold the LAST layer's intermediates (R rows: B * S,
+ *   or the packed rows in the ragged form; rows from the packed total on are not written):
+ *     x    fp32 [R, H]   the last layer's post-attention LayerNorm output; with hidden_out NULL the final hidden
+ *                        state instead
+ *     t    fp32 [R, H]   the last layer's x + output.dense(ff) + bias, the input of the final LayerNorm
+ *     x16  bf16 [R, H]   the RNE copy of the final LayerNorm's fp32 rows (not zeroed for a sequence with no live
+ *                        key: only hidden_out is)
+ *     qkv  bf16 [R, 3H]  the last layer's q | k | v
+ *     ctx  bf16 [R, H]   the last layer's attention context
+ *     ff   bf16 [R, I]   the last layer's GELU output
+ *   tests/bert_bf16_stages.py checks each stage in float64 on these operands. */
 typedef struct gr_bert_bf16_params {
   int32_t vocab_size, hidden_size, num_heads, head_dim, intermediate_size, num_layers, max_position,
       type_vocab_size, hidden_act, position_type;

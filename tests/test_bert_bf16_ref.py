@@ -5,8 +5,10 @@ from the float64 run -- can tell apart.
 Documented limits, asserted nowhere: a dropped key bias is not detectable by any tolerance (it adds q . b_k to every
 score of a row, and the softmax is invariant under a per-row shift; in exact arithmetic the output does not change),
 and tanh-GELU for the exact erf-GELU is not detectable by this one (measured: its distance from float64 stays within
-about 1.2 x the exact restatement's).  Against the second the guarantee is structural: the bf16 GEMM kernel and the
-float32 one call the same ``be_epilogue`` device function.
+about 1.2 x the exact restatement's).  The second IS detected by the per-stage checks on the call's own operands
+(tests/bert_bf16_stages.py, test_bert_bf16_stages_gpu.py; shown on the CPU in test_bert_bf16_stages_ref.py: 7-9 % of the
+GELU stage's elements fall outside the rounding bound), as are truncation for RNE, a row sum from unrounded weights and
+normalise-then-round, which this end-to-end tolerance cannot see either.
 """
 import pytest
 import torch
