@@ -214,6 +214,10 @@ SIGNATURES = {
     "gr_beam_hits_i64": (ctypes.c_int, [_vp, _i64, _i32, _i32, _i64, _vp, _i32, _vp, _vp]),
     "gr_t5_embed_workspace_bytes": (_sz, [ctypes.POINTER(T5EmbedParams), _i64, _i32]),
     "gr_t5_embed_f32": (ctypes.c_int, [ctypes.POINTER(T5EmbedParams), _vp, _vp, _i64, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "gr_t5_embed_project_f32": (ctypes.c_int, [ctypes.POINTER(T5EmbedParams), _vp, _i64, _vp, _vp]),
+    "gr_t5_embed_rows_workspace_bytes": (_sz, [ctypes.POINTER(T5EmbedParams), _i64, _i64]),
+    "gr_t5_embed_rows_f32": (ctypes.c_int, [ctypes.POINTER(T5EmbedParams), _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp,
+                                            _vp, _sz, _vp]),
     "gr_bert_embed_workspace_bytes": (_sz, [ctypes.POINTER(BertParams), _i64, _i32]),
     "gr_bert_embed_f32": (ctypes.c_int, [ctypes.POINTER(BertParams), _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp,
                                          _sz, _vp]),

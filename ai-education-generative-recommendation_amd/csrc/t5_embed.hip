@@ -30,13 +30,21 @@
 //
 // Every output element has one summation order that depends on neither B nor the row's tile position,
 // and nothing uses atomics, so a call is bitwise repeatable and batch-invariant.
+//
+// The packed entry (gr_t5_embed_project_f32 once per table, gr_t5_embed_rows_f32 per batch) runs the same
+// kernels on the live rows only, one user after the other: the first GEMM's output is a table
+// (t5e_gemm<false, false> over the R table rows), x is gathered from it by t5e_gather_kernel, the GEMMs take
+// M = rows, and the <ROWS = true> instantiations of the attention and pooling kernels find a user's rows
+// and length through offsets[b], offsets[b + 1] (t5e_user_rows, which also bounds them).  A masked key weighs
+// exactly 0 in the dense call and a dead row is never pooled, so the packed call returns the dense call's
+// bits.  t5e_normalize_rows_kernel writes NaN for a user whose offsets or tokens were out of range.
 #include "gr_common.h"
 
 namespace gr {
 namespace {
 
 constexpr int TE_MAX_S = 32, TE_MAX_INNER = 256;
-constexpr int64_t TE_MAX_USERS = 1ll << 20;
+constexpr int64_t TE_MAX_USERS = 1ll << 20, TE_MAX_TABLE = 1ll << 24;
 constexpr int TE_BM = 64, TE_BN = 64, TE_BK = 32, TE_PITCH = TE_BK + 4, TE_NT = 256;
 constexpr float TE_MASKED = -3.4028234663852886e38f;   // finfo(float32).min: what HF adds for a masked key
 
@@ -167,6 +175,22 @@ __global__ __launch_bounds__(TE_NT, 2) void t5e_gemm_kernel(
   }
 }
 
+// The packed layout's user b: rows [row0, row0 + len) of the call's `rows`, from offsets[b], offsets[b + 1].
+// Whatever the two hold, row0 and len come back inside [0, rows) and 1..TE_MAX_S; -> false when they had to be
+// bounded (such a user reads the bounded range, stores into no row, and its pred row becomes NaN).
+__device__ __forceinline__ bool t5e_user_rows(const int64_t* __restrict__ offsets, int64_t b, int64_t rows,
+                                              int64_t& row0, int& len) {
+  const int64_t s = offsets[b], e = offsets[b + 1];
+  const bool ok = s >= 0 && s < rows && e > s && e <= rows && e - s <= TE_MAX_S;
+  row0 = s < 0 ? 0 : s >= rows ? rows - 1 : s;
+  const int64_t n = (e < 0 ? 0 : e > rows ? rows : e) - row0;
+  len = n < 1 ? 1 : n > TE_MAX_S ? TE_MAX_S : (int)n;
+  return ok;
+}
+
+// ROWS: the packed layout -- `mask` is offsets [B + 1], `S` arrives as the call's row count and becomes the
+// user's own length, every one of its rows is live
+template <bool ROWS>
 __global__ __launch_bounds__(256) void t5e_attn_o_kernel(const float* __restrict__ qkv,
                                                          const int64_t* __restrict__ mask,
                                                          const float* __restrict__ rel,
@@ -178,9 +202,12 @@ __global__ __launch_bounds__(256) void t5e_attn_o_kernel(const float* __restrict
   const int r = lane & 31, h = lane >> 5;
   const int inner = H * dkv, ap = inner + 4, ld = 3 * inner;
   const int64_t b = blockIdx.x;
-  const float* base = qkv + b * S * ld;
+  int64_t row0 = b * S;
+  bool store = true;
+  if constexpr (ROWS) store = t5e_user_rows(mask, b, /*rows=*/S, row0, /*len=*/S);
+  const float* base = qkv + row0 * ld;
   // bit j: position j is a key (lanes 0..31 look at one position each)
-  const bool mine = r < S && (mask == nullptr || mask[b * S + r] != 0);
+  const bool mine = r < S && (ROWS || mask == nullptr || mask[row0 + r] != 0);
   const uint32_t livebits = (uint32_t)__ballot(mine);
   const int rc = r < S ? r : S - 1;   // rows past S read row S - 1: finite, weighted 0 as keys, never stored as queries
   const int nkc = dkv / 8;
@@ -267,25 +294,34 @@ __global__ __launch_bounds__(256) void t5e_attn_o_kernel(const float* __restrict
 #pragma unroll
     for (int v = 0; v < 16; ++v) {
       const int row = mfma32_row(v, h);
-      if (row < S) {
-        float* px = x + (b * S + row) * D + col;
+      if (row < S && store) {
+        float* px = x + (row0 + row) * D + col;
         *px = *px + ((acc[0][v] + acc[1][v]) + (acc[2][v] + acc[3][v]));
       }
     }
   }
 }
 
+// ROWS: as in t5e_attn_o_kernel; hidden_out is then [rows, D]
+template <bool ROWS>
 __global__ __launch_bounds__(256) void t5e_pool_kernel(const float* __restrict__ x, const int64_t* __restrict__ mask,
                                                        const float* __restrict__ lnw, float eps, int S, int D,
                                                        float* __restrict__ pooled, float* __restrict__ hidden_out) {
   __shared__ float ps[4][512];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int64_t b = blockIdx.x;
+  int64_t row0 = 0;
+  bool store = true;
+  if constexpr (ROWS) store = t5e_user_rows(mask, b, /*rows=*/S, row0, /*len=*/S);
+  const auto at = [&](int i) {   // position i of user b as a row of x
+    if constexpr (ROWS) return row0 + i;
+    else return b * S + i;
+  };
   float part[8];
 #pragma unroll
   for (int t = 0; t < 8; ++t) part[t] = 0.f;
   for (int i = wave; i < S; i += 4) {
-    const float* row = x + (b * S + i) * D;
+    const float* row = x + at(i) * D;
     float xv[8], ss = 0.f;
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
@@ -295,13 +331,13 @@ __global__ __launch_bounds__(256) void t5e_pool_kernel(const float* __restrict__
     }
     ss = wave_sum(ss);
     const float ri = 1.0f / sqrtf(ss / (float)D + eps);
-    const bool lv = mask == nullptr || mask[b * S + i] != 0;
+    const bool lv = ROWS || mask == nullptr || mask[at(i)] != 0;
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
       const int c = lane + 64 * t;
       if (c < D) {
         const float hv = lnw[c] * (xv[t] * ri);
-        if (hidden_out != nullptr) hidden_out[(b * S + i) * D + c] = hv;
+        if (hidden_out != nullptr && store) hidden_out[at(i) * D + c] = hv;
         if (lv) part[t] += hv;
       }
     }
@@ -310,7 +346,7 @@ __global__ __launch_bounds__(256) void t5e_pool_kernel(const float* __restrict__
   for (int t = 0; t < 8; ++t) ps[wave][lane + 64 * t] = part[t];
   __syncthreads();
   int cnt = 0;
-  for (int i = 0; i < S; ++i) cnt += (mask == nullptr || mask[b * S + i] != 0) ? 1 : 0;
+  for (int i = 0; i < S; ++i) cnt += (ROWS || mask == nullptr || mask[at(i)] != 0) ? 1 : 0;
   const float den = fmaxf((float)cnt, 1e-9f);
   for (int c = tid; c < D; c += 256) pooled[b * D + c] = ((ps[0][c] + ps[1][c]) + (ps[2][c] + ps[3][c])) / den;
 }
@@ -327,6 +363,43 @@ __global__ __launch_bounds__(256) void t5e_normalize_kernel(const float* __restr
   ss = wave_sum(ss);
   const float den = fmaxf(sqrtf(ss), 1e-8f);
   for (int c = lane; c < N; c += 64) out[b * N + c] = p[c] / den;
+}
+
+// x[row] = projected[tokens[row]], one float4 per thread; a token outside [0, R) reads the nearest table row
+// (t5e_normalize_rows_kernel turns that user's result into NaN)
+__global__ __launch_bounds__(256) void t5e_gather_kernel(const float* __restrict__ projected, int64_t R,
+                                                         const int64_t* __restrict__ tokens, int64_t rows, int D,
+                                                         float* __restrict__ x) {
+  const int dv = D / 4;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= rows * dv) return;
+  const int64_t row = i / dv;
+  const int c = (int)(i - row * dv) * 4;
+  int64_t t = tokens[row];
+  t = t < 0 ? 0 : t >= R ? R - 1 : t;
+  *reinterpret_cast<f32x4*>(x + row * D + c) = *reinterpret_cast<const f32x4*>(projected + t * D + c);
+}
+
+// t5e_normalize_kernel on the packed layout, one wave per user: the same arithmetic, and NaN in every
+// element for a user whose offsets t5e_user_rows had to bound or one of whose tokens is outside [0, R)
+__global__ __launch_bounds__(256) void t5e_normalize_rows_kernel(const float* __restrict__ pred, float* __restrict__ out,
+                                                                 int64_t B, int N, const int64_t* __restrict__ tokens,
+                                                                 const int64_t* __restrict__ offsets, int64_t rows,
+                                                                 int64_t R) {
+  const int lane = threadIdx.x & 63;
+  const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= B) return;
+  int64_t row0;
+  int len;
+  const bool ok = t5e_user_rows(offsets, b, rows, row0, len);
+  const int64_t t = lane < len ? tokens[row0 + lane] : 0;
+  const bool bad = !ok || __any(t < 0 || t >= R);
+  const float* p = pred + b * N;
+  float ss = 0.f;
+  for (int c = lane; c < N; c += 64) ss = fmaf(p[c], p[c], ss);
+  ss = wave_sum(ss);
+  const float den = fmaxf(sqrtf(ss), 1e-8f);
+  for (int c = lane; c < N; c += 64) out[b * N + c] = bad ? __builtin_nanf("") : p[c] / den;
 }
 
 const char* t5e_check(const gr_t5_embed_params* p, int64_t B, int S) {
@@ -349,8 +422,9 @@ struct T5eLayout {   // float offsets into the workspace
   size_t x, qkv, ff, pooled, pred, total;
 };
 
-T5eLayout t5e_layout(const gr_t5_embed_params* p, int64_t B, int S) {
-  const size_t M = (size_t)B * S;
+// M token rows (B * S dense, the live rows packed) of B users
+T5eLayout t5e_layout(const gr_t5_embed_params* p, int64_t B, int64_t rows) {
+  const size_t M = (size_t)rows;
   T5eLayout L;
   size_t o = 0;
   L.x = o;      o += align_up(M * p->d_model, 4);
@@ -362,7 +436,24 @@ T5eLayout t5e_layout(const gr_t5_embed_params* p, int64_t B, int S) {
   return L;
 }
 
-size_t t5e_bytes(const gr_t5_embed_params* p, int64_t B, int S) { return t5e_layout(p, B, S).total * sizeof(float) + 16; }
+size_t t5e_bytes(const gr_t5_embed_params* p, int64_t B, int64_t rows) {
+  return t5e_layout(p, B, rows).total * sizeof(float) + 16;
+}
+
+// the packed entry's shape: the widths and B through t5e_check, then B <= rows <= 32 B
+const char* t5e_rows_check(const gr_t5_embed_params* p, int64_t B, int64_t rows) {
+  if (const char* why = t5e_check(p, B, 1)) return why;
+  if (rows < B || rows > TE_MAX_S * B) return "rows must be B..32 B (1..32 rows per user)";
+  return nullptr;
+}
+
+bool t5e_weights_ok(const gr_t5_embed_params* p) {
+  bool ok = p->in_w && p->in_b && p->out_w && p->out_b && p->rel && p->bucket && p->final_ln && aligned16(p->in_w) &&
+            aligned16(p->out_w) && aligned16(p->final_ln);
+  for (int l = 0; ok && l < p->n_layers; ++l)
+    for (int i = 0; i < 8; ++i) ok = ok && p->layer[l][i] && aligned16(p->layer[l][i]);
+  return ok;
+}
 
 template <bool NORM, bool RELU>
 int t5e_gemm(const char* what, const float* x, const float* lnw, float eps, const float* w0, const float* w1,
@@ -375,12 +466,48 @@ int t5e_gemm(const char* what, const float* x, const float* lnw, float eps, cons
   return check_launch(what);
 }
 
+struct T5eBuffers {
+  float *X, *QKV, *FF, *pooled, *pred;
+  T5eBuffers(void* workspace, const T5eLayout& L) {
+    float* ws = static_cast<float*>(workspace);
+    X = ws + L.x, QKV = ws + L.qkv, FF = ws + L.ff, pooled = ws + L.pooled, pred = ws + L.pred;
+  }
+};
+
+// Everything between x's first value and the normalisation: the blocks, the pooling, output_proj.  Dense: users =
+// the mask (or null), S the positions; ROWS: users = offsets, S the call's row count (M either way the GEMMs' rows).
+template <bool ROWS>
+int t5e_encode(const gr_t5_embed_params* p, const int64_t* users, int64_t B, int S, int64_t M, const T5eBuffers& buf,
+               float* hidden_out, hipStream_t st) {
+  const int D = p->d_model, inner = p->n_heads * p->d_kv, F = p->d_ff;
+  float *X = buf.X, *QKV = buf.QKV, *FF = buf.FF;
+  for (int l = 0; l < p->n_layers; ++l) {
+    const float* const* w = p->layer[l];
+    if (int rc = t5e_gemm<true, false>("t5e norm + qkv", X, w[0], p->eps, w[1], w[2], w[3], inner, nullptr, nullptr, QKV,
+                                       M, 3 * inner, D, st))
+      return rc;
+    t5e_attn_o_kernel<ROWS><<<dim3((unsigned)B), dim3(256), 0, st>>>(QKV, users, p->rel, p->bucket, w[4], X, S,
+                                                                     p->n_heads, p->d_kv, D);
+    if (int rc = check_launch("t5e_attn_o_kernel")) return rc;
+    if (int rc = t5e_gemm<true, true>("t5e norm + wi + relu", X, w[5], p->eps, w[6], nullptr, nullptr, F, nullptr, nullptr,
+                                      FF, M, F, D, st))
+      return rc;
+    if (int rc = t5e_gemm<false, false>("t5e wo + residual", FF, nullptr, 0.f, w[7], nullptr, nullptr, D, nullptr, X, X, M,
+                                        D, F, st))
+      return rc;
+  }
+  t5e_pool_kernel<ROWS><<<dim3((unsigned)B), dim3(256), 0, st>>>(X, users, p->final_ln, p->eps, S, D, buf.pooled, hidden_out);
+  if (int rc = check_launch("t5e_pool_kernel")) return rc;
+  return t5e_gemm<false, false>("t5e output_proj", buf.pooled, nullptr, 0.f, p->out_w, nullptr, nullptr, p->out_dim,
+                                p->out_b, nullptr, buf.pred, B, p->out_dim, D, st);
+}
+
 }  // namespace
 }  // namespace gr
 
 extern "C" size_t gr_t5_embed_workspace_bytes(const gr_t5_embed_params* p, int64_t B, int32_t S) {
   if (gr::t5e_check(p, B, S)) return 0;
-  return gr::t5e_bytes(p, B, S);
+  return gr::t5e_bytes(p, B, B * S);
 }
 
 extern "C" int gr_t5_embed_f32(const gr_t5_embed_params* p, const float* seq_embs, const int64_t* attention_mask,
@@ -391,46 +518,69 @@ extern "C" int gr_t5_embed_f32(const gr_t5_embed_params* p, const float* seq_emb
   const std::string who = "gr_t5_embed_f32: ";
   if (const char* why = t5e_check(p, B, S)) return fail(!p || B < 0 ? GR_ERR_ARG : GR_ERR_UNSUPPORTED, who + why);
   if (B == 0) return GR_OK;
-  if (!workspace || workspace_bytes < t5e_bytes(p, B, S) || !aligned16(workspace))
+  const int64_t M = B * S;
+  if (!workspace || workspace_bytes < t5e_bytes(p, B, M) || !aligned16(workspace))
     return fail(GR_ERR_WORKSPACE, who + "workspace missing, misaligned or smaller than gr_t5_embed_workspace_bytes");
   if (!seq_embs || !pred_out) return fail(GR_ERR_ARG, who + "null pointer");
   if (!aligned16(seq_embs)) return fail(GR_ERR_ARG, who + "seq_embs must be 16-byte aligned");
-  bool ok = p->in_w && p->in_b && p->out_w && p->out_b && p->rel && p->bucket && p->final_ln && aligned16(p->in_w) &&
-            aligned16(p->out_w) && aligned16(p->final_ln);
-  for (int l = 0; ok && l < p->n_layers; ++l)
-    for (int i = 0; i < 8; ++i) ok = ok && p->layer[l][i] && aligned16(p->layer[l][i]);
-  if (!ok) return fail(GR_ERR_ARG, who + "a weight pointer is null or not 16-byte aligned");
+  if (!t5e_weights_ok(p)) return fail(GR_ERR_ARG, who + "a weight pointer is null or not 16-byte aligned");
 
-  const int D = p->d_model, inner = p->n_heads * p->d_kv, F = p->d_ff;
-  const int64_t M = B * S;
-  const T5eLayout L = t5e_layout(p, B, S);
-  float* ws = static_cast<float*>(workspace);
-  float *X = ws + L.x, *QKV = ws + L.qkv, *FF = ws + L.ff, *pooled = ws + L.pooled, *pred = ws + L.pred;
+  const T5eBuffers w(workspace, t5e_layout(p, B, M));
   hipStream_t st = static_cast<hipStream_t>(stream);
-
-  if (int rc = t5e_gemm<false, false>("t5e input_proj", seq_embs, nullptr, 0.f, p->in_w, nullptr, nullptr, D, p->in_b,
-                                      nullptr, X, M, D, p->in_dim, st))
+  if (int rc = t5e_gemm<false, false>("t5e input_proj", seq_embs, nullptr, 0.f, p->in_w, nullptr, nullptr, p->d_model,
+                                      p->in_b, nullptr, w.X, M, p->d_model, p->in_dim, st))
     return rc;
-  for (int l = 0; l < p->n_layers; ++l) {
-    const float* const* w = p->layer[l];
-    if (int rc = t5e_gemm<true, false>("t5e norm + qkv", X, w[0], p->eps, w[1], w[2], w[3], inner, nullptr, nullptr, QKV,
-                                       M, 3 * inner, D, st))
-      return rc;
-    t5e_attn_o_kernel<<<dim3((unsigned)B), dim3(256), 0, st>>>(QKV, attention_mask, p->rel, p->bucket, w[4], X, S,
-                                                                      p->n_heads, p->d_kv, D);
-    if (int rc = check_launch("t5e_attn_o_kernel")) return rc;
-    if (int rc = t5e_gemm<true, true>("t5e norm + wi + relu", X, w[5], p->eps, w[6], nullptr, nullptr, F, nullptr, nullptr,
-                                      FF, M, F, D, st))
-      return rc;
-    if (int rc = t5e_gemm<false, false>("t5e wo + residual", FF, nullptr, 0.f, w[7], nullptr, nullptr, D, nullptr, X, X, M,
-                                        D, F, st))
-      return rc;
-  }
-  t5e_pool_kernel<<<dim3((unsigned)B), dim3(256), 0, st>>>(X, attention_mask, p->final_ln, p->eps, S, D, pooled, hidden_out);
-  if (int rc = check_launch("t5e_pool_kernel")) return rc;
-  if (int rc = t5e_gemm<false, false>("t5e output_proj", pooled, nullptr, 0.f, p->out_w, nullptr, nullptr, p->out_dim,
-                                      p->out_b, nullptr, pred, B, p->out_dim, D, st))
-    return rc;
-  t5e_normalize_kernel<<<dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st>>>(pred, pred_out, B, p->out_dim);
+  if (int rc = t5e_encode<false>(p, attention_mask, B, S, M, w, hidden_out, st)) return rc;
+  t5e_normalize_kernel<<<dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st>>>(w.pred, pred_out, B, p->out_dim);
   return check_launch("t5e_normalize_kernel");
 }
+
+extern "C" int gr_t5_embed_project_f32(const gr_t5_embed_params* p, const float* table, int64_t R, float* projected,
+                                       void* stream) {
+  using namespace gr;
+  clear_error();
+  const std::string who = "gr_t5_embed_project_f32: ";
+  if (const char* why = t5e_check(p, 0, 1)) return fail(!p ? GR_ERR_ARG : GR_ERR_UNSUPPORTED, who + why);
+  if (R < 1) return fail(GR_ERR_ARG, who + "R must be at least 1 table row");
+  if (R > TE_MAX_TABLE) return fail(GR_ERR_UNSUPPORTED, who + "R must be at most 2^24 table rows");
+  if (!table || !projected) return fail(GR_ERR_ARG, who + "null pointer");
+  if (!aligned16(table) || !aligned16(projected)) return fail(GR_ERR_ARG, who + "table and projected must be 16-byte aligned");
+  if (!p->in_w || !p->in_b || !aligned16(p->in_w))
+    return fail(GR_ERR_ARG, who + "a weight pointer is null or not 16-byte aligned");
+  return t5e_gemm<false, false>("t5e input_proj", table, nullptr, 0.f, p->in_w, nullptr, nullptr, p->d_model, p->in_b,
+                                nullptr, projected, R, p->d_model, p->in_dim, static_cast<hipStream_t>(stream));
+}
+
+extern "C" size_t gr_t5_embed_rows_workspace_bytes(const gr_t5_embed_params* p, int64_t B, int64_t rows) {
+  if (gr::t5e_rows_check(p, B, rows)) return 0;
+  return gr::t5e_bytes(p, B, rows);
+}
+
+extern "C" int gr_t5_embed_rows_f32(const gr_t5_embed_params* p, const float* projected, int64_t R,
+                                    const int64_t* tokens, const int64_t* offsets, int64_t B, int64_t rows,
+                                    float* pred_out, float* hidden_out, void* workspace, size_t workspace_bytes,
+                                    void* stream) {
+  using namespace gr;
+  clear_error();
+  const std::string who = "gr_t5_embed_rows_f32: ";
+  if (const char* why = t5e_rows_check(p, B, rows)) return fail(!p || B < 0 ? GR_ERR_ARG : GR_ERR_UNSUPPORTED, who + why);
+  if (R < 1) return fail(GR_ERR_ARG, who + "R must be at least 1 table row");
+  if (R > TE_MAX_TABLE) return fail(GR_ERR_UNSUPPORTED, who + "R must be at most 2^24 table rows");
+  if (B == 0) return GR_OK;
+  if (!workspace || workspace_bytes < t5e_bytes(p, B, rows) || !aligned16(workspace))
+    return fail(GR_ERR_WORKSPACE, who + "workspace missing, misaligned or smaller than gr_t5_embed_rows_workspace_bytes");
+  if (!projected || !tokens || !offsets || !pred_out) return fail(GR_ERR_ARG, who + "null pointer");
+  if (!aligned16(projected)) return fail(GR_ERR_ARG, who + "projected must be 16-byte aligned");
+  if (!t5e_weights_ok(p)) return fail(GR_ERR_ARG, who + "a weight pointer is null or not 16-byte aligned");
+
+  const T5eBuffers w(workspace, t5e_layout(p, B, rows));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int64_t vecs = rows * (p->d_model / 4);
+  t5e_gather_kernel<<<dim3((unsigned)((vecs + 255) / 256)), dim3(256), 0, st>>>(projected, R, tokens, rows, p->d_model, w.X);
+  if (int rc = check_launch("t5e_gather_kernel")) return rc;
+  if (int rc = t5e_encode<true>(p, offsets, B, (int)rows, rows, w, hidden_out, st)) return rc;
+  t5e_normalize_rows_kernel<<<dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st>>>(w.pred, pred_out, B, p->out_dim, tokens,
+                                                                                 offsets, rows, R);
+  return check_launch("t5e_normalize_rows_kernel");
+}
+

@@ -2107,6 +2107,66 @@ def t5_embed(binding, seq_embs, attention_mask=None, with_hidden=False):
     return (pred, hidden) if with_hidden else pred
 
 
+T5E_MAX_TABLE = 1 << 24
+
+
+def t5_embed_project(binding, table):
+    """``gr_t5_embed_project_f32``: input_proj over a whole table, once.  table [R, in_dim] fp32 (R 1..2^24) ->
+    projected [R, d_model]: row r holds the bits ``t5_embed`` puts into x for that vector."""
+    L.require_gpu(table)
+    p = binding.params
+    if table.dim() != 2 or table.shape[-1] != p.in_dim:
+        raise RuntimeError(f"t5_embed_project takes a [R, {p.in_dim}] table, got {tuple(table.shape)}")
+    R = table.shape[0]
+    if not 1 <= R <= T5E_MAX_TABLE:
+        raise NotImplementedError(f"T5 embedding retriever: a table of {R} rows; 1..2^24 are supported; there is no CPU "
+                                  "fallback")
+    table = L.as_f32(table)
+    projected = torch.empty((R, p.d_model), dtype=torch.float32, device=table.device)
+    with L.on(table.device):
+        L.check(L.lib().gr_t5_embed_project_f32(binding.ref, L.ptr(table), R, L.ptr(projected),
+                                                L.stream_of(table.device)), "gr_t5_embed_project_f32")
+    return projected
+
+
+def t5_embed_rows(binding, projected, tokens, offsets, with_hidden=False):
+    """``gr_t5_embed_rows_f32``: the encoder on packed live rows, one C call, nothing synchronises.  projected
+    [R, d_model] from ``t5_embed_project``; tokens [rows] int64 rows of it, user after user; offsets [B + 1] int64,
+    user b is tokens[offsets[b]:offsets[b + 1]] (1..32 of them) -> pred [B, out_dim] unit rows[, hidden [rows,
+    d_model]]: the bits ``t5_embed`` gives for the same sequences right-padded.  The values of tokens and offsets
+    are not read on the host: a user with a token outside the table or with bad offsets gets a NaN row."""
+    L.require_gpu(projected, tokens, offsets)
+    p = binding.params
+    if projected.dim() != 2 or projected.shape[-1] != p.d_model:
+        raise RuntimeError(f"t5_embed_rows takes a projected [R, {p.d_model}] table, got {tuple(projected.shape)}")
+    projected = L.as_f32(projected)
+    if tokens.dim() != 1 or offsets.dim() != 1 or offsets.shape[0] < 1:
+        raise RuntimeError(f"t5_embed_rows takes tokens [rows] and offsets [B + 1], got {tuple(tokens.shape)} and "
+                           f"{tuple(offsets.shape)}")
+    if tokens.dtype != torch.int64 or offsets.dtype != torch.int64:
+        raise TypeError(f"tokens and offsets must be int64, got {tokens.dtype} and {offsets.dtype}")
+    tokens, offsets = tokens.contiguous(), offsets.contiguous()
+    R, rows, B = projected.shape[0], tokens.shape[0], offsets.shape[0] - 1
+    t5_embed_check(binding.cfg, None, B)
+    if not B <= rows <= 32 * B:
+        raise NotImplementedError(f"T5 embedding retriever: {rows} rows for {B} users; every user has 1..32 rows; there is "
+                                  "no CPU fallback")
+    if B > 0 and not 1 <= R <= T5E_MAX_TABLE:
+        raise NotImplementedError(f"T5 embedding retriever: a table of {R} rows; 1..2^24 are supported; there is no CPU "
+                                  "fallback")
+    dev = projected.device
+    pred = torch.empty((B, p.out_dim), dtype=torch.float32, device=dev)
+    hidden = torch.empty((rows, p.d_model), dtype=torch.float32, device=dev) if with_hidden else None
+    if B > 0:
+        nbytes = L.lib().gr_t5_embed_rows_workspace_bytes(binding.ref, B, rows)
+        wsp = L.workspace(nbytes, dev)
+        with L.on(dev):
+            L.check(L.lib().gr_t5_embed_rows_f32(binding.ref, L.ptr(projected), R, L.ptr(tokens), L.ptr(offsets), B, rows,
+                                                 L.ptr(pred), L.ptr(hidden), L.ptr(wsp), nbytes, L.stream_of(dev)),
+                    "gr_t5_embed_rows_f32")
+    return (pred, hidden) if with_hidden else pred
+
+
 BERT_LAYER_KEYS = ("attention.self.query.weight", "attention.self.query.bias", "attention.self.key.weight",
                    "attention.self.key.bias", "attention.self.value.weight", "attention.self.value.bias",
                    "attention.output.dense.weight", "attention.output.dense.bias",

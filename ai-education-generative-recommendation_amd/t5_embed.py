@@ -14,6 +14,12 @@ is not built.
 ``retrieve`` / ``evaluate_batches`` restate the metric tail of T5/evaluate.py:38-75 (scores through
 ``gr_linear_f32``, top k through ``gr_topk_f32``), ``collate`` restates ``collate_emb_batch`` on arrays.
 Reading the ``.h5`` embedding files stays with the caller.
+
+Every position of every sequence is a row of one of two fixed tables (T5/data_vision.py:119-154), so there is a
+second way in that moves no vectors per batch: ``Tables(model, item_embs, user_embs)`` holds the tables and their
+``input_proj`` on the device, ``collate_ids`` turns samples into row ids and offsets, ``model.embed_rows`` runs the
+encoder on the live rows only and returns ``generate``'s bits, and ``evaluate_ids`` / ``eval_loss_ids`` are the two
+loops on top of it.
 """
 import numpy as np
 import torch
@@ -95,6 +101,50 @@ class TIGER(nn.Module):
     def generate(self, seq_embs, attention_mask=None, **kwargs):
         return self.forward(seq_embs=seq_embs, attention_mask=attention_mask, target_emb=None)[1]
 
+    @torch.no_grad()
+    def embed_rows(self, tables, tokens, offsets):
+        """``generate`` on id sequences: ``tokens`` [rows] are rows of ``tables`` (a ``Tables`` of this model), user b
+        is tokens[offsets[b]:offsets[b + 1]] -> pred [B, target_emb_dim], the bits ``generate`` returns for the same
+        sequences as right-padded vectors.  One C call on the live rows only; nothing is read back."""
+        return ops.t5_embed_rows(self.binding(), tables.projected(), tokens, offsets)
+
+
+class Tables:
+    """The two fixed tables every sequence is drawn from (T5/data_vision.py:119-154), on the model's device:
+    ``table`` [n_items + n_users, input_emb_dim], item rows first and user rows after, so an item's row is its id
+    and ``user_row(user_id) = n_items + user_id - 1``; ``items_normalized``, the L2-normalised catalog ``retrieve``
+    scores against; and ``projected()``, ``input_proj`` of ``table``, computed once and kept."""
+
+    def __init__(self, model, item_embs, user_embs=None):
+        self.model = model
+        dev = model.input_proj.weight.device
+        items = torch.as_tensor(item_embs, dtype=torch.float32, device=dev)
+        self.n_items = items.shape[0]
+        self.n_users = 0
+        self.table = items
+        if user_embs is not None:
+            users = torch.as_tensor(user_embs, dtype=torch.float32, device=dev)
+            self.n_users = users.shape[0]
+            self.table = torch.cat([items, users], dim=0)
+        self.items = self.table[:self.n_items]
+        self._projected = None
+        self._key = None
+        self.projected()                              # refuses a CPU model here, not at the first batch
+        self.items_normalized = F.normalize(self.items, p=2, dim=1)
+
+    def user_row(self, user_id):
+        return self.n_items + user_id - 1
+
+    def projected(self):
+        """``input_proj`` of the table: a snapshot, rebuilt when ``input_proj``'s storage pointer or ``_version``
+        changes -- so after an in-place update or a ``load_state_dict`` the next call projects with the new weights."""
+        lin = self.model.input_proj
+        key = tuple((t.data_ptr(), t._version) for t in (lin.weight, lin.bias))
+        if self._projected is None or key != self._key:
+            self._projected = ops.t5_embed_project(self.model.binding(), self.table)
+            self._key = key
+        return self._projected
+
 
 def collate(batch):
     """``collate_emb_batch`` (T5/train.py:17-35) on arrays: samples with ``seq_embs`` [seq_len, dim], ``seq_len``,
@@ -111,6 +161,33 @@ def collate(batch):
             "target_emb": torch.from_numpy(np.stack([np.asarray(b["target_emb"], dtype=np.float32) for b in batch])),
             "target_id": torch.tensor([int(b["target_id"]) for b in batch], dtype=torch.long),
             "user_id": torch.tensor([int(b["user_id"]) for b in batch], dtype=torch.long)}
+
+
+MAX_ROWS = 32         # positions per user
+
+
+def collate_ids(samples, n_items):
+    """The reference's ``__getitem__`` + ``collate_emb_batch`` (T5/data_vision.py:131-154, T5/train.py:17-35)
+    without the vectors: samples with ``history`` (item ids), ``user_id``, ``target_id`` -> int64 ``tokens`` [rows]
+    (per user its row ``n_items + user_id - 1`` of a ``Tables`` over ``n_items`` items, then the history), ``offsets``
+    [B + 1], ``target_id``, ``user_id``.  An empty history (the reference cannot concatenate one either), a
+    sequence of more than 32 rows and an empty batch are ValueErrors here, before anything reaches the device."""
+    if len(samples) == 0:
+        raise ValueError("collate_ids: an empty batch")
+    tokens, offsets = [], [0]
+    for i, s in enumerate(samples):
+        history = [int(t) for t in s["history"]]
+        if len(history) == 0:
+            raise ValueError(f"collate_ids: sample {i} has an empty history")
+        if 1 + len(history) > MAX_ROWS:
+            raise ValueError(f"collate_ids: sample {i} has {1 + len(history)} rows (the user's and {len(history)} "
+                             f"items); at most {MAX_ROWS} are supported")
+        tokens.append(n_items + int(s["user_id"]) - 1)
+        tokens.extend(history)
+        offsets.append(len(tokens))
+    return {"tokens": torch.tensor(tokens, dtype=torch.long), "offsets": torch.tensor(offsets, dtype=torch.long),
+            "target_id": torch.tensor([int(s["target_id"]) for s in samples], dtype=torch.long),
+            "user_id": torch.tensor([int(s["user_id"]) for s in samples], dtype=torch.long)}
 
 
 def retrieve(pred, item_embs, k, catalog_normalized=False):
@@ -161,3 +238,30 @@ def evaluate_batches(batches, model, item_embs, topk_list, device=None):
         _, ids = retrieve(pred, items, max(topk_list), catalog_normalized=True)
         per_batch.append(batch_metrics(ids, batch["target_id"].to(device), topk_list))
     return average_metrics(per_batch, topk_list)
+
+
+@torch.no_grad()
+def evaluate_ids(batches, model, tables, topk_list):
+    """``evaluate_batches`` on ``collate_ids`` batches: the same loop and the same floats, with only the ids going to
+    the device per batch -- the vectors are ``tables``' and the catalog is its ``items_normalized``."""
+    device = tables.table.device
+    per_batch = []
+    for batch in batches:
+        pred = model.embed_rows(tables, batch["tokens"].to(device), batch["offsets"].to(device))
+        _, ids = retrieve(pred, tables.items_normalized, max(topk_list), catalog_normalized=True)
+        per_batch.append(batch_metrics(ids, batch["target_id"].to(device), topk_list))
+    return average_metrics(per_batch, topk_list)
+
+
+@torch.no_grad()
+def eval_loss_ids(batches, model, tables):
+    """``eval_loss`` (T5/train.py:57-67) on ``collate_ids`` batches: the mean over the batches of the contrastive loss
+    of ``forward``, the targets' vectors gathered from ``tables`` on the device.  The per-batch losses stay on the device
+    until the end."""
+    device = tables.table.device
+    losses = []
+    for batch in batches:
+        pred = model.embed_rows(tables, batch["tokens"].to(device), batch["offsets"].to(device))
+        losses.append(model.compute_contrastive_loss(pred, tables.items[batch["target_id"].to(device)]))
+    values = [float(v) for v in torch.stack(losses).tolist()] if losses else []
+    return sum(values) / len(values) if values else 0.0

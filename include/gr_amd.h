@@ -866,6 +866,40 @@ int gr_t5_embed_f32(const gr_t5_embed_params* p, const float* seq_embs, const in
                     int64_t B, int32_t S, float* pred_out, float* hidden_out, void* workspace,
                     size_t workspace_bytes, void* stream);
 
+/* The packed entry: sequences as ids into a table that input_proj went over once, live rows only.
+ * In the reference every position is a row of one of two fixed tables (T5/data_vision.py:119-154: the
+ * user's profile vector, then the history's item vectors), so the per-batch host gather, the upload
+ * and the 768 -> d_model projection of vectors that never change are not needed.
+ *
+ * gr_t5_embed_project_f32: projected[r] = table[r] . in_w^T + in_b for table [R, in_dim] into projected
+ * [R, d_model] -- the launch gr_t5_embed_f32 makes first, so row r holds the bits that call puts into x
+ * for that vector.  R 1..2^24 (GR_ERR_ARG below, GR_ERR_UNSUPPORTED above); both pointers 16-byte
+ * aligned.  One launch, no workspace.
+ *
+ * gr_t5_embed_rows_f32: user b is rows [offsets[b], offsets[b + 1]) of tokens [rows], 1..32 of them, at
+ * positions 0..len_b - 1; tokens index projected [R, d_model]; offsets [B + 1] is device int64 with
+ * offsets[0] = 0 and offsets[B] = rows; rows is the host's count (it sizes the workspace and the grids).
+ * 1 + 4 n_layers + 3 launches, nothing synchronises: a gather x[row] = projected[tokens[row]]; the
+ * blocks with M = rows (attention per user on its own rows and length); pooling over the user's rows;
+ * output_proj; normalise.  pred_out [B, out_dim] holds the bits gr_t5_embed_f32 returns for the same
+ * sequences right-padded to any S with the matching mask; hidden_out (optional) is [rows, d_model] and
+ * holds that call's live rows.  Same repeatability and batch invariance.
+ * Envelope: gr_t5_embed_f32's widths; B 0..2^20 (B = 0 with rows = 0: GR_OK, no launch); B <= rows <=
+ * 32 B, else GR_ERR_UNSUPPORTED naming rows; R as above.
+ * No input value leads outside the buffers: a token outside [0, R) reads the nearest table row, and
+ * offsets that do not describe 1..32 rows inside [0, rows) are bounded to some that do; such a user's
+ * pred_out row is NaN in every element (and with bad offsets it stores no hidden_out row).  Every other
+ * user keeps the bits of the clean call as long as no other user's range overlaps its rows.
+ * workspace: gr_t5_embed_rows_workspace_bytes(p, B, rows) bytes, 16-byte aligned (0 outside the
+ * envelope); the dense layout with B * S replaced by rows, so (p, B, B * S) gives
+ * gr_t5_embed_workspace_bytes(p, B, S). */
+int gr_t5_embed_project_f32(const gr_t5_embed_params* p, const float* table, int64_t R, float* projected,
+                            void* stream);
+size_t gr_t5_embed_rows_workspace_bytes(const gr_t5_embed_params* p, int64_t B, int64_t rows);
+int gr_t5_embed_rows_f32(const gr_t5_embed_params* p, const float* projected, int64_t R, const int64_t* tokens,
+                         const int64_t* offsets, int64_t B, int64_t rows, float* pred_out, float* hidden_out,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------ */
 /* BERT text encoder (transformers' BertModel in eval mode, eager attention, absolute positions) with
  * the reference's two poolings (T5/item_encode.py:11-34,59-78; major-encode/bert_emb.py:131-168).

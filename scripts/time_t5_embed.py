@@ -5,6 +5,8 @@ the same GPU in the same process, and next to transformers' T5EncoderModel with 
 
     python scripts/time_t5_embed.py [--out profiles/r20/t5_embed.txt]
     rocprofv3 --kernel-trace --stats ... -- python scripts/time_t5_embed.py --only-kernels   (per-kernel shares)
+    python scripts/time_t5_embed.py --rows [--out profiles/r25/t5_embed_rows.txt]       (the id-sequence entry)
+    rocprofv3 --kernel-trace --stats ... -- python scripts/time_t5_embed.py --rows --only-kernels
 
 Each call is timed by its own pair of events after a warm-up; the figure is the median over ``--reps`` calls
 with the minimum, the quartiles and the maximum beside it.  The fp32 floor is the multiply-adds the shapes
@@ -68,12 +70,99 @@ def weight_bytes(p, layers):
     return 4 * (p["input_emb_dim"] * d + layers * (4 * inner * d + 2 * d * p["d_ff"]) + p["target_emb_dim"] * d)
 
 
+def wall(fn, reps, warmup):
+    """Wall-clock of ``fn`` from an idle device to an idle device (host work included), per call."""
+    import time
+    for _ in range(warmup):
+        fn()
+    ms = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        ms.append((time.perf_counter() - t0) * 1e3)
+    q = np.percentile(np.array(ms), [0, 25, 50, 75, 100])
+    return dict(median_ms=float(q[2]), min_ms=float(q[0]), q25_ms=float(q[1]), q75_ms=float(q[3]), max_ms=float(q[4]),
+                calls=reps)
+
+
+def rows_report(a, model, dev):
+    """``--rows``: the id-sequence entry (``Tables``, ``embed_rows``) next to the dense call, in one process.
+
+    1  the dense call, ``seq_embs`` already on the device (twice: the spread between the two runs is the yardstick)
+    2  the dense path as the reference runs it: per sample the host gather from the numpy tables
+       (T5/data_vision.py:131-154), ``collate``, ``.to(device)``, the call -- wall-clock around a synchronise
+    3  the rows call, every user at ``--positions`` rows: the dense call's work minus input_proj plus the gather
+    4  the rows call, lengths uniform on 2..``--positions`` (and the dense call on the same sequences, padded)
+    5  the one-off projection of a 10,000-row table
+    """
+    from gr_amd import t5_embed
+    B, S, dim = a.batch, a.positions, PARAMS["input_emb_dim"]
+    rng = np.random.default_rng(0)
+    items = (0.5 * rng.standard_normal((10000 - B, dim))).astype(np.float32)
+    users = (0.5 * rng.standard_normal((B, dim))).astype(np.float32)
+    full = [dict(history=rng.integers(0, len(items), S - 1).tolist(), user_id=u + 1, target_id=0) for u in range(B)]
+    ragged = [dict(s, history=s["history"][:int(rng.integers(2, S + 1)) - 1]) for s in full]
+    tables = t5_embed.Tables(model, items, users)
+
+    def vectors(samples):      # the reference's __getitem__
+        return [dict(seq_embs=np.concatenate([np.expand_dims(users[s["user_id"] - 1], 0),
+                                              np.array([items[i] for i in s["history"]])], axis=0),
+                     seq_len=len(s["history"]) + 1, target_emb=items[s["target_id"]], target_id=s["target_id"],
+                     user_id=s["user_id"]) for s in samples]
+
+    def dense_inputs(samples):
+        b = t5_embed.collate(vectors(samples))
+        return b["seq_embs"].to(dev), b["attention_mask"].to(dev)
+
+    def ids(samples):
+        b = t5_embed.collate_ids(samples, tables.n_items)
+        return b["tokens"].to(dev), b["offsets"].to(dev)
+
+    seq, mask = dense_inputs(full)
+    rseq, rmask = dense_inputs(ragged)
+    tok, off = ids(full)
+    rtok, roff = ids(ragged)
+    dense = lambda: model.generate(seq, mask)
+    rows = lambda: model.embed_rows(tables, tok, off)
+    rows_ragged = lambda: model.embed_rows(tables, rtok, roff)
+    if a.only_kernels:
+        for _ in range(10):
+            rows_ragged()
+        torch.cuda.synchronize()
+        return None
+    same = lambda x, y: bool(torch.equal(x.view(torch.int32), y.view(torch.int32)))
+    res = {"shape": dict(B=B, S=S, table_rows=int(tables.table.shape[0]), live_rows_uniform=int(rtok.shape[0]),
+                         **{k: PARAMS[k] for k in ("d_model", "d_ff", "num_heads", "d_kv", "input_emb_dim", "target_emb_dim")},
+                         blocks=len(model.model.encoder.block)),
+           "device": torch.cuda.get_device_name(0),
+           "upload_bytes_dense": int(seq.numel() * 4 + mask.numel() * 8), "upload_bytes_ids": int((tok.numel() + off.numel()) * 8),
+           "bits_equal_full": same(rows(), dense()), "bits_equal_uniform": same(rows_ragged(), model.generate(rseq, rmask))}
+    res["1_dense_on_device_run1"] = timed(dense, a.reps, 5)
+    res["3_rows_all_full"] = timed(rows, a.reps, 5)
+    res["1_dense_on_device_run2"] = timed(dense, a.reps, 5)
+    res["2_dense_as_the_reference_feeds_it_wall"] = wall(lambda: model.generate(*dense_inputs(full)), a.reps, 3)
+    res["2b_rows_from_host_ids_wall"] = wall(lambda: model.embed_rows(tables, *ids(full)), a.reps, 3)
+    res["4_rows_uniform_lengths"] = timed(rows_ragged, a.reps, 5)
+    res["4b_dense_uniform_lengths"] = timed(lambda: model.generate(rseq, rmask), a.reps, 5)
+    binding, table = model.binding(), tables.table
+    res["5_project_10000_rows"] = timed(lambda: gr_amd.ops.t5_embed_project(binding, table), a.reps, 5)
+    d1, d2 = res["1_dense_on_device_run1"]["median_ms"], res["1_dense_on_device_run2"]["median_ms"]
+    r3 = res["3_rows_all_full"]["median_ms"]
+    res["dense_run_to_run_spread_ms"] = abs(d1 - d2)
+    res["rows_full_minus_dense_ms"] = r3 - min(d1, d2)
+    res["rows_full_within_the_spread_of_dense"] = bool(r3 <= max(d1, d2))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--positions", type=int, default=21)
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--only-kernels", action="store_true", help="a few calls of the kernels alone (for a kernel trace)")
+    ap.add_argument("--rows", action="store_true", help="the id-sequence entry next to the dense call (see rows_report)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -83,6 +172,16 @@ def main():
         for p in model.parameters():
             p.copy_(p.to(torch.bfloat16).float())
     model = model.to(dev).eval()
+    if a.rows:
+        res = rows_report(a, model, dev)
+        if res is not None:
+            line = json.dumps(res, indent=1)
+            print(line)
+            if a.out:
+                os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+                with open(a.out, "w") as f:
+                    f.write(line + "\n")
+        return
     seq, mask = inputs(a.batch, a.positions, PARAMS["input_emb_dim"], dev)
     run = lambda: model.generate(seq, mask)
     if a.only_kernels:
