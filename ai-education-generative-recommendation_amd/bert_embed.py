@@ -112,10 +112,7 @@ class BertEncoder(nn.Module):
         self.embeddings = _Embeddings(cfg)
         self.encoder = _Stack(cfg)
         self.pooler = _Dense(cfg["hidden_size"], cfg["hidden_size"])
-        self._binding = None
-        self._binding_key = None
-        self._binding_bf16 = None
-        self._binding_bf16_key = None
+        self._bindings = {}      # precision -> (key, binding)
 
     def load_state_dict(self, state_dict, strict=True, **kw):
         """``BertModel``'s state dict, strictly; the ``position_ids`` / ``token_type_ids`` buffers that older
@@ -123,34 +120,30 @@ class BertEncoder(nn.Module):
         sd = {k: v for k, v in state_dict.items() if k not in _IGNORED_KEYS}
         return super().load_state_dict(sd, strict=strict, **kw)
 
+    def _binding_for(self, precision):
+        """The precision's binding from the one cache: (key, binding) per precision, rebuilt when the key changes."""
+        if precision == "fp16":
+            raise ValueError("precision='fp16' is not built: 'fp32' or 'bf16'")
+        if precision not in ("fp32", "bf16"):
+            raise ValueError(f"precision={precision!r} must be 'fp32' or 'bf16'")
+        tensors = self.state_dict(keep_vars=True)
+        if precision == "fp32":
+            make, key = ops.BertBinding, tuple(t.data_ptr() for t in tensors.values())
+        else:
+            make, key = ops.BertBf16Binding, tuple((t.data_ptr(), t._version) for t in tensors.values())
+        if self._bindings.get(precision, (None, None))[0] != key:
+            self._bindings[precision] = (key, make(self.config, {k: v.detach() for k, v in tensors.items()}))
+        return self._bindings[precision][1]
+
     def binding(self):
         """The parameters' device-pointer view, rebuilt when a parameter's storage moves."""
-        tensors = self.state_dict(keep_vars=True)
-        key = tuple(t.data_ptr() for t in tensors.values())
-        if self._binding is None or key != self._binding_key:
-            self._binding = ops.BertBinding(self.config, {k: v.detach() for k, v in tensors.items()})
-            self._binding_key = key
-        return self._binding
+        return self._binding_for("fp32")
 
     def binding_bf16(self):
         """The bf16 precision's binding (``ops.BertBf16Binding``: a snapshot of the six matrices per layer rounded to
         bf16), rebuilt when a parameter's storage pointer or its ``_version`` changes -- so after an in-place update
         or a ``load_state_dict`` the next call rounds the new weights."""
-        tensors = self.state_dict(keep_vars=True)
-        key = tuple((t.data_ptr(), t._version) for t in tensors.values())
-        if self._binding_bf16 is None or key != self._binding_bf16_key:
-            self._binding_bf16 = ops.BertBf16Binding(self.config, {k: v.detach() for k, v in tensors.items()})
-            self._binding_bf16_key = key
-        return self._binding_bf16
-
-    def _binding_for(self, precision):
-        if precision == "fp32":
-            return self.binding()
-        if precision == "bf16":
-            return self.binding_bf16()
-        if precision == "fp16":
-            raise ValueError("precision='fp16' is not built: 'fp32' or 'bf16'")
-        raise ValueError(f"precision={precision!r} must be 'fp32' or 'bf16'")
+        return self._binding_for("bf16")
 
     def _refuse_training(self):
         if self.training and torch.is_grad_enabled():

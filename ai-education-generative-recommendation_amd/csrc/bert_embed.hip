@@ -6,18 +6,23 @@
 // attention step runs per sequence.
 //
 //   be_embed_ln_kernel   a wave per token row: (word[id] + token_type[type]) + position[s], LayerNorm.
-//   be_gemm_kernel<WM, TM, TN, EPI>   y = epi(A . W^T + bias) per 256-thread workgroup, K staged 32 deep
-//       through a double-buffered LDS image (t5_embed.hip's staging: rows padded to 36 floats, one float4
-//       per operand per 8-deep slice).  Each wave owns TM x TN blocks of 32 x 32 outputs, one
-//       v_mfma_f32_32x32x2_f32 accumulator chain each: 128 x 128 outputs as 2 x 2 waves of four chains (the
-//       guide's 128 x 128 x 32 block), 64 x 128 as 2 x 2 waves of two, 128 x 96 as 4 x 1 waves of three.
-//       be_gemm picks per launch the tile that leaves the fewest compute units idle (option "bert_tile"
-//       forces one).  Each output element is a sum, in k order, of fma chains of 256 consecutive k each
-//       (per 8-deep slice in the order 0 4 1 5 2 6 3 7): a chain is closed into a second accumulator every
-//       eight stages, because one chain over K = 3072 rounds about three times as much as the blocked sum.
-//       Every tile uses that order, so the choice changes no bit.  Up to three weight matrices side by
-//       side (q/k/v: one launch).
-//       Epilogues: bias; bias + exact-erf GELU; bias + residual.
+//   be_gemm_kernel<T, WM, TM, TN, EPI>   y = epi(A . W^T + bias) per 256-thread workgroup, for two operand formats
+//       T (BeF32: both entries' fp32; BeB16: the bf16 entries').  K is staged through a double-buffered LDS image
+//       of 128-byte rows on a 144-byte pitch (t5_embed.hip's staging: 16-byte loads, conflict-free 16-byte
+//       fragment reads): 32 floats or 64 bf16 deep.  Each wave owns TM x TN blocks of 32 x 32 outputs, one fp32
+//       accumulator chain each: 128 x 128 outputs as 2 x 2 waves of four chains (the guide's 128 x 128 x 32 block),
+//       64 x 128 as 2 x 2 waves of two, 128 x 96 as 4 x 1 waves of three.  be_gemm picks per launch the tile that
+//       leaves the fewest compute units idle (option "bert_tile" forces one).  Up to three weight matrices side by
+//       side (q/k/v: one launch).  Epilogues: bias; bias + exact-erf GELU; bias + residual.
+//       BeF32 (v_mfma_f32_32x32x2_f32, one float4 per operand per 8-deep slice): each output element is a sum, in k
+//       order, of fma chains of 256 consecutive k each (per 8-deep slice in the order 0 4 1 5 2 6 3 7): a chain is
+//       closed into a second accumulator every eight stages, because one chain over K = 3072 rounds about three
+//       times as much as the blocked sum.  fp32 output.
+//       BeB16 (v_mfma_f32_32x32x16_bf16, eight bf16 per operand per 16-deep step): K is a multiple of 32, so the last
+//       stage may be half zeros, never read from memory.  One fp32 chain per element, k ascending in steps of 16:
+//       bf16 products are exact in fp32 and K <= 4096, so the 256-deep blocking buys nothing next to the operands'
+//       2^-9.  Output bf16 (bias, GELU) or fp32 (residual).
+//       Every tile uses its format's order, so the choice changes no bit.
 //   be_attn_kernel<HD>   one workgroup per (sequence, head, 128 queries), a wave per 32 queries.  Key / value
 //       tiles of 32 positions stream through a double-buffered LDS image shared by the four waves; tiles
 //       with no live key are never loaded.  Scores are taken transposed (A rows are keys, B columns are
@@ -40,8 +45,9 @@
 // query tile past it exits.  The sums' orders are the padded call's, so the kept rows and the pooled vectors have
 // its bits.  The padded instantiations take the row map (BeRows) and never read it.
 //
-// gr_bert_embed_bf16 / gr_bert_embed_ragged_bf16: the same encoder with bf16 GEMM operands (opt-in; the fp32 entries
-// keep their kernels and their bits).  bf16 = the upper 16 bits of the RNE-rounded fp32.  The contract:
+// gr_bert_embed_bf16 / gr_bert_embed_ragged_bf16: the same encoder, the same layer loop (be_forward) and the same
+// GEMM on bf16 operands (opt-in; the fp32 entries keep their bits).  bf16 = the upper 16 bits of the RNE-rounded
+// fp32.  The contract:
 //   GEMM operands   A and W of the four projections per layer (fused q/k/v, attention output, intermediate, output)
 //                   are bf16, accumulated in fp32 in the MFMA accumulator (v_mfma_f32_32x32x16_bf16).
 //   epilogues       bias, exact-erf GELU, residual add (be_epilogue, the fp32 kernel's own expressions), both
@@ -59,17 +65,12 @@
 //   determinism     one summation order per output element (k ascending in steps of 16, the order inside a step is
 //                   the instruction's), whatever B, the row's place in a tile or the tile; no atomics: bitwise
 //                   repeatable, batch-invariant, and the ragged form returns the padded form's bits.
-//   be_gemm_bf16_kernel<WM, TM, TN, EPI>   be_gemm_kernel's tiles and epilogues; K staged 64 deep through a
-//       double-buffered LDS image of 128-byte rows on a 144-byte pitch (16-byte loads, conflict-free 16-byte fragment
-//       reads); K is a multiple of 32, so the last stage may be half zeros, never read from memory.  One fp32 chain per
-//       element: bf16 products are exact in fp32 and K <= 4096, so the fp32 kernel's 256-deep blocking buys nothing
-//       next to the operands' 2^-9.  Output bf16 (bias, GELU) or fp32 (residual).
 //   be_attn_bf16_kernel<HD>   be_attn_kernel's grid and tile order on bf16 q/k/v.  Scores transposed (A rows are keys,
 //       B columns are queries); the probability registers, rounded pairwise, are the B operand of
 //       O^T = V^T . P^T, so a query's running max, sum and output column all sit in its own lane; v is staged
 //       transposed, its keys in the order the accumulator's registers hold them.
 //   workspace on return   what a test may read after the call; not an interface for callers.  The six parts of
-//       BeLayout16, in order, each rounded up to 16 bytes, hold the LAST layer's intermediates over R rows (B * S, or
+//       BeLayout, in order, each rounded up to 16 bytes, hold the LAST layer's intermediates over R rows (B * S, or
 //       the packed rows): x fp32 [R, H] the post-attention LayerNorm output (the final hidden state instead when
 //       hidden_out is NULL); t fp32 [R, H] x + output.dense(ff) + bias, the final LayerNorm's input; x16 bf16 [R, H]
 //       the RNE copy of the final LayerNorm's fp32 rows (be_pool_kernel zeroes hidden_out alone for a sequence with no
@@ -87,13 +88,27 @@ namespace {
 
 constexpr int BE_MAX_S = 512, BE_MAX_H = 1024, BE_MAX_I = 4096;
 constexpr int64_t BE_MAX_B = 1ll << 16;
-constexpr int BE_BK = 32, BE_PITCH = BE_BK + 4, BE_NT = 256;
-constexpr int BE_KFLUSH = 8;               // 32-deep stages per fma chain: 256 deep
+constexpr int BE_NT = 256;
 constexpr int BE_QT = 128, BE_KT = 32;     // queries per workgroup, keys per streamed tile
 enum { BE_EPI_BIAS = 0, BE_EPI_GELU = 1, BE_EPI_RESID = 2 };
-constexpr int BH_BK = 64, BH_PITCH = BH_BK + 8;   // bf16 elements per staged row and its pitch: 128 of 144 bytes
 
-// What follows a GEMM's sum, in the fp32 and in the bf16 kernel: the bias, then exact-erf GELU or the residual add.
+// The GEMM's two operand formats.  E: the element of A and W; V: the 16 bytes a thread stages and a lane reads per
+// fragment; BK elements per staged row (128 bytes) on a pitch of PITCH (144 bytes); VE elements per 16-byte piece;
+// KD: the k depth one fragment read covers; KFLUSH: stages per fma chain (0: one chain over all of K).
+struct BeF32 {
+  using E = float;
+  using V = f32x4;
+  static constexpr int BK = 32, PITCH = BK + 4, VE = 4, KD = 8;
+  static constexpr int KFLUSH = 8;   // 32-deep stages per fma chain: 256 deep
+};
+struct BeB16 {
+  using E = uint16_t;
+  using V = u32x4;
+  static constexpr int BK = 64, PITCH = BK + 8, VE = 8, KD = 16;
+  static constexpr int KFLUSH = 0;   // bf16 products are exact in fp32 and K <= 4096: blocking buys nothing
+};
+
+// What follows a GEMM's sum, in either format: the bias, then exact-erf GELU or the residual add.
 template <int EPI>
 __device__ __forceinline__ float be_epilogue(float sum, float bias, const float* __restrict__ residual, int64_t at) {
   float o = sum + bias;
@@ -118,106 +133,138 @@ struct BeRows {
   const int32_t* flag;
 };
 
+template <typename E>
 struct BeSeg {   // up to three [seg_n, K] weight matrices side by side, and their biases
-  const float* w[3];
+  const E* w[3];
   const float* b[3];
 };
 
-// WM waves down the tile's rows (4 / WM across its columns), each owning TM x TN blocks of 32 x 32 outputs.
+// One 8-deep (fp32) or 16-deep (bf16) slice into every accumulator chain a wave owns.  fp32: step s, the outermost
+// loop, takes k = s from lane half 0 and k = 4 + s from half 1: the contract's order 0 4 1 5 2 6 3 7.
+template <int TM, int TN>
+__device__ __forceinline__ void be_mma(const f32x4 (&a)[TM], const f32x4 (&b)[TN], f32x16 (&acc)[TM][TN]) {
+#pragma unroll
+  for (int s = 0; s < 4; ++s)
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int j = 0; j < TN; ++j) acc[i][j] = mfma32(a[i][s], b[j][s], acc[i][j]);
+}
+template <int TM, int TN>
+__device__ __forceinline__ void be_mma(const u32x4 (&a)[TM], const u32x4 (&b)[TN], f32x16 (&acc)[TM][TN]) {
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int j = 0; j < TN; ++j) acc[i][j] = mfma32_bf16(a[i], b[j], acc[i][j]);
+}
+
+// y: fp32 from fp32 operands and after the residual add, bf16 otherwise (it is then only ever a GEMM A operand)
+template <typename T, int EPI>
+using BeOut = std::conditional_t<EPI == BE_EPI_RESID, float, typename T::E>;
+
+// T: BeF32 or BeB16; x [M, K] and the weights [seg_n, K] of T::E, fp32 accumulation, be_epilogue.
+// WM waves down the tile's rows (4 / WM across its columns), each owning TM x TN blocks of 32 x 32 outputs.  Lane
+// (r, h) of a wave takes, per slice, the 16 bytes at k = VE h of row r of each operand from the LDS image.
 // RAGGED: the grid covers the caller's row bound (M_), the row count is rg.total[0]; a tile at or past it exits.
-template <int WM, int TM, int TN, int EPI, bool RAGGED>
-__global__ __launch_bounds__(BE_NT, 2) void be_gemm_kernel(const float* __restrict__ x, BeSeg sg, int seg_n,
-                                                           const float* __restrict__ residual, float* __restrict__ y,
-                                                           int64_t M_, int N, int K, int tiles_n, BeRows rg) {
+template <typename T, int WM, int TM, int TN, int EPI, bool RAGGED>
+__global__ __launch_bounds__(BE_NT, 2) void be_gemm_kernel(const typename T::E* __restrict__ x, BeSeg<typename T::E> sg,
+                                                           int seg_n, const float* __restrict__ residual,
+                                                           void* __restrict__ y_, int64_t M_, int N, int K,
+                                                           int tiles_n, BeRows rg) {
+  using E = typename T::E;
+  using V = typename T::V;
+  BeOut<T, EPI>* __restrict__ y = static_cast<BeOut<T, EPI>*>(y_);
   constexpr int WN = 4 / WM, BM = 32 * WM * TM, BN = 32 * WN * TN;
   int64_t M = M_;
   if constexpr (RAGGED) {
     M = rg.total[0];
     if ((int64_t)(blockIdx.x / tiles_n) * BM >= M) return;
   }
-  __shared__ __attribute__((aligned(16))) float lds[2][(BM + BN) * BE_PITCH];
+  __shared__ __attribute__((aligned(16))) E lds[2][(BM + BN) * T::PITCH];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN, r = lane & 31, h = lane >> 5;
   const int tni = blockIdx.x % tiles_n;
   const int64_t m0 = (int64_t)(blockIdx.x / tiles_n) * BM;
   const int n0 = tni * BN;
 
-  constexpr int AV = BM * BE_BK / 4 / BE_NT, BV = BN * BE_BK / 4 / BE_NT;
-  f32x4 ra[AV], rb[BV];
+  constexpr int AV = BM * T::BK / T::VE / BE_NT, BV = BN * T::BK / T::VE / BE_NT;
+  V ra[AV], rb[BV];
+  // eight 16-byte pieces per staged row.  K is a multiple of 32 and kk of VE: a piece lies inside the row or wholly
+  // past it (then zeros, never read from memory: the last bf16 stage may be half zeros)
   auto gload = [&](int k0) {
 #pragma unroll
     for (int i = 0; i < AV; ++i) {
-      const int f = tid + BE_NT * i, row = f >> 3, kk = k0 + (f & 7) * 4;
+      const int f = tid + BE_NT * i, row = f >> 3, kk = k0 + (f & 7) * T::VE;
       const int64_t g = m0 + row;
-      ra[i] = (g < M && kk < K) ? *reinterpret_cast<const f32x4*>(x + g * K + kk) : f32x4{0.f, 0.f, 0.f, 0.f};
+      ra[i] = (g < M && kk < K) ? *reinterpret_cast<const V*>(x + g * K + kk) : V{0, 0, 0, 0};
     }
 #pragma unroll
     for (int i = 0; i < BV; ++i) {
-      const int f = tid + BE_NT * i, row = f >> 3, kk = k0 + (f & 7) * 4;
+      const int f = tid + BE_NT * i, row = f >> 3, kk = k0 + (f & 7) * T::VE;
       const int gn = n0 + row;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      V v = {0, 0, 0, 0};
       if (gn < N && kk < K) {
         const int seg = gn / seg_n, wr = gn - seg * seg_n;
-        const float* wp = seg == 0 ? sg.w[0] : seg == 1 ? sg.w[1] : sg.w[2];
-        v = *reinterpret_cast<const f32x4*>(wp + (int64_t)wr * K + kk);
+        const E* wp = seg == 0 ? sg.w[0] : seg == 1 ? sg.w[1] : sg.w[2];
+        v = *reinterpret_cast<const V*>(wp + (int64_t)wr * K + kk);
       }
       rb[i] = v;
     }
   };
   auto swrite = [&](int buf) {
-    float* s = lds[buf];
+    E* s = lds[buf];
 #pragma unroll
     for (int i = 0; i < AV; ++i) {
       const int f = tid + BE_NT * i;
-      *reinterpret_cast<f32x4*>(s + (f >> 3) * BE_PITCH + (f & 7) * 4) = ra[i];
+      *reinterpret_cast<V*>(s + (f >> 3) * T::PITCH + (f & 7) * T::VE) = ra[i];
     }
 #pragma unroll
     for (int i = 0; i < BV; ++i) {
       const int f = tid + BE_NT * i;
-      *reinterpret_cast<f32x4*>(s + (BM + (f >> 3)) * BE_PITCH + (f & 7) * 4) = rb[i];
+      *reinterpret_cast<V*>(s + (BM + (f >> 3)) * T::PITCH + (f & 7) * T::VE) = rb[i];
     }
   };
 
-  f32x16 acc[TM][TN], tot[TM][TN];
+  f32x16 acc[TM][TN], tot[TM][TN];   // tot: the closed chains' sum, with KFLUSH only
 #pragma unroll
   for (int i = 0; i < TM; ++i)
 #pragma unroll
     for (int j = 0; j < TN; ++j)
 #pragma unroll
-      for (int v = 0; v < 16; ++v) acc[i][j][v] = tot[i][j][v] = 0.f;
+      for (int v = 0; v < 16; ++v) {
+        acc[i][j][v] = 0.f;
+        if constexpr (T::KFLUSH > 0) tot[i][j][v] = 0.f;
+      }
 
-  const int nk = (K + BE_BK - 1) / BE_BK;
+  const int nk = (K + T::BK - 1) / T::BK;
   gload(0);
   swrite(0);
   __syncthreads();
   for (int kt = 0; kt < nk; ++kt) {
     const int cur = kt & 1;
-    if (kt + 1 < nk) gload((kt + 1) * BE_BK);
-    const float* As = lds[cur] + (wm * 32 * TM + r) * BE_PITCH + 4 * h;
-    const float* Bs = lds[cur] + (BM + wn * 32 * TN + r) * BE_PITCH + 4 * h;
+    if (kt + 1 < nk) gload((kt + 1) * T::BK);
+    const E* As = lds[cur] + (wm * 32 * TM + r) * T::PITCH + T::VE * h;
+    const E* Bs = lds[cur] + (BM + wn * 32 * TN + r) * T::PITCH + T::VE * h;
 #pragma unroll
-    for (int kc = 0; kc < BE_BK / 8; ++kc) {
-      f32x4 a[TM], b[TN];
+    for (int kc = 0; kc < T::BK / T::KD; ++kc) {
+      V a[TM], b[TN];
 #pragma unroll
-      for (int i = 0; i < TM; ++i) a[i] = *reinterpret_cast<const f32x4*>(As + i * 32 * BE_PITCH + kc * 8);
+      for (int i = 0; i < TM; ++i) a[i] = *reinterpret_cast<const V*>(As + i * 32 * T::PITCH + kc * T::KD);
 #pragma unroll
-      for (int j = 0; j < TN; ++j) b[j] = *reinterpret_cast<const f32x4*>(Bs + j * 32 * BE_PITCH + kc * 8);
-#pragma unroll
-      for (int s = 0; s < 4; ++s)
+      for (int j = 0; j < TN; ++j) b[j] = *reinterpret_cast<const V*>(Bs + j * 32 * T::PITCH + kc * T::KD);
+      be_mma(a, b, acc);
+    }
+    if constexpr (T::KFLUSH > 0) {
+      if ((kt + 1) % T::KFLUSH == 0 || kt + 1 == nk) {   // close the 256-deep chain: a short chain rounds less
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
-          for (int j = 0; j < TN; ++j) acc[i][j] = mfma32(a[i][s], b[j][s], acc[i][j]);
-    }
-    if ((kt + 1) % BE_KFLUSH == 0 || kt + 1 == nk) {   // close the 256-deep chain: a short chain rounds less
+          for (int j = 0; j < TN; ++j) {
+            tot[i][j] += acc[i][j];
 #pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          tot[i][j] += acc[i][j];
-#pragma unroll
-          for (int v = 0; v < 16; ++v) acc[i][j][v] = 0.f;
-        }
+            for (int v = 0; v < 16; ++v) acc[i][j][v] = 0.f;
+          }
+      }
     }
     if (kt + 1 < nk) swrite(cur ^ 1);
     __syncthreads();
@@ -236,126 +283,11 @@ __global__ __launch_bounds__(BE_NT, 2) void be_gemm_kernel(const float* __restri
       for (int v = 0; v < 16; ++v) {
         const int64_t row = m0 + wm * 32 * TM + i * 32 + mfma32_row(v, h);
         if (row < M) {
-          y[row * N + col] = be_epilogue<EPI>(tot[i][j][v], bv, residual, row * N + col);
-        }
-      }
-    }
-  }
-}
-
-struct BeSeg16 {   // BeSeg with bf16 matrices
-  const uint16_t* w[3];
-  const float* b[3];
-};
-
-// be_gemm_kernel on bf16 operands: x [M, K] and the weights [seg_n, K] bf16, fp32 accumulation, be_epilogue, y
-// fp32 (EPI_RESID) or bf16 (the others).  Lane (r, h) of a wave takes, per 16-deep step, the 16 bytes k = 8 h .. 8 h + 7
-// of row r of each operand from the LDS image.
-template <int WM, int TM, int TN, int EPI, bool RAGGED>
-__global__ __launch_bounds__(BE_NT, 2) void be_gemm_bf16_kernel(const uint16_t* __restrict__ x, BeSeg16 sg, int seg_n,
-                                                                const float* __restrict__ residual,
-                                                                void* __restrict__ y_, int64_t M_, int N, int K,
-                                                                int tiles_n, BeRows rg) {
-  constexpr int WN = 4 / WM, BM = 32 * WM * TM, BN = 32 * WN * TN;
-  using OT = std::conditional_t<EPI == BE_EPI_RESID, float, uint16_t>;
-  OT* __restrict__ y = static_cast<OT*>(y_);
-  int64_t M = M_;
-  if constexpr (RAGGED) {
-    M = rg.total[0];
-    if ((int64_t)(blockIdx.x / tiles_n) * BM >= M) return;
-  }
-  __shared__ __attribute__((aligned(16))) uint16_t lds[2][(BM + BN) * BH_PITCH];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave / WN, wn = wave % WN, r = lane & 31, h = lane >> 5;
-  const int tni = blockIdx.x % tiles_n;
-  const int64_t m0 = (int64_t)(blockIdx.x / tiles_n) * BM;
-  const int n0 = tni * BN;
-
-  constexpr int AV = BM * BH_BK / 8 / BE_NT, BV = BN * BH_BK / 8 / BE_NT;
-  u32x4 ra[AV], rb[BV];
-  // K is a multiple of 32 and kk of 8: a 16-byte piece lies inside the row or wholly past it (then zeros)
-  auto gload = [&](int k0) {
-#pragma unroll
-    for (int i = 0; i < AV; ++i) {
-      const int f = tid + BE_NT * i, row = f >> 3, kk = k0 + (f & 7) * 8;
-      const int64_t g = m0 + row;
-      ra[i] = (g < M && kk < K) ? *reinterpret_cast<const u32x4*>(x + g * K + kk) : u32x4{0u, 0u, 0u, 0u};
-    }
-#pragma unroll
-    for (int i = 0; i < BV; ++i) {
-      const int f = tid + BE_NT * i, row = f >> 3, kk = k0 + (f & 7) * 8;
-      const int gn = n0 + row;
-      u32x4 v = {0u, 0u, 0u, 0u};
-      if (gn < N && kk < K) {
-        const int seg = gn / seg_n, wr = gn - seg * seg_n;
-        const uint16_t* wp = seg == 0 ? sg.w[0] : seg == 1 ? sg.w[1] : sg.w[2];
-        v = *reinterpret_cast<const u32x4*>(wp + (int64_t)wr * K + kk);
-      }
-      rb[i] = v;
-    }
-  };
-  auto swrite = [&](int buf) {
-    uint16_t* s = lds[buf];
-#pragma unroll
-    for (int i = 0; i < AV; ++i) {
-      const int f = tid + BE_NT * i;
-      *reinterpret_cast<u32x4*>(s + (f >> 3) * BH_PITCH + (f & 7) * 8) = ra[i];
-    }
-#pragma unroll
-    for (int i = 0; i < BV; ++i) {
-      const int f = tid + BE_NT * i;
-      *reinterpret_cast<u32x4*>(s + (BM + (f >> 3)) * BH_PITCH + (f & 7) * 8) = rb[i];
-    }
-  };
-
-  f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int v = 0; v < 16; ++v) acc[i][j][v] = 0.f;
-
-  const int nk = (K + BH_BK - 1) / BH_BK;
-  gload(0);
-  swrite(0);
-  __syncthreads();
-  for (int kt = 0; kt < nk; ++kt) {
-    const int cur = kt & 1;
-    if (kt + 1 < nk) gload((kt + 1) * BH_BK);
-    const uint16_t* As = lds[cur] + (wm * 32 * TM + r) * BH_PITCH + 8 * h;
-    const uint16_t* Bs = lds[cur] + (BM + wn * 32 * TN + r) * BH_PITCH + 8 * h;
-#pragma unroll
-    for (int kc = 0; kc < BH_BK / 16; ++kc) {
-      u32x4 a[TM], b[TN];
-#pragma unroll
-      for (int i = 0; i < TM; ++i) a[i] = *reinterpret_cast<const u32x4*>(As + i * 32 * BH_PITCH + kc * 16);
-#pragma unroll
-      for (int j = 0; j < TN; ++j) b[j] = *reinterpret_cast<const u32x4*>(Bs + j * 32 * BH_PITCH + kc * 16);
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = mfma32_bf16(a[i], b[j], acc[i][j]);
-    }
-    if (kt + 1 < nk) swrite(cur ^ 1);
-    __syncthreads();
-  }
-
-#pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    const int col = n0 + wn * 32 * TN + j * 32 + r;
-    if (col >= N) continue;
-    const int seg = col / seg_n;
-    const float* bp = seg == 0 ? sg.b[0] : seg == 1 ? sg.b[1] : sg.b[2];
-    const float bv = bp[col - seg * seg_n];
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-#pragma unroll
-      for (int v = 0; v < 16; ++v) {
-        const int64_t row = m0 + wm * 32 * TM + i * 32 + mfma32_row(v, h);
-        if (row < M) {
-          const float o = be_epilogue<EPI>(acc[i][j][v], bv, residual, row * N + col);
-          if constexpr (EPI == BE_EPI_RESID) y[row * N + col] = o;
+          float sum;
+          if constexpr (T::KFLUSH > 0) sum = tot[i][j][v];
+          else sum = acc[i][j][v];
+          const float o = be_epilogue<EPI>(sum, bv, residual, row * N + col);
+          if constexpr (std::is_same_v<BeOut<T, EPI>, float>) y[row * N + col] = o;
           else y[row * N + col] = be_bf16(o);
         }
       }
@@ -889,46 +821,35 @@ const char* be_check(const P* p, int64_t B, int S) {
   return nullptr;
 }
 
-struct BeLayout {   // float offsets into the workspace
-  size_t x, t, qkv, ctx, ff, total;
-};
+template <typename P>
+using BePrec = std::conditional_t<std::is_same_v<P, gr_bert_bf16_params>, BeB16, BeF32>;   // a parameter struct's format
 
-BeLayout be_layout_rows(const gr_bert_params* p, size_t M) {
-  const size_t H = (size_t)p->hidden_size;
-  BeLayout L;
-  size_t o = 0;
-  L.x = o;   o += align_up(M * H, 4);
-  L.t = o;   o += align_up(M * H, 4);
-  L.qkv = o; o += align_up(M * 3 * H, 4);
-  L.ctx = o; o += align_up(M * H, 4);
-  L.ff = o;  o += align_up(M * (size_t)p->intermediate_size, 4);
-  L.total = o;
-  return L;
-}
-
-size_t be_rows_bytes(const gr_bert_params* p, size_t M) { return be_layout_rows(p, M).total * sizeof(float); }
-
-// The bf16 calls' workspace, byte offsets: the fp32 residual stream x and the pre-LN sum t, then the bf16 GEMM
-// operands (x's copy, q/k/v, the context, the GELU output); no fp32 qkv, ctx or ff.
-struct BeLayout16 {
+// The workspace's rows' part, byte offsets, each part rounded up to 16 bytes: the fp32 residual stream x and the
+// pre-LN sum t, then what the GEMMs read and write in the format's element: x's bf16 copy (bf16 only: the fp32 GEMMs
+// read x itself, so the part is empty), q/k/v, the context, the GELU output.
+struct BeLayout {
   size_t x, t, x16, qkv, ctx, ff, total;
 };
 
-BeLayout16 be_layout16_rows(const gr_bert_bf16_params* p, size_t M) {
-  const size_t H = (size_t)p->hidden_size;
-  BeLayout16 L;
+template <typename T>
+BeLayout be_layout(size_t H, size_t I, size_t M) {
+  constexpr size_t es = sizeof(typename T::E);
+  BeLayout L;
   size_t o = 0;
   L.x = o;   o += align_up(M * H * 4, 16);
   L.t = o;   o += align_up(M * H * 4, 16);
-  L.x16 = o; o += align_up(M * H * 2, 16);
-  L.qkv = o; o += align_up(M * 3 * H * 2, 16);
-  L.ctx = o; o += align_up(M * H * 2, 16);
-  L.ff = o;  o += align_up(M * (size_t)p->intermediate_size * 2, 16);
+  L.x16 = o; o += std::is_same_v<T, BeB16> ? align_up(M * H * 2, 16) : 0;
+  L.qkv = o; o += align_up(M * 3 * H * es, 16);
+  L.ctx = o; o += align_up(M * H * es, 16);
+  L.ff = o;  o += align_up(M * I * es, 16);
   L.total = o;
   return L;
 }
 
-size_t be_rows_bytes(const gr_bert_bf16_params* p, size_t M) { return be_layout16_rows(p, M).total; }
+template <typename P>
+size_t be_rows_bytes(const P* p, size_t M) {
+  return be_layout<BePrec<P>>((size_t)p->hidden_size, (size_t)p->intermediate_size, M).total;
+}
 
 // The ragged call's workspace: the rows' part (be_rows_bytes(rows)), then off[B + 1] int64, total int64 + flag int32
 // (16 bytes), len[B] int32, each on a 16-byte boundary.
@@ -975,242 +896,169 @@ int be_pick_tile(int64_t M, int N) {
   return pick;
 }
 
-// The bf16 GEMM: be_gemm's tiles, picked the same way.  y: fp32 with EPI_RESID, bf16 otherwise.
-template <int EPI, bool RAGGED>
-int be_gemm_bf16(const char* what, const uint16_t* x, const BeSeg16& sg, int seg_n, const float* residual, void* y,
-                 int64_t M, int N, int K, hipStream_t st, const BeRows& rg) {
-  const int pick = be_pick_tile(M, N);
-  const int tn = (N + BE_TILES[pick].bn - 1) / BE_TILES[pick].bn;
-  const dim3 grid((unsigned)(((M + BE_TILES[pick].bm - 1) / BE_TILES[pick].bm) * tn));
-  if (pick == 0)
-    be_gemm_bf16_kernel<2, 2, 2, EPI, RAGGED><<<grid, dim3(BE_NT), 0, st>>>(x, sg, seg_n, residual, y, M, N, K, tn, rg);
-  else if (pick == 1)
-    be_gemm_bf16_kernel<2, 1, 2, EPI, RAGGED><<<grid, dim3(BE_NT), 0, st>>>(x, sg, seg_n, residual, y, M, N, K, tn, rg);
-  else
-    be_gemm_bf16_kernel<4, 1, 3, EPI, RAGGED><<<grid, dim3(BE_NT), 0, st>>>(x, sg, seg_n, residual, y, M, N, K, tn, rg);
-  return check_launch(what);
-}
-
+// y: fp32 with EPI_RESID or from BeF32, bf16 otherwise.
 // RAGGED: M is the caller's row bound (it sizes the grid and picks the tile), the row count is rg.total[0].
-template <int EPI, bool RAGGED>
-int be_gemm(const char* what, const float* x, const BeSeg& sg, int seg_n, const float* residual, float* y, int64_t M,
-            int N, int K, hipStream_t st, const BeRows& rg) {
+template <typename T, int EPI, bool RAGGED>
+int be_gemm(const char* what, const typename T::E* x, const BeSeg<typename T::E>& sg, int seg_n, const float* residual,
+            BeOut<T, EPI>* y, int64_t M, int N, int K, hipStream_t st, const BeRows& rg) {
   const int pick = be_pick_tile(M, N);
   const int tn = (N + BE_TILES[pick].bn - 1) / BE_TILES[pick].bn;
   const dim3 grid((unsigned)(((M + BE_TILES[pick].bm - 1) / BE_TILES[pick].bm) * tn));
   if (pick == 0)
-    be_gemm_kernel<2, 2, 2, EPI, RAGGED><<<grid, dim3(BE_NT), 0, st>>>(x, sg, seg_n, residual, y, M, N, K, tn, rg);
+    be_gemm_kernel<T, 2, 2, 2, EPI, RAGGED><<<grid, dim3(BE_NT), 0, st>>>(x, sg, seg_n, residual, y, M, N, K, tn, rg);
   else if (pick == 1)
-    be_gemm_kernel<2, 1, 2, EPI, RAGGED><<<grid, dim3(BE_NT), 0, st>>>(x, sg, seg_n, residual, y, M, N, K, tn, rg);
+    be_gemm_kernel<T, 2, 1, 2, EPI, RAGGED><<<grid, dim3(BE_NT), 0, st>>>(x, sg, seg_n, residual, y, M, N, K, tn, rg);
   else
-    be_gemm_kernel<4, 1, 3, EPI, RAGGED><<<grid, dim3(BE_NT), 0, st>>>(x, sg, seg_n, residual, y, M, N, K, tn, rg);
+    be_gemm_kernel<T, 4, 1, 3, EPI, RAGGED><<<grid, dim3(BE_NT), 0, st>>>(x, sg, seg_n, residual, y, M, N, K, tn, rg);
   return check_launch(what);
 }
 
-// The encoder stack over M rows of X (RAGGED: M bounds the packed rows, rg.total[0] counts them), the last
-// LayerNorm into last: 7 launches per layer.
-template <bool RAGGED>
-int be_stack(const gr_bert_params* p, const int64_t* attention_mask, int64_t B, int S, int64_t M, float* ws,
-             const BeLayout& L, float* last, hipStream_t st, const BeRows& rg) {
-  const int H = p->hidden_size, I = p->intermediate_size, NH = p->num_heads, HD = p->head_dim;
-  float *X = ws + L.x, *T = ws + L.t, *QKV = ws + L.qkv, *CTX = ws + L.ctx, *FF = ws + L.ff;
-  const unsigned row_blocks = (unsigned)((M + 3) / 4);
-  const float scale = sas_scale(HD);
+template <int HD, bool RAGGED, typename E>
+void be_attn(const E* qkv, const int64_t* mask, E* ctx, int64_t B, int S, int NH, hipStream_t st, const BeRows& rg) {
   const int nqt = (S + BE_QT - 1) / BE_QT;
-  for (int l = 0; l < p->num_layers; ++l) {
-    const float* const* w = p->layer[l];
-    const BeSeg qkv_w = {{w[0], w[2], w[4]}, {w[1], w[3], w[5]}};
-    if (int rc = be_gemm<BE_EPI_BIAS, RAGGED>("bert q/k/v", X, qkv_w, H, nullptr, QKV, M, 3 * H, H, st, rg)) return rc;
-    const dim3 ag((unsigned)(B * NH * nqt));
-    if (HD == 64)
-      be_attn_kernel<64, RAGGED><<<ag, dim3(256), 0, st>>>(QKV, attention_mask, CTX, S, NH, nqt, scale, rg);
-    else
-      be_attn_kernel<32, RAGGED><<<ag, dim3(256), 0, st>>>(QKV, attention_mask, CTX, S, NH, nqt, scale, rg);
-    if (int rc = check_launch("be_attn_kernel")) return rc;
-    const BeSeg ao = {{w[6], nullptr, nullptr}, {w[7], nullptr, nullptr}};
-    if (int rc = be_gemm<BE_EPI_RESID, RAGGED>("bert attention output + residual", CTX, ao, H, X, T, M, H, H, st, rg))
-      return rc;
-    be_ln_kernel<RAGGED, false><<<dim3(row_blocks), dim3(256), 0, st>>>(T, w[8], w[9], p->eps, H, M, X, nullptr, rg);
-    if (int rc = check_launch("be_ln_kernel")) return rc;
-    const BeSeg inter = {{w[10], nullptr, nullptr}, {w[11], nullptr, nullptr}};
-    if (int rc = be_gemm<BE_EPI_GELU, RAGGED>("bert intermediate + gelu", X, inter, I, nullptr, FF, M, I, H, st, rg))
-      return rc;
-    const BeSeg outw = {{w[12], nullptr, nullptr}, {w[13], nullptr, nullptr}};
-    if (int rc = be_gemm<BE_EPI_RESID, RAGGED>("bert output + residual", FF, outw, H, X, T, M, H, I, st, rg)) return rc;
-    be_ln_kernel<RAGGED, false><<<dim3(row_blocks), dim3(256), 0, st>>>(T, w[14], w[15], p->eps, H, M,
-                                                                        l + 1 == p->num_layers ? last : X, nullptr, rg);
-    if (int rc = check_launch("be_ln_kernel")) return rc;
-  }
-  return GR_OK;
+  const dim3 grid((unsigned)(B * NH * nqt));
+  if constexpr (std::is_same_v<E, float>)
+    be_attn_kernel<HD, RAGGED><<<grid, dim3(256), 0, st>>>(qkv, mask, ctx, S, NH, nqt, sas_scale(HD), rg);
+  else
+    be_attn_bf16_kernel<HD, RAGGED><<<grid, dim3(256), 0, st>>>(qkv, mask, ctx, S, NH, nqt, sas_scale(HD), rg);
 }
 
-bool be_weights_ok(const gr_bert_params* p) {
-  bool ok = p->word && p->position && p->token_type && p->emb_ln_w && p->emb_ln_b;
-  for (int l = 0; ok && l < p->num_layers; ++l)
-    for (int i = 0; i < 16; ++i) ok = ok && p->layer[l][i] && aligned16(p->layer[l][i]);
-  return ok;
+// A layer's parameters by role, whichever struct holds them: the six [out, in] matrices in the format's element and
+// the ten fp32 vectors, in gr_bert_bf16_params' order.
+enum { BE_W_Q, BE_W_K, BE_W_V, BE_W_ATTN_OUT, BE_W_INTER, BE_W_OUT };
+enum { BE_B_Q, BE_B_K, BE_B_V, BE_B_ATTN_OUT, BE_LN1_W, BE_LN1_B, BE_B_INTER, BE_B_OUT, BE_LN2_W, BE_LN2_B };
+template <typename E>
+struct BeLayer {
+  const E* w[6];
+  const float* v[10];
+};
+
+BeLayer<float> be_layer(const gr_bert_params* p, int l) {   // layer[l]: each weight followed by its bias
+  const float* const* a = p->layer[l];
+  return {{a[0], a[2], a[4], a[6], a[10], a[12]}, {a[1], a[3], a[5], a[7], a[8], a[9], a[11], a[13], a[14], a[15]}};
 }
 
-bool be_weights_ok(const gr_bert_bf16_params* p) {
+BeLayer<uint16_t> be_layer(const gr_bert_bf16_params* p, int l) {
+  BeLayer<uint16_t> y;
+  for (int i = 0; i < 6; ++i) y.w[i] = p->matrix[l][i];
+  for (int i = 0; i < 10; ++i) y.v[i] = p->vector[l][i];
+  return y;
+}
+
+template <typename P>
+bool be_weights_ok(const P* p) {
   bool ok = p->word && p->position && p->token_type && p->emb_ln_w && p->emb_ln_b;
   for (int l = 0; ok && l < p->num_layers; ++l) {
-    for (int i = 0; i < 6; ++i) ok = ok && p->matrix[l][i] && aligned16(p->matrix[l][i]);
-    for (int i = 0; i < 10; ++i) ok = ok && p->vector[l][i] && aligned16(p->vector[l][i]);
+    const auto y = be_layer(p, l);
+    for (int i = 0; i < 6; ++i) ok = ok && y.w[i] && aligned16(y.w[i]);
+    for (int i = 0; i < 10; ++i) ok = ok && y.v[i] && aligned16(y.v[i]);
   }
   return ok;
 }
 
-// Embeddings + LayerNorm into the workspace's x, then the stack with the last LayerNorm into last (the workspace's x
-// when null); returns through *last_out where the last hidden state lies.
-template <bool RAGGED>
-int be_forward(const gr_bert_params* p, const int64_t* input_ids, const int64_t* attention_mask,
-               const int64_t* token_type_ids, int64_t B, int S, int64_t M, void* workspace, float* last,
-               const float** last_out, hipStream_t st, const BeRows& rg) {
-  const int H = p->hidden_size;
-  const BeLayout L = be_layout_rows(p, (size_t)M);
-  float* ws = static_cast<float*>(workspace);
+// Embeddings + LayerNorm into the workspace's x, then the encoder stack over M rows (RAGGED: M bounds the packed
+// rows, rg.total[0] counts them), the last LayerNorm into last (the workspace's x when null); returns through
+// *last_out where the last hidden state lies.  2 + 7 num_layers launches with the caller's pooling.  P picks the
+// format (the bf16 contract is at the head of this file): with bf16 each LayerNorm also writes the copy the next GEMM
+// reads, with fp32 that GEMM reads x itself.
+template <bool RAGGED, typename P>
+int be_forward(const P* p, const int64_t* input_ids, const int64_t* attention_mask, const int64_t* token_type_ids,
+               int64_t B, int S, int64_t M, void* workspace, float* last, const float** last_out, hipStream_t st,
+               const BeRows& rg) {
+  using T = BePrec<P>;
+  using E = typename T::E;
+  constexpr bool B16 = std::is_same_v<T, BeB16>;
+  const int H = p->hidden_size, I = p->intermediate_size, NH = p->num_heads, HD = p->head_dim;
+  const BeLayout L = be_layout<T>((size_t)H, (size_t)I, (size_t)M);
+  char* wb = static_cast<char*>(workspace);
+  float *X = reinterpret_cast<float*>(wb + L.x), *SUM = reinterpret_cast<float*>(wb + L.t);
+  uint16_t* X16 = B16 ? reinterpret_cast<uint16_t*>(wb + L.x16) : nullptr;
+  E *QKV = reinterpret_cast<E*>(wb + L.qkv), *CTX = reinterpret_cast<E*>(wb + L.ctx);
+  E* FF = reinterpret_cast<E*>(wb + L.ff);
+  const E* XA;   // x as the GEMMs read it
+  if constexpr (B16) XA = X16;
+  else XA = X;
   const dim3 eg = RAGGED ? dim3((unsigned)B, (unsigned)((S + 3) / 4)) : dim3((unsigned)((M + 3) / 4));
   // RAGGED: B x ceil(S / 4) <= 65536 x 128 workgroups
-  be_embed_ln_kernel<RAGGED, false><<<eg, dim3(256), 0, st>>>(
-      input_ids, token_type_ids, p->word, p->position, p->token_type, p->emb_ln_w, p->emb_ln_b, p->eps, p->vocab_size,
-      p->type_vocab_size, S, H, M, ws + L.x, nullptr, rg);
-  if (int rc = check_launch("be_embed_ln_kernel")) return rc;
-  if (!last) last = ws + L.x;
-  *last_out = last;
-  return be_stack<RAGGED>(p, attention_mask, B, S, M, ws, L, last, st, rg);
-}
-
-// The same on bf16 GEMM operands (the contract at the head of this file): 2 + 7 num_layers launches as well.
-// matrix[l] = {query, key, value, attention.output.dense, intermediate.dense, output.dense}.weight,
-// vector[l] = {query, key, value, attention.output.dense}.bias, attention.output.LayerNorm.{weight, bias},
-//             {intermediate.dense, output.dense}.bias, output.LayerNorm.{weight, bias}.
-template <bool RAGGED>
-int be_forward(const gr_bert_bf16_params* p, const int64_t* input_ids, const int64_t* attention_mask,
-               const int64_t* token_type_ids, int64_t B, int S, int64_t M, void* workspace, float* last,
-               const float** last_out, hipStream_t st, const BeRows& rg) {
-  const int H = p->hidden_size, I = p->intermediate_size, NH = p->num_heads, HD = p->head_dim;
-  const BeLayout16 L = be_layout16_rows(p, (size_t)M);
-  char* wb = static_cast<char*>(workspace);
-  float *X = reinterpret_cast<float*>(wb + L.x), *T = reinterpret_cast<float*>(wb + L.t);
-  uint16_t *X16 = reinterpret_cast<uint16_t*>(wb + L.x16), *QKV = reinterpret_cast<uint16_t*>(wb + L.qkv);
-  uint16_t *CTX = reinterpret_cast<uint16_t*>(wb + L.ctx), *FF = reinterpret_cast<uint16_t*>(wb + L.ff);
-  const dim3 eg = RAGGED ? dim3((unsigned)B, (unsigned)((S + 3) / 4)) : dim3((unsigned)((M + 3) / 4));
-  be_embed_ln_kernel<RAGGED, true><<<eg, dim3(256), 0, st>>>(
+  be_embed_ln_kernel<RAGGED, B16><<<eg, dim3(256), 0, st>>>(
       input_ids, token_type_ids, p->word, p->position, p->token_type, p->emb_ln_w, p->emb_ln_b, p->eps, p->vocab_size,
       p->type_vocab_size, S, H, M, X, X16, rg);
   if (int rc = check_launch("be_embed_ln_kernel")) return rc;
   if (!last) last = X;
   *last_out = last;
-  const unsigned row_blocks = (unsigned)((M + 3) / 4);
-  const float scale = sas_scale(HD);
-  const int nqt = (S + BE_QT - 1) / BE_QT;
+  auto ln = [&](const float* w, const float* b, float* out) {   // LayerNorm of SUM: a wave per row
+    be_ln_kernel<RAGGED, B16><<<dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st>>>(SUM, w, b, p->eps, H, M, out, X16, rg);
+    return check_launch("be_ln_kernel");
+  };
   for (int l = 0; l < p->num_layers; ++l) {
-    const uint16_t* const* w = p->matrix[l];
-    const float* const* v = p->vector[l];
-    const BeSeg16 qkv_w = {{w[0], w[1], w[2]}, {v[0], v[1], v[2]}};
-    if (int rc = be_gemm_bf16<BE_EPI_BIAS, RAGGED>("bert bf16 q/k/v", X16, qkv_w, H, nullptr, QKV, M, 3 * H, H, st, rg))
+    const BeLayer<E> y = be_layer(p, l);
+    const BeSeg<E> qkv_w = {{y.w[BE_W_Q], y.w[BE_W_K], y.w[BE_W_V]}, {y.v[BE_B_Q], y.v[BE_B_K], y.v[BE_B_V]}};
+    if (int rc = be_gemm<T, BE_EPI_BIAS, RAGGED>("bert q/k/v", XA, qkv_w, H, nullptr, QKV, M, 3 * H, H, st, rg)) return rc;
+    if (HD == 64) be_attn<64, RAGGED>(QKV, attention_mask, CTX, B, S, NH, st, rg);
+    else be_attn<32, RAGGED>(QKV, attention_mask, CTX, B, S, NH, st, rg);
+    if (int rc = check_launch("bert attention")) return rc;
+    const BeSeg<E> ao = {{y.w[BE_W_ATTN_OUT], nullptr, nullptr}, {y.v[BE_B_ATTN_OUT], nullptr, nullptr}};
+    if (int rc = be_gemm<T, BE_EPI_RESID, RAGGED>("bert attention output + residual", CTX, ao, H, X, SUM, M, H, H, st, rg))
       return rc;
-    const dim3 ag((unsigned)(B * NH * nqt));
-    if (HD == 64)
-      be_attn_bf16_kernel<64, RAGGED><<<ag, dim3(256), 0, st>>>(QKV, attention_mask, CTX, S, NH, nqt, scale, rg);
-    else
-      be_attn_bf16_kernel<32, RAGGED><<<ag, dim3(256), 0, st>>>(QKV, attention_mask, CTX, S, NH, nqt, scale, rg);
-    if (int rc = check_launch("be_attn_bf16_kernel")) return rc;
-    const BeSeg16 ao = {{w[3], nullptr, nullptr}, {v[3], nullptr, nullptr}};
-    if (int rc = be_gemm_bf16<BE_EPI_RESID, RAGGED>("bert bf16 attention output + residual", CTX, ao, H, X, T, M, H, H,
-                                                    st, rg))
+    if (int rc = ln(y.v[BE_LN1_W], y.v[BE_LN1_B], X)) return rc;
+    const BeSeg<E> inter = {{y.w[BE_W_INTER], nullptr, nullptr}, {y.v[BE_B_INTER], nullptr, nullptr}};
+    if (int rc = be_gemm<T, BE_EPI_GELU, RAGGED>("bert intermediate + gelu", XA, inter, I, nullptr, FF, M, I, H, st, rg))
       return rc;
-    be_ln_kernel<RAGGED, true><<<dim3(row_blocks), dim3(256), 0, st>>>(T, v[4], v[5], p->eps, H, M, X, X16, rg);
-    if (int rc = check_launch("be_ln_kernel")) return rc;
-    const BeSeg16 inter = {{w[4], nullptr, nullptr}, {v[6], nullptr, nullptr}};
-    if (int rc = be_gemm_bf16<BE_EPI_GELU, RAGGED>("bert bf16 intermediate + gelu", X16, inter, I, nullptr, FF, M, I, H,
-                                                   st, rg))
+    const BeSeg<E> outw = {{y.w[BE_W_OUT], nullptr, nullptr}, {y.v[BE_B_OUT], nullptr, nullptr}};
+    if (int rc = be_gemm<T, BE_EPI_RESID, RAGGED>("bert output + residual", FF, outw, H, X, SUM, M, H, I, st, rg))
       return rc;
-    const BeSeg16 outw = {{w[5], nullptr, nullptr}, {v[7], nullptr, nullptr}};
-    if (int rc = be_gemm_bf16<BE_EPI_RESID, RAGGED>("bert bf16 output + residual", FF, outw, H, X, T, M, H, I, st, rg))
-      return rc;
-    be_ln_kernel<RAGGED, true><<<dim3(row_blocks), dim3(256), 0, st>>>(T, v[8], v[9], p->eps, H, M,
-                                                                       l + 1 == p->num_layers ? last : X, X16, rg);
-    if (int rc = check_launch("be_ln_kernel")) return rc;
+    if (int rc = ln(y.v[BE_LN2_W], y.v[BE_LN2_B], l + 1 == p->num_layers ? last : X)) return rc;
   }
   return GR_OK;
 }
 
-// The padded entries' body: the checks in gr_bert_embed_f32's order, then the launches.  who: "<entry>: ";
-// ws_query: the entry's workspace query, named in the workspace message.
-template <typename P>
+// The four entries' body: the checks in gr_bert_embed_f32's order, then the launches.  who: "<entry>: "; ws_query: the
+// entry's workspace query, named in the workspace message.  hidden: hidden_out [B, S, H], or RAGGED hidden_rows_out
+// [rows_bound, H]; rows_bound and row_offsets_out are the ragged entries' (the padded ones pass 0 and null).
+template <bool RAGGED, typename P>
 int be_embed(const std::string& who, const char* ws_query, const P* p, const int64_t* input_ids,
-             const int64_t* attention_mask, const int64_t* token_type_ids, int64_t B, int32_t S, int32_t pooling,
-             float* pooled_out, float* hidden_out, void* workspace, size_t workspace_bytes, void* stream) {
+             const int64_t* attention_mask, const int64_t* token_type_ids, int64_t B, int32_t S, int64_t rows_bound,
+             int32_t pooling, float* pooled_out, float* hidden, int64_t* row_offsets_out, void* workspace,
+             size_t workspace_bytes, void* stream) {
   clear_error();
   if (const char* why = be_check(p, B, S)) return fail(!p || B < 0 ? GR_ERR_ARG : GR_ERR_UNSUPPORTED, who + why);
+  if (RAGGED && B > 0 && rows_bound < 1) return fail(GR_ERR_ARG, who + "rows_bound must be at least 1");
   if (pooling != GR_BERT_POOL_NONE && pooling != GR_BERT_POOL_MEAN_NO_CLS && pooling != GR_BERT_POOL_CLS)
     return fail(GR_ERR_ARG, who + "pooling must be GR_BERT_POOL_NONE, _MEAN_NO_CLS or _CLS");
   if (B == 0) return GR_OK;
-  if (!workspace || workspace_bytes < be_bytes(p, B, S) || !aligned16(workspace))
+  const BeRagged R = be_ragged(p, B, S, rows_bound);   // read by the ragged entries only
+  if (!workspace || workspace_bytes < (RAGGED ? R.bytes : be_bytes(p, B, S)) || !aligned16(workspace))
     return fail(GR_ERR_WORKSPACE, who + "workspace missing, misaligned or smaller than " + ws_query);
   if (!input_ids) return fail(GR_ERR_ARG, who + "input_ids is null");
   if (pooling != GR_BERT_POOL_NONE && !pooled_out) return fail(GR_ERR_ARG, who + "pooled_out is null");
-  if (pooling == GR_BERT_POOL_NONE && !hidden_out)
-    return fail(GR_ERR_ARG, who + "hidden_out is null and pooling is GR_BERT_POOL_NONE: nothing to compute");
-  if (hidden_out && !aligned16(hidden_out)) return fail(GR_ERR_ARG, who + "hidden_out must be 16-byte aligned");
+  if (pooling == GR_BERT_POOL_NONE && (!hidden || (RAGGED && !row_offsets_out)))
+    return fail(GR_ERR_ARG, who + (RAGGED ? "hidden_rows_out or row_offsets_out" : "hidden_out") +
+                                " is null and pooling is GR_BERT_POOL_NONE: nothing to compute");
+  if (hidden && !aligned16(hidden))
+    return fail(GR_ERR_ARG, who + (RAGGED ? "hidden_rows_out" : "hidden_out") + " must be 16-byte aligned");
   if (!be_weights_ok(p)) return fail(GR_ERR_ARG, who + "a weight pointer is null or not 16-byte aligned");
 
   const int H = p->hidden_size;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const BeRows none = {nullptr, nullptr, nullptr, nullptr};
+  BeRows rg = {nullptr, nullptr, nullptr, nullptr};
+  if constexpr (RAGGED) {
+    char* wb = static_cast<char*>(workspace);
+    int64_t* off = reinterpret_cast<int64_t*>(wb + R.off);
+    int64_t* total = reinterpret_cast<int64_t*>(wb + R.total);
+    int32_t* flag = reinterpret_cast<int32_t*>(wb + R.total + sizeof(int64_t));
+    int32_t* len = reinterpret_cast<int32_t*>(wb + R.len);
+    rg = {len, off, total, flag};
+    be_len_kernel<<<dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st>>>(attention_mask, B, S, len);
+    if (int rc = check_launch("be_len_kernel")) return rc;
+    be_offsets_kernel<<<dim3(1), dim3(BE_SCAN_NT), 0, st>>>(len, B, R.rows, off, total, flag, row_offsets_out);
+    if (int rc = check_launch("be_offsets_kernel")) return rc;
+  }
   const float* last = nullptr;
-  if (int rc = be_forward<false>(p, input_ids, attention_mask, token_type_ids, B, S, B * S, workspace, hidden_out, &last,
-                                 st, none))
+  if (int rc = be_forward<RAGGED>(p, input_ids, attention_mask, token_type_ids, B, S, RAGGED ? R.rows : B * S, workspace,
+                                  hidden, &last, st, rg))
     return rc;
-  be_pool_kernel<false><<<dim3((unsigned)B, (unsigned)((H + 255) / 256)), dim3(256), 0, st>>>(
-      last, attention_mask, S, H, pooling, pooled_out, hidden_out, none);
-  return check_launch("be_pool_kernel");
-}
-
-// The ragged entries' body, likewise.
-template <typename P>
-int be_embed_ragged(const std::string& who, const char* ws_query, const P* p, const int64_t* input_ids,
-                    const int64_t* attention_mask, const int64_t* token_type_ids, int64_t B, int32_t S,
-                    int64_t rows_bound, int32_t pooling, float* pooled_out, float* hidden_rows_out,
-                    int64_t* row_offsets_out, void* workspace, size_t workspace_bytes, void* stream) {
-  clear_error();
-  if (const char* why = be_check(p, B, S)) return fail(!p || B < 0 ? GR_ERR_ARG : GR_ERR_UNSUPPORTED, who + why);
-  if (B > 0 && rows_bound < 1) return fail(GR_ERR_ARG, who + "rows_bound must be at least 1");
-  if (pooling != GR_BERT_POOL_NONE && pooling != GR_BERT_POOL_MEAN_NO_CLS && pooling != GR_BERT_POOL_CLS)
-    return fail(GR_ERR_ARG, who + "pooling must be GR_BERT_POOL_NONE, _MEAN_NO_CLS or _CLS");
-  if (B == 0) return GR_OK;
-  const BeRagged R = be_ragged(p, B, S, rows_bound);
-  if (!workspace || workspace_bytes < R.bytes || !aligned16(workspace))
-    return fail(GR_ERR_WORKSPACE, who + "workspace missing, misaligned or smaller than " + ws_query);
-  if (!input_ids) return fail(GR_ERR_ARG, who + "input_ids is null");
-  if (pooling != GR_BERT_POOL_NONE && !pooled_out) return fail(GR_ERR_ARG, who + "pooled_out is null");
-  if (pooling == GR_BERT_POOL_NONE && (!hidden_rows_out || !row_offsets_out))
-    return fail(GR_ERR_ARG, who + "hidden_rows_out or row_offsets_out is null and pooling is GR_BERT_POOL_NONE: "
-                                  "nothing to compute");
-  if (hidden_rows_out && !aligned16(hidden_rows_out))
-    return fail(GR_ERR_ARG, who + "hidden_rows_out must be 16-byte aligned");
-  if (!be_weights_ok(p)) return fail(GR_ERR_ARG, who + "a weight pointer is null or not 16-byte aligned");
-
-  const int H = p->hidden_size;
-  char* wb = static_cast<char*>(workspace);
-  int64_t* off = reinterpret_cast<int64_t*>(wb + R.off);
-  int64_t* total = reinterpret_cast<int64_t*>(wb + R.total);
-  int32_t* flag = reinterpret_cast<int32_t*>(wb + R.total + sizeof(int64_t));
-  int32_t* len = reinterpret_cast<int32_t*>(wb + R.len);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const BeRows rg = {len, off, total, flag};
-
-  be_len_kernel<<<dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st>>>(attention_mask, B, S, len);
-  if (int rc = check_launch("be_len_kernel")) return rc;
-  be_offsets_kernel<<<dim3(1), dim3(BE_SCAN_NT), 0, st>>>(len, B, R.rows, off, total, flag, row_offsets_out);
-  if (int rc = check_launch("be_offsets_kernel")) return rc;
-  const float* last = nullptr;
-  if (int rc = be_forward<true>(p, input_ids, attention_mask, token_type_ids, B, S, R.rows, workspace, hidden_rows_out,
-                                &last, st, rg))
-    return rc;
-  be_pool_kernel<true><<<dim3((unsigned)B, (unsigned)((H + 255) / 256)), dim3(256), 0, st>>>(
-      last, attention_mask, S, H, pooling, pooled_out, nullptr, rg);
+  be_pool_kernel<RAGGED><<<dim3((unsigned)B, (unsigned)((H + 255) / 256)), dim3(256), 0, st>>>(
+      last, attention_mask, S, H, pooling, pooled_out, RAGGED ? nullptr : hidden, rg);
   return check_launch("be_pool_kernel");
 }
 
@@ -1226,8 +1074,9 @@ extern "C" int gr_bert_embed_f32(const gr_bert_params* p, const int64_t* input_i
                                  const int64_t* token_type_ids, int64_t B, int32_t S, int32_t pooling,
                                  float* pooled_out, float* hidden_out, void* workspace, size_t workspace_bytes,
                                  void* stream) {
-  return gr::be_embed("gr_bert_embed_f32: ", "gr_bert_embed_workspace_bytes", p, input_ids, attention_mask,
-                      token_type_ids, B, S, pooling, pooled_out, hidden_out, workspace, workspace_bytes, stream);
+  return gr::be_embed<false>("gr_bert_embed_f32: ", "gr_bert_embed_workspace_bytes", p, input_ids, attention_mask,
+                             token_type_ids, B, S, 0, pooling, pooled_out, hidden_out, nullptr, workspace,
+                             workspace_bytes, stream);
 }
 
 extern "C" size_t gr_bert_embed_ragged_workspace_bytes(const gr_bert_params* p, int64_t B, int32_t S,
@@ -1241,9 +1090,9 @@ extern "C" int gr_bert_embed_ragged_f32(const gr_bert_params* p, const int64_t* 
                                         int32_t S, int64_t rows_bound, int32_t pooling, float* pooled_out,
                                         float* hidden_rows_out, int64_t* row_offsets_out, void* workspace,
                                         size_t workspace_bytes, void* stream) {
-  return gr::be_embed_ragged("gr_bert_embed_ragged_f32: ", "gr_bert_embed_ragged_workspace_bytes", p, input_ids,
-                             attention_mask, token_type_ids, B, S, rows_bound, pooling, pooled_out, hidden_rows_out,
-                             row_offsets_out, workspace, workspace_bytes, stream);
+  return gr::be_embed<true>("gr_bert_embed_ragged_f32: ", "gr_bert_embed_ragged_workspace_bytes", p, input_ids,
+                            attention_mask, token_type_ids, B, S, rows_bound, pooling, pooled_out, hidden_rows_out,
+                            row_offsets_out, workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t gr_bert_embed_bf16_workspace_bytes(const gr_bert_bf16_params* p, int64_t B, int32_t S) {
@@ -1255,8 +1104,9 @@ extern "C" int gr_bert_embed_bf16(const gr_bert_bf16_params* p, const int64_t* i
                                   const int64_t* attention_mask, const int64_t* token_type_ids, int64_t B, int32_t S,
                                   int32_t pooling, float* pooled_out, float* hidden_out, void* workspace,
                                   size_t workspace_bytes, void* stream) {
-  return gr::be_embed("gr_bert_embed_bf16: ", "gr_bert_embed_bf16_workspace_bytes", p, input_ids, attention_mask,
-                      token_type_ids, B, S, pooling, pooled_out, hidden_out, workspace, workspace_bytes, stream);
+  return gr::be_embed<false>("gr_bert_embed_bf16: ", "gr_bert_embed_bf16_workspace_bytes", p, input_ids, attention_mask,
+                             token_type_ids, B, S, 0, pooling, pooled_out, hidden_out, nullptr, workspace,
+                             workspace_bytes, stream);
 }
 
 extern "C" size_t gr_bert_embed_ragged_bf16_workspace_bytes(const gr_bert_bf16_params* p, int64_t B, int32_t S,
@@ -1270,8 +1120,8 @@ extern "C" int gr_bert_embed_ragged_bf16(const gr_bert_bf16_params* p, const int
                                          int32_t S, int64_t rows_bound, int32_t pooling, float* pooled_out,
                                          float* hidden_rows_out, int64_t* row_offsets_out, void* workspace,
                                          size_t workspace_bytes, void* stream) {
-  return gr::be_embed_ragged("gr_bert_embed_ragged_bf16: ", "gr_bert_embed_ragged_bf16_workspace_bytes", p, input_ids,
-                             attention_mask, token_type_ids, B, S, rows_bound, pooling, pooled_out, hidden_rows_out,
-                             row_offsets_out, workspace, workspace_bytes, stream);
+  return gr::be_embed<true>("gr_bert_embed_ragged_bf16: ", "gr_bert_embed_ragged_bf16_workspace_bytes", p, input_ids,
+                            attention_mask, token_type_ids, B, S, rows_bound, pooling, pooled_out, hidden_rows_out,
+                            row_offsets_out, workspace, workspace_bytes, stream);
 }
 

@@ -2311,6 +2311,27 @@ def _bert_ids(name, t, B, S):
     return t.contiguous()
 
 
+def _bert_args(fn, binding, input_ids, attention_mask, token_type_ids, pooling):
+    """What ``bert_embed`` and ``bert_embed_ragged`` (``fn``: the one named in the shape message) open with -> the
+    checked [B, S] int64 tensors, the pooling mode and ``pooled`` [B, H] (None without pooling)."""
+    if pooling not in BERT_POOLINGS:
+        raise ValueError(f"pooling={pooling!r} must be 'mean_no_cls', 'cls' or None")
+    mode = BERT_POOLINGS[pooling]
+    if input_ids.dim() != 2:
+        raise RuntimeError(f"{fn} takes [B, S] token ids, got {tuple(input_ids.shape)}")
+    B, S = input_ids.shape
+    input_ids = _bert_ids("input_ids", input_ids, B, S)
+    bert_check(binding.cfg, S, B)
+    if attention_mask is not None:
+        attention_mask = _bert_ids("attention_mask", attention_mask, B, S)
+    if token_type_ids is not None:
+        token_type_ids = _bert_ids("token_type_ids", token_type_ids, B, S)
+    pooled = None
+    if mode != L.GR_BERT_POOL_NONE:
+        pooled = torch.empty((B, binding.params.hidden_size), dtype=torch.float32, device=input_ids.device)
+    return input_ids, attention_mask, token_type_ids, mode, pooled
+
+
 def bert_embed(binding, input_ids, attention_mask=None, token_type_ids=None, pooling="mean_no_cls", with_hidden=False):
     """``gr_bert_embed_f32``: embeddings, the encoder stack and the pooling in one C call, nothing synchronises.
     The binding's type picks the precision: a ``BertBf16Binding`` calls ``gr_bert_embed_bf16`` (the outputs are
@@ -2319,22 +2340,10 @@ def bert_embed(binding, input_ids, attention_mask=None, token_type_ids=None, poo
     None (zeros).  pooling "mean_no_cls" (the live rows after position 0, 0 when there is none), "cls" (row 0) or
     None -> pooled [B, H][, hidden [B, S, H] with ``with_hidden``], or hidden alone when pooling is None.  A
     sequence with no live key gives zeros."""
-    if pooling not in BERT_POOLINGS:
-        raise ValueError(f"pooling={pooling!r} must be 'mean_no_cls', 'cls' or None")
-    mode = BERT_POOLINGS[pooling]
-    if input_ids.dim() != 2:
-        raise RuntimeError(f"bert_embed takes [B, S] token ids, got {tuple(input_ids.shape)}")
-    B, S = input_ids.shape
-    input_ids = _bert_ids("input_ids", input_ids, B, S)
-    bert_check(binding.cfg, S, B)
-    if attention_mask is not None:
-        attention_mask = _bert_ids("attention_mask", attention_mask, B, S)
-    if token_type_ids is not None:
-        token_type_ids = _bert_ids("token_type_ids", token_type_ids, B, S)
-    dev = input_ids.device
-    H = binding.params.hidden_size
-    want_hidden = with_hidden or mode == L.GR_BERT_POOL_NONE
-    pooled = torch.empty((B, H), dtype=torch.float32, device=dev) if mode != L.GR_BERT_POOL_NONE else None
+    input_ids, attention_mask, token_type_ids, mode, pooled = _bert_args("bert_embed", binding, input_ids, attention_mask,
+                                                                         token_type_ids, pooling)
+    (B, S), dev, H = input_ids.shape, input_ids.device, binding.params.hidden_size
+    want_hidden = with_hidden or pooled is None
     hidden = torch.empty((B, S, H), dtype=torch.float32, device=dev) if want_hidden else None
     if B > 0:
         nbytes = binding.workspace_bytes(B, S)
@@ -2359,25 +2368,13 @@ def bert_embed_ragged(binding, input_ids, attention_mask=None, token_type_ids=No
     -> pooled [B, H], or with ``with_hidden`` (pooled, hidden_rows [rows_bound, H], row_offsets [B + 1] int64):
     ``hidden_rows[row_offsets[b] + s]`` is position s of sequence b, rows from ``row_offsets[B]`` on are unset.
     ``pooling=None`` returns (hidden_rows, row_offsets)."""
-    if pooling not in BERT_POOLINGS:
-        raise ValueError(f"pooling={pooling!r} must be 'mean_no_cls', 'cls' or None")
-    mode = BERT_POOLINGS[pooling]
-    if input_ids.dim() != 2:
-        raise RuntimeError(f"bert_embed_ragged takes [B, S] token ids, got {tuple(input_ids.shape)}")
-    B, S = input_ids.shape
-    input_ids = _bert_ids("input_ids", input_ids, B, S)
-    bert_check(binding.cfg, S, B)
-    if attention_mask is not None:
-        attention_mask = _bert_ids("attention_mask", attention_mask, B, S)
-    if token_type_ids is not None:
-        token_type_ids = _bert_ids("token_type_ids", token_type_ids, B, S)
+    input_ids, attention_mask, token_type_ids, mode, pooled = _bert_args("bert_embed_ragged", binding, input_ids,
+                                                                         attention_mask, token_type_ids, pooling)
+    (B, S), dev, H = input_ids.shape, input_ids.device, binding.params.hidden_size
     if rows_bound is not None and int(rows_bound) < 0:
         raise ValueError(f"rows_bound={rows_bound} must not be negative")
     rows = B * S if rows_bound is None else max(min(int(rows_bound), B * S), min(B, 1))   # the C entry takes >= 1
-    dev = input_ids.device
-    H = binding.params.hidden_size
-    want_hidden = with_hidden or mode == L.GR_BERT_POOL_NONE
-    pooled = torch.empty((B, H), dtype=torch.float32, device=dev) if mode != L.GR_BERT_POOL_NONE else None
+    want_hidden = with_hidden or pooled is None
     hidden = torch.empty((rows, H), dtype=torch.float32, device=dev) if want_hidden else None
     offsets = torch.zeros((B + 1,), dtype=torch.int64, device=dev) if want_hidden else None
     if B > 0:

@@ -994,7 +994,8 @@ int gr_bert_embed_ragged_f32(const gr_bert_params* p, const int64_t* input_ids, 
                              int64_t* row_offsets_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* The same encoder with bf16 GEMM operands and fp32 accumulation: an opt-in second precision.  The fp32
- * entries above keep their kernels and their bits.  bf16 = the upper 16 bits of the RNE-rounded fp32.
+ * entries above keep their bits (one GEMM kernel and one layer loop serve both precisions).  bf16 = the
+ * upper 16 bits of the RNE-rounded fp32.
  *
  * Numerics contract:
  *   GEMM operands: the A and B operands of the four projections per layer (the fused q/k/v, the attention
